@@ -7,6 +7,11 @@ persistent HIP chain kernel (reads and candidates already resident in HBM),
 overlap records back on the host, and for N>1 one RCCL gather of the records
 to rank 0.  value = DP cells of all ranks / max-over-ranks time (GCUPS).
 
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs if asked and prints
+one JSON line.  Everything else the benchmark measures or checks (the one-at-a-time and roofline
+legs, parity gates, CPU baselines, other configurations and variants, config4_strong, the
+reference's caller) runs with --full.
+
 N>1 is launched by the driver as
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
@@ -140,6 +145,22 @@ def seed_floor_slots_per_cell(linear):
 
 
 PMC_MAX_DRIFT = 0.08         # a committed PMC pass whose kernel time is further than this from the live one is not quoted
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, recs):
+    """--dump-outputs: the records the timed path delivered in its last step, DIR/<field>.npy per field as float64 (the
+    int32 fields and the int64 cell counts are exact in it).  Where all of them would exceed DUMP_LIMIT_BYTES, a fixed,
+    seeded sample of records, the same rows in every field, and the rows taken in DIR/sample_rows.npy."""
+    import numpy as np
+    fields = [f for f in recs.dtype.names if f != "reserved"]
+    if len(recs) * 8 * len(fields) > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(len(recs), DUMP_LIMIT_BYTES // (8 * (len(fields) + 1)), replace=False))
+        recs = recs[rows]
+        fields.append("sample_rows")
+    os.makedirs(path, exist_ok=True)
+    for f in fields:
+        np.save(os.path.join(path, f + ".npy"), (rows if f == "sample_rows" else recs[f]).astype(np.float64))
 
 
 def main_kernel_name(st):
@@ -228,16 +249,16 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--force-dist", action="store_true", help="use torch.distributed even at N=1")
     ap.add_argument("--no-others", action="store_true",
-                    help="skip what a default N=1 run appends: the other single-GPU configurations (pacbio50mb, ont; other_configs) "
+                    help="skip what a --full N=1 run appends: the other single-GPU configurations (pacbio50mb, ont; other_configs) "
                          "and the headline workload off its fastest kernels (variants)")
     ap.add_argument("--slots", type=int, default=4,
                     help="engine slots the timed steps alternate over (steps in flight at once: the fetch of step k is taken after "
                          "step k+S-1 has been launched).  1: every step is launched, waited for and fetched before the next")
-    ap.add_argument("--only-variants", action="store_true", help="of what a default N=1 run appends, the variants alone (profiling)")
+    ap.add_argument("--only-variants", action="store_true", help="of what a --full N=1 run appends, the variants alone (profiling)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default): one genome block of --workload per rank, per-GPU work fixed; strong: the FIXED job "
                          "`--workload config4` (eight pacbio50mb genome blocks, 40,000 reads, 2.67 M candidates) dealt over the N ranks")
-    ap.add_argument("--no-config4", action="store_true", help="skip the config4_strong entry every default line carries")
+    ap.add_argument("--no-config4", action="store_true", help="skip the config4_strong entry every --full line carries")
     ap.add_argument("--no-reference-caller", action="store_true",
                     help="skip the reference's own unmodified darwin.cpp on the engine (a child process behind the timed region, N = 1)")
     ap.add_argument("--no-cabi-gather-check", action="store_true", help="N > 1: skip the second gather through the C-ABI's own RCCL path")
@@ -250,7 +271,16 @@ def main():
                     help="the whole N > 1 path -- block exchange, deal, steps in flight, gather, checksums -- with every rank on device 0 "
                          "and the collectives over gloo on host tensors (RCCL refuses two ranks on one device): a rehearsal, not a "
                          "measurement; the line says so")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the one-at-a-time and roofline legs, the parity gates and checks, the "
+                         "CPU baselines, the other configurations and variants, config4_strong, the reference's caller.  Without it "
+                         "a run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path delivered in its last step (its overlap records) into DIR, one float64 "
+                         "<field>.npy per record field (a fixed, seeded sample of the records above %d MB in all)" % (DUMP_LIMIT_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
     if args.workload == "config4":
         args.scaling = "strong"
     if args.scaling == "strong" and args.workload not in ("config4", "ecoli10x"):
@@ -386,43 +416,50 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     eng.set_option("runs_in_flight", 0)
-    # the same steps one at a time (launched, waited for, fetched), as the figure of rounds 1-2: `single_slot`
-    n_single, dt_single = args.steps, dt / max(args.steps, 1)
-    if S > 1:
-        n_single = min(5, max(2, args.steps))
-        t1 = time.perf_counter()
-        run_steps(n_single, 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rec if rec is not None else np.concatenate(gathered))
+    # the kernels the timed steps ran (the last one's slot): the line's dtype
+    head_st = eng.last_run_stats((args.steps - 1) % S)
+    if args.full:
+        # the same steps one at a time (launched, waited for, fetched), as the figure of rounds 1-2: `single_slot`
+        n_single, dt_single = args.steps, dt / max(args.steps, 1)
+        if S > 1:
+            n_single = min(5, max(2, args.steps))
+            t1 = time.perf_counter()
+            run_steps(n_single, 1)
+            barrier()
+            dt_single = (time.perf_counter() - t1) / n_single
+        single_overlapped = bool(eng.last_run_stats(0)["overlapped_seeding"]) if nf + nr else False
+        single_lane = bool(eng.last_run_stats(0).get("critical_lane", False)) if nf + nr else False
+        # ... and once more in the engine's plain sequence -- seed launch, then ONE main launch on the whole machine -- for the
+        # per-kernel HIP-event times of `roofline`: a kernel's own duration is the time the chip spent on it only when it runs
+        # alone (inside the timed region the kernels of S steps share the machine; and one at a time the engine seeds most of a
+        # run beside two main launches, gact_hip_run_stats.overlapped_seeding)
+        n_roof = min(4, max(2, args.steps))
+        eng.set_option("overlap_seed", 0)
+        run_steps(1, 1)
+        t2 = time.perf_counter()
+        run_steps(n_roof, 1, record_ms=True)
         barrier()
-        dt_single = (time.perf_counter() - t1) / n_single
-    single_overlapped = bool(eng.last_run_stats(0)["overlapped_seeding"]) if nf + nr else False
-    single_lane = bool(eng.last_run_stats(0).get("critical_lane", False)) if nf + nr else False
-    # ... and once more in the engine's plain sequence -- seed launch, then ONE main launch on the whole machine -- for the
-    # per-kernel HIP-event times of `roofline`: a kernel's own duration is the time the chip spent on it only when it runs
-    # alone (inside the timed region the kernels of S steps share the machine; and one at a time the engine seeds most of a
-    # run beside two main launches, gact_hip_run_stats.overlapped_seeding)
-    n_roof = min(4, max(2, args.steps))
-    eng.set_option("overlap_seed", 0)
-    run_steps(1, 1)
-    t2 = time.perf_counter()
-    run_steps(n_roof, 1, record_ms=True)
-    barrier()
-    dt_roof = (time.perf_counter() - t2) / n_roof
-    eng.set_option("overlap_seed", 1)
+        dt_roof = (time.perf_counter() - t2) / n_roof
+        eng.set_option("overlap_seed", 1)
     if rec is None:          # distributed run: the engine's full records of this rank, for the cell count and the parity gate
         rec = eng.candidates_fetch(nf + nr, slot=0, out=rec_bufs[0])
-        # what rank 0 gathered of EVERY rank is what that rank's engine holds (checksums, one all_gather)
-        try:
-            rank_sums = gdist.verify_gathered(torch, dist, gdist.lines_from_overlaps(rec), gathered, rank, world, CDEV)
-        except RuntimeError as err:
-            raise SystemExit("bench.py: %s" % err)
-        # the same gather once more through the C-ABI's own RCCL path (gact_hip_comm_*, what host/darwin_hip --rccl-gather
-        # uses), outside the timed region, compared on rank 0 with what torch.distributed delivered
-        cpp_gather = {"ok": None, "skipped": "--no-cabi-gather-check" if args.no_cabi_gather_check else "gloo rehearsal on one device"} \
-            if (args.no_cabi_gather_check or args.rehearse_on_one_device) else \
-            cpp_gather_check(eng, dist, torch, rank, world, nf + nr, gathered)
-    for k in sorted(ran - {0}):    # every slot that took a step holds the same records
-        if eng.candidates_fetch(nf + nr, slot=k).tobytes() != eng.candidates_fetch(nf + nr, slot=0).tobytes():
-            raise SystemExit("bench.py: slot %d's records differ from slot 0's" % k)
+        if args.full:
+            # what rank 0 gathered of EVERY rank is what that rank's engine holds (checksums, one all_gather)
+            try:
+                rank_sums = gdist.verify_gathered(torch, dist, gdist.lines_from_overlaps(rec), gathered, rank, world, CDEV)
+            except RuntimeError as err:
+                raise SystemExit("bench.py: %s" % err)
+            # the same gather once more through the C-ABI's own RCCL path (gact_hip_comm_*, what host/darwin_hip --rccl-gather
+            # uses), outside the timed region, compared on rank 0 with what torch.distributed delivered
+            cpp_gather = {"ok": None, "skipped": "--no-cabi-gather-check" if args.no_cabi_gather_check else "gloo rehearsal on one device"} \
+                if (args.no_cabi_gather_check or args.rehearse_on_one_device) else \
+                cpp_gather_check(eng, dist, torch, rank, world, nf + nr, gathered)
+    if args.full:
+        for k in sorted(ran - {0}):    # every slot that took a step holds the same records
+            if eng.candidates_fetch(nf + nr, slot=k).tobytes() != eng.candidates_fetch(nf + nr, slot=0).tobytes():
+                raise SystemExit("bench.py: slot %d's records differ from slot 0's" % k)
     rf, rr = rec[:nf], rec[nf:]
 
     my_cells = int(rf["cells"].sum() + rr["cells"].sum())
@@ -439,15 +476,40 @@ def main():
         tot_tiles = my_tiles
 
     gen_all = None
-    if use_dist:
+    if use_dist and args.full:
         g = [torch.zeros(1, dtype=torch.float64, device=CDEV) for _ in range(world)]
         dist.all_gather(g, torch.tensor([t_gen], dtype=torch.float64, device=CDEV))
         gen_all = [round(float(x.item()), 1) for x in g]
     if rank == 0:
         gcups = tot_cells * args.steps / max_dt / 1e9
+        out = {
+            "metric": "GACT GCUPS (DP cells/s) on ~10 kb PacBio-shape reads",
+            "value": round(gcups, 2), "unit": "GCUPS", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(max_dt / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": ("int16x2 (packed)" if head_st["seed_layout"] == "packed16"
+                      else "int16x2 (packed) main kernel, int32 seed kernel") if head_st["packed16"] else "int32",
+            "data": "synthetic",
+            "config": {"workload": args.workload + "_self_overlap", "candidate_source": args.candidates, "tile_size": 320, "tile_overlap": 120,
+                       "scoring": "%+d/%+d/%+d/%+d" % scoring, "reads": len(reads), "bases": int(offs[-1]),
+                       "candidates": int(len(cf_all) + len(cr_all)), "tiles": tot_tiles,
+                       "cells_per_step": tot_cells, "parallelism": "candidates dealt round-robin over %d GPU(s)" % world,
+                       # steps in flight: step k's records are fetched after step k+S-1 has been launched, each step on an engine
+                       # slot of its own (stream, queues, workspace) -- what the reference's 8 feeder threads with a GPU_storage
+                       # each do (darwin.cpp:619-629); every step is complete, records on the host, inside the timed region
+                       "slots_in_flight": S,
+                       # every pass over the candidate list this process made (warm-up, timed region, and with --full the
+                       # one-at-a-time leg, the roofline leg and its warm-up): what a profile of this command has to be divided by
+                       "passes_in_this_process": args.warmup + args.steps + ((n_single if S > 1 else 0) + 1 + n_roof if args.full else 0),
+                       "arch": info["arch"], "gen_seconds": round(t_gen, 1)},
+        }
+        if gathered is not None:
+            out["config"]["gathered_records"] = int(sum(len(g) for g in gathered))
+            if args.rehearse_on_one_device:
+                out["config"]["rehearsal"] = "every rank on device 0, collectives over gloo on host tensors: the N > 1 code path, not a measurement"
+    if rank == 0 and args.full:
         # dominant kernel: the main launch (packed-int16 extend_p16_kernel, or the int32 extend_kernel when
         # the scoring does not fit int16); HIP events on its own stream, this rank
-        packed = kernel_ms[-1]["packed16"]
         k_ms = float(np.mean([k["main_ms"] for k in kernel_ms]))
         seed_ms = float(np.mean([k["seed_ms"] for k in kernel_ms]))
         seed_cells = int(kernel_ms[-1]["seed_cells"])
@@ -553,42 +615,18 @@ def main():
             "source": (pmc_d["source"] + " (SQ_INSTS_VALU of every kernel of %d profiled steps / steps; utilisation = that x 2 cycles / "
                        "(1024 SIMDs x %d MHz x ms_per_step))" % (pmc_d["steps_profiled"], info["clock_mhz"])) if pmc_d else None,
         }
-        out = {
-            "metric": "GACT GCUPS (DP cells/s) on ~10 kb PacBio-shape reads",
-            "value": round(gcups, 2), "unit": "GCUPS", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(max_dt / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": ("int16x2 (packed)" if kernel_ms[-1]["seed_layout"] == "packed16"
-                      else "int16x2 (packed) main kernel, int32 seed kernel") if packed else "int32",
-            "data": "synthetic",
-            "config": {"workload": args.workload + "_self_overlap", "candidate_source": args.candidates, "tile_size": 320, "tile_overlap": 120,
-                       "scoring": "%+d/%+d/%+d/%+d" % scoring, "reads": len(reads), "bases": int(offs[-1]),
-                       "candidates": int(len(cf_all) + len(cr_all)), "tiles": tot_tiles,
-                       "cells_per_step": tot_cells, "parallelism": "candidates dealt round-robin over %d GPU(s)" % world,
-                       # steps in flight: step k's records are fetched after step k+S-1 has been launched, each step on an engine
-                       # slot of its own (stream, queues, workspace) -- what the reference's 8 feeder threads with a GPU_storage
-                       # each do (darwin.cpp:619-629); every step is complete, records on the host, inside the timed region
-                       "slots_in_flight": S,
-                       # every pass over the candidate list this process made (warm-up, timed region, the one-at-a-time leg, the
-                       # roofline leg and its warm-up): what a profile of this command has to be divided by
-                       "passes_in_this_process": args.warmup + args.steps + (n_single if S > 1 else 0) + 1 + n_roof,
-                       "arch": info["arch"], "gen_seconds": round(t_gen, 1)},
-            "roofline": roofline,
-            # the same pass one step at a time (launch, wait, fetch, then the next): the figure of rounds 1 and 2
-            "single_slot": {"value": round(my_cells * (world if use_dist else 1) / dt_single / 1e9, 2) if not use_dist else None,
-                            "ms_per_step": round(dt_single * 1e3, 3), "steps": n_single,
-                            # (one at a time the engine seeds a run of this size in length order, most of it beside the main
-                            #  launch: gact_hip_run_stats.overlapped_seeding)
-                            "overlapped_seeding": single_overlapped,
-                            # (... and a wide launch beside the split one takes the longest chains: gact_hip_run_stats.critical_lane)
-                            "critical_lane": single_lane},
-        }
+        out["roofline"] = roofline
+        # the same pass one step at a time (launch, wait, fetch, then the next): the figure of rounds 1 and 2
+        out["single_slot"] = {"value": round(my_cells * (world if use_dist else 1) / dt_single / 1e9, 2) if not use_dist else None,
+                              "ms_per_step": round(dt_single * 1e3, 3), "steps": n_single,
+                              # (one at a time the engine seeds a run of this size in length order, most of it beside the main
+                              #  launch: gact_hip_run_stats.overlapped_seeding)
+                              "overlapped_seeding": single_overlapped,
+                              # (... and a wide launch beside the split one takes the longest chains: gact_hip_run_stats.critical_lane)
+                              "critical_lane": single_lane}
         if gathered is not None:
             # what the one RCCL gather delivered: records per rank and each rank's own checksum of what it sent (compared on
             # rank 0 with what arrived, dist.verify_gathered), the seconds every rank took to build its block
-            out["config"]["gathered_records"] = int(sum(len(g) for g in gathered))
-            if args.rehearse_on_one_device:
-                out["config"]["rehearsal"] = "every rank on device 0, collectives over gloo on host tensors: the N > 1 code path, not a measurement"
             out["config"]["gather"] = {"ranks": world, "records_per_rank": [int(len(g)) for g in gathered],
                                        "crc32_per_rank": rank_sums if isinstance(rank_sums, list) else None,
                                        "gen_seconds_per_rank": gen_all, "c_abi_rccl_gather": cpp_gather}
@@ -606,8 +644,8 @@ def main():
                 out["feeder_threads"] = feeder_config(args.workload, cat, offs, rcat, my_cf, my_cr, rec)
                 out["other_configs"] = [side_config(w, args) for w in ("pacbio50mb", "ont")]
             out["variants"] = [variant_config(v, args.workload, reads, my_cf, my_cr) for v in VARIANTS]
-    # ---- the fixed eight-block job of BASELINE config 4 dealt over these N ranks (strong scaling): every default line carries it
-    if not args.no_config4 and not args.only_variants and not _CPP_GATHER_STUCK and args.workload == "ecoli10x":
+    # ---- the fixed eight-block job of BASELINE config 4 dealt over these N ranks (strong scaling): every --full line carries it
+    if args.full and not args.no_config4 and not args.only_variants and not _CPP_GATHER_STUCK and args.workload == "ecoli10x":
         if eng is not None:
             eng.close()
             eng = None
@@ -615,7 +653,7 @@ def main():
         if rank == 0:
             out["config4_strong"] = entry
     if rank == 0:
-        if world == 1 and not use_dist and not args.no_reference_caller and args.workload == "ecoli10x" and not args.only_variants:
+        if args.full and world == 1 and not use_dist and not args.no_reference_caller and args.workload == "ecoli10x" and not args.only_variants:
             if eng is not None:
                 eng.close()
                 eng = None
@@ -736,19 +774,27 @@ def config4_strong(args, dist, torch, rank, world, local_rank, use_dist, steps, 
     barrier()
     dt = time.perf_counter() - t1
     eng.set_option("runs_in_flight", 0)
-    # one run at a time on this rank (what a caller that submits its list once sees), outside the timed region
-    t2 = time.perf_counter()
-    launch(0)
-    single_rec = eng.candidates_fetch(nf + nr, slot=0, out=bufs[0]).copy()
-    dt_single = time.perf_counter() - t2
-    st = eng.last_run_stats(0)
-    rec = single_rec
+    if headline and args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rec if rec is not None else np.concatenate(gathered))
+    full = args.full or not headline
+    st = eng.last_run_stats((steps - 1) % S)
+    dt_single = 0.0
+    if full:
+        # one run at a time on this rank (what a caller that submits its list once sees), outside the timed region
+        t2 = time.perf_counter()
+        launch(0)
+        single_rec = eng.candidates_fetch(nf + nr, slot=0, out=bufs[0]).copy()
+        dt_single = time.perf_counter() - t2
+        st = eng.last_run_stats(0)
+        rec = single_rec
+    elif rec is None:        # distributed run: this rank's records, for the cell count
+        rec = eng.candidates_fetch(nf + nr, slot=0, out=bufs[0])
     my_cells, my_tiles = int(rec["cells"].sum()), int(rec["n_tiles"].sum())
     # ---- parity: rank g of EIGHT's share is the golden file's; here it lies on rank g % world, every (8 / world)-th record
     checked = {}
     for g in (0, 5):
         path = os.path.join(ROOT, "tests", "golden", "config_config4_rank%d.npz" % g)
-        if NB % world or g % world != rank or not os.path.exists(path) or args.strong_blocks_of != "pacbio50mb":
+        if not full or NB % world or g % world != rank or not os.path.exists(path) or args.strong_blocks_of != "pacbio50mb":
             continue
         gold = np.load(path)
         stride, first = NB // world, g // world
@@ -778,11 +824,12 @@ def config4_strong(args, dist, torch, rank, world, local_rank, use_dist, steps, 
         per_rank_ms = [r[0] for r in rows]; per_rank_single = [r[1] for r in rows]; builds = [round(r[3], 1) for r in rows]
         all_checked = {"records_checked_against_golden_all_ranks": int(sum(r[2] for r in rows))}
         gather_ms = round(rows[0][4], 3)
-        # what rank 0 gathered of every rank is what that rank's engine holds
-        try:
-            gdist.verify_gathered(torch, dist, gdist.lines_from_overlaps(rec), gathered, rank, world, CDEV)
-        except RuntimeError as err:
-            raise SystemExit("bench.py: config 4: %s" % err)
+        if full:
+            # what rank 0 gathered of every rank is what that rank's engine holds
+            try:
+                gdist.verify_gathered(torch, dist, gdist.lines_from_overlaps(rec), gathered, rank, world, CDEV)
+            except RuntimeError as err:
+                raise SystemExit("bench.py: config 4: %s" % err)
     eng.close()
     if rank != 0:
         return None
@@ -797,13 +844,15 @@ def config4_strong(args, dist, torch, rank, world, local_rank, use_dist, steps, 
         # rank 0 sees it (the wait for the slowest rank included)
         "per_rank_ms_per_step": {"min": round(min(per_rank_ms), 3), "max": round(max(per_rank_ms), 3), "all": [round(x, 3) for x in per_rank_ms]},
         "gather_ms_per_step_rank0": gather_ms,
-        "single_run_ms_per_rank": {"min": round(min(per_rank_single), 2), "max": round(max(per_rank_single), 2)},
         "kernel_layout": st["layout"] + ("-lin" if st["linear_gap"] else "") + ("-roles" if st.get("role_waves") else "-coop" if st.get("coop_walks") else ""),
-        "kernel_ms": round(st["main_ms"], 3), "seed_kernel_ms": round(st["seed_ms"], 3),
-        "parity": dict(all_checked, bit_exact=True, golden="tests/golden/config_config4_rank{0,5}.npz (every record of two ranks of eight, from the oracle)"),
         "build_seconds_per_rank": builds,
         "note": "no scaling curve is claimed from this entry at one N: the driver's 1/2/4/8 runs each carry it" if not headline else None,
     }
+    if full:
+        entry.update({
+            "single_run_ms_per_rank": {"min": round(min(per_rank_single), 2), "max": round(max(per_rank_single), 2)},
+            "kernel_ms": round(st["main_ms"], 3), "seed_kernel_ms": round(st["seed_ms"], 3),
+            "parity": dict(all_checked, bit_exact=True, golden="tests/golden/config_config4_rank{0,5}.npz (every record of two ranks of eight, from the oracle)")})
     if not headline:
         return entry
     # the contract's line for `--scaling strong --workload config4`

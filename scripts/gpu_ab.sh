@@ -9,7 +9,7 @@ for w in ${WORKLOADS:-ecoli10x ont}; do
   for rep in $(seq 1 ${REPS:-3}); do
     for lib in ${LIBS:-darwin-gpu_amd/libgact_hip.so}; do
       name=$(basename $lib .so)
-      GACT_HIP_LIB_PATH=$R/$lib timeout -k 10 280 python $R/bench.py --workload $w --steps ${STEPS:-10} --warmup 3 --no-cpu --no-others > $OUT/${w}_${name}_$rep.json 2> $OUT/${w}_${name}_$rep.err
+      GACT_HIP_LIB_PATH=$R/$lib timeout -k 10 280 python $R/bench.py --full --workload $w --steps ${STEPS:-10} --warmup 3 --no-cpu --no-others > $OUT/${w}_${name}_$rep.json 2> $OUT/${w}_${name}_$rep.err
     done
   done
 done

@@ -9,7 +9,7 @@ for w in ${WORKLOADS:-ecoli10x}; do
   for rep in $(seq 1 ${REPS:-3}); do
     for cs in "${CS[@]}"; do
       IFS='|' read -r name lib envs <<< "$cs"
-      env GACT_HIP_LIB_PATH=$R/$lib $envs timeout -k 10 280 python $R/bench.py --workload $w --steps ${STEPS:-10} --warmup 3 --no-cpu --no-others > $OUT/${w}_${name}_$rep.json 2> $OUT/${w}_${name}_$rep.err || echo "FAILED $w $name $rep: $(tail -n 2 $OUT/${w}_${name}_$rep.err)"
+      env GACT_HIP_LIB_PATH=$R/$lib $envs timeout -k 10 280 python $R/bench.py --full --workload $w --steps ${STEPS:-10} --warmup 3 --no-cpu --no-others > $OUT/${w}_${name}_$rep.json 2> $OUT/${w}_${name}_$rep.err || echo "FAILED $w $name $rep: $(tail -n 2 $OUT/${w}_${name}_$rep.err)"
     done
   done
 done

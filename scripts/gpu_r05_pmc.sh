@@ -4,7 +4,7 @@
 # usage: TAG=r05_pmc [PART=roles|ont|all] bash scripts/gpu_r05_pmc.sh
 R=$GRAFT_REPO_ROOT
 TAG=${TAG:-r05_pmc}
-B="python3 $R/bench.py --slots 1 --steps 1 --warmup 0 --no-cpu --no-others --no-config4 --no-reference-caller"
+B="python3 $R/bench.py --full --slots 1 --steps 1 --warmup 0 --no-cpu --no-others --no-config4 --no-reference-caller"
 if [ "${PART:-all}" != ont ]; then
   for m in old roles; do
     if [ $m = roles ]; then envv="GACT_HIP_ROLES=1"; else envv="X=1"; fi

@@ -1,3 +1,6 @@
+import gzip
+import hashlib
+import json
 import os
 import sys
 
@@ -19,12 +22,55 @@ def oracle():
     return oracle_py.Oracle()
 
 
+REFERENCE_CALLS = os.path.join(ROOT, "tests", "golden", "reference_calls.json.gz")
+
+
+class ReferenceCalls:
+    """The reference's own answers (oracle_py.RefLib) to the calls the tests make, keyed by the call.  With `live` every
+    call goes to the library and is kept for save() (tests/golden/make_reference_calls.py); without it the answers come
+    from REFERENCE_CALLS, so that the tests stand where oracle/_ref cannot be built."""
+
+    def __init__(self, live=None):
+        self.live, self.calls = live, {}
+        if live is None:
+            with gzip.open(REFERENCE_CALLS, "rt") as f:
+                self.calls = json.load(f)
+
+    def _call(self, name, *args, **kwargs):
+        key = hashlib.sha256(repr((name, args, sorted(kwargs.items()))).encode()).hexdigest()
+        if self.live is not None:
+            self.calls[key] = getattr(self.live, name)(*args, **kwargs)
+            return self.calls[key]
+        if key not in self.calls:
+            pytest.skip("oracle/_ref/libdarwin_ref.so not built and this call is not in %s" % os.path.relpath(REFERENCE_CALLS, ROOT))
+        res = self.calls[key]
+        return [[tuple(c) for c in q] for q in res] if name == "dsoft_candidates" else res
+
+    def dsoft_candidates(self, *args, **kwargs):
+        return self._call("dsoft_candidates", *args, **kwargs)
+
+    def align_with_bt(self, *args, **kwargs):
+        return self._call("align_with_bt", *args, **kwargs)
+
+    def gact_line(self, *args, **kwargs):
+        return self._call("gact_line", *args, **kwargs)
+
+    def save(self):
+        with gzip.GzipFile(REFERENCE_CALLS, "wb", mtime=0) as f:
+            f.write(json.dumps(self.calls, sort_keys=True, separators=(",", ":")).encode())
+
+
 @pytest.fixture(scope="session")
 def reflib():
     import oracle_py
     if not oracle_py.ref_available():
-        pytest.skip("oracle/_ref/libdarwin_ref.so not built (reference not mounted)")
-    return oracle_py.RefLib()
+        yield ReferenceCalls()
+    elif os.environ.get("GACT_RECORD_REFERENCE_CALLS"):
+        rec = ReferenceCalls(live=oracle_py.RefLib())
+        yield rec
+        rec.save()
+    else:
+        yield oracle_py.RefLib()
 
 
 @pytest.fixture(scope="session")

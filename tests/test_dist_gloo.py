@@ -57,7 +57,7 @@ def _worker(rank, world, port, q):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_two_ranks_gather_equals_single_process(world):
-    import torch.multiprocessing as mp
+    import multiprocessing as mp          # (not torch's: torch stays out of the pytest process, see test_cabi.py)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
@@ -101,7 +101,7 @@ def _strong_worker(rank, world, port, q):
 def test_fixed_job_of_blocks_over_ranks(world):
     """every rank ends up with the job a single process builds, whatever the number of ranks (strong scaling)"""
     import zlib
-    import torch.multiprocessing as mp
+    import multiprocessing as mp          # (not torch's: torch stays out of the pytest process, see test_cabi.py)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, os.path.join(root, "darwin-gpu_amd"))
     from gact_amd import dist as gdist, workload
@@ -165,7 +165,7 @@ def _pipeline_worker(rank, world, port, q):
 
 
 def test_steps_in_flight_gather_in_launch_order():
-    import torch.multiprocessing as mp
+    import multiprocessing as mp          # (not torch's: torch stays out of the pytest process, see test_cabi.py)
     world = 2
     ctx = mp.get_context("spawn")
     q = ctx.Queue()

@@ -30,7 +30,7 @@ def _env():
 
 @pytest.mark.parametrize("slots,steps", [(4, 6), (4, 2), (1, 2)], ids=["four-in-flight", "fewer-steps-than-slots", "one-at-a-time"])
 def test_bench_force_dist_as_a_child_process(slots, steps):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--workload", "ecoli10x_small",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-dist", "--workload", "ecoli10x_small",
                           "--steps", str(steps), "--warmup", "1", "--cpu-seconds", "2", "--slots", str(slots)], capture_output=True,
                          text=True, cwd=ROOT, env=_env(), timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
@@ -54,7 +54,7 @@ def _two_ranks_on_one_device(extra, timeout=900):
     for r in range(2):
         env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2",
                    LOCAL_WORLD_SIZE="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-on-one-device"] + extra,
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--rehearse-on-one-device"] + extra,
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, env=env))
     outs = [p.communicate(timeout=timeout) for p in procs]
     for p, (so, se) in zip(procs, outs):

@@ -31,7 +31,7 @@ for f in glob.glob(os.path.join(root, "**", "*counter_collection.csv"), recursiv
             seen.add(key)
             k["dispatches"] += 1
 total = sum(k["SQ_INSTS_VALU"] for k in kernels.values())
-print(json.dumps({"command": "bench.py --workload %s --no-others --no-cpu (default slots, steps, warm-up) under rocprofv3 --pmc SQ_INSTS_VALU GRBM_GUI_ACTIVE"
+print(json.dumps({"command": "bench.py --full --workload %s --no-others --no-cpu (default slots, steps, warm-up) under rocprofv3 --pmc SQ_INSTS_VALU GRBM_GUI_ACTIVE"
                              % bench["config"]["workload"].replace("_self_overlap", ""),
                   "workload": bench["config"]["workload"], "cells_per_step": bench["config"]["cells_per_step"],
                   "steps_profiled": steps, "slots_in_flight": bench["config"]["slots_in_flight"],
