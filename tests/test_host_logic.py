@@ -107,6 +107,22 @@ def test_launch_policy_operating_points():
     assert "gact_big" in _plan(10, tile_size=1024, tile_overlap=256)["sequence"]
 
 
+def test_int16_guard_edges_pin_the_plan(monkeypatch):
+    """tests/scoring_edges.py's table: the plan at the last scoring each int16 guard admits and one step past it, at a count
+    of 100 (wide layout) and 2 * S (split layout).  A change to any of the five predicates must change this table."""
+    from scoring_edges import EDGES, S
+    for var in ("GACT_HIP_FORCE_INT32", "GACT_HIP_FORCE_UNIFORM", "GACT_HIP_FORCE_INT32_SEED", "GACT_HIP_FORCE_WIDE",
+                "GACT_HIP_NO_WIDE", "GACT_HIP_NO_TAGGED", "GACT_HIP_NO_LIN", "GACT_HIP_NO_AFF", "GACT_HIP_COOP"):
+        monkeypatch.delenv(var, raising=False)
+    for e in EDGES:
+        for scoring, want in ((e.last, e.at_last), (e.past, e.at_past)):
+            for count, main in ((2 * S, want.split), (100, want.wide)):
+                p = _plan(count, tile_size=e.tile, tile_overlap=e.overlap, scoring=scoring)
+                got = (p["seed_kernel"], p["main_kernel"])
+                assert got == (want.seed, main), (e.name, e.guard, scoring, count, p)
+                assert (p["sequence"] == "int32-one-launch") == (main == "-"), (e.name, scoring, count, p)
+
+
 def test_launch_policy_is_sane_over_a_sweep_of_counts():
     """1 ... 3 M candidates: grids never exceed the machine, never shrink as the list grows inside one sequence, every
     candidate of a list up to the resident tile slots has a slot of its own, and the two launches of a split sequence

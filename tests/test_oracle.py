@@ -100,6 +100,46 @@ def test_oracle_equals_reference_chains(oracle, reflib):
     assert n > 10
 
 
+def test_oracle_equals_reference_tiles_at_int16_edges(oracle, reflib):
+    """every scoring of tests/scoring_edges.py (the last one each int16 guard admits and the first one past it) on the
+    adversarial tiles at its tile size: the oracle the GPU edge tests compare against must itself follow the reference
+    there"""
+    from scoring_edges import adversarial_tiles, scorings
+    n = 0
+    for tile, overlap, sc in scorings():
+        for a, b, rev, first in adversarial_tiles(tile, overlap):
+            early = tile - overlap
+            assert oracle.align_with_bt(a, b, sc, rev, first, early) == reflib.align_with_bt(a, b, sc, rev, first, early), \
+                (tile, overlap, sc, len(a), len(b), rev, first)
+            n += 1
+    assert n > 600
+
+
+def test_oracle_equals_reference_chains_at_int16_edges(oracle, reflib):
+    """... and whole chains on the edge read sets: exact copies, gap runs, disjoint alphabets, repeats, boundary lengths
+    and N, both strands"""
+    from gact_amd import synth
+    from scoring_edges import EDGES, edge_reads, threshold
+    n = 0
+    for e in EDGES:
+        er = edge_reads(e.tile, e.overlap)
+        for sc in (e.last, e.past):
+            thr = threshold(e, sc)
+            for comp, lists in ((False, (er.clean_f, er.raw_f)), (True, (er.clean_r, er.raw_r))):
+                for cands in lists:
+                    for c in cands[::max(1, len(cands) // 3)][:3]:
+                        r = er.rs.reads[c["ref_id"]].tobytes()
+                        q = er.rs.reads[c["query_id"]]
+                        q = (synth.revcomp(q) if comp else q).tobytes()
+                        kw = dict(tile_size=e.tile, tile_overlap=e.overlap, threshold=thr, ref_id=int(c["ref_id"]),
+                                  query_id=int(c["query_id"]), complement=comp, scoring=sc)
+                        ov, _ = oracle.gact(r, q, int(c["ref_pos"]), int(c["query_pos"]), **kw)
+                        line = oracle.format_line(ov, "r", "q") if ov.emitted else ""
+                        assert line == reflib.gact_line(r, q, int(c["ref_pos"]), int(c["query_pos"]), **kw), (e.name, sc, c)
+                        n += 1
+    assert n > 500
+
+
 def test_gact_many_threads_agree(oracle):
     from gact_amd import synth
     rs = synth.simulate_reads(9000, n_reads=8, seed=3, mean_len=2500, sd_len=500, min_len=800, max_len=4000)
