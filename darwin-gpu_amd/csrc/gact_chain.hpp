@@ -505,6 +505,15 @@ __device__ __forceinline__ void walk_chain_lin_team(uint32_t *scratch, const boo
     // (open == extend: the gap bookkeeping of wk decides nothing)
 }
 
+// Path runs (gact_path.hpp): where walk_chain<..., PATH = true> writes one GACT_PATH_OP_* byte per alignment column.
+// The left phase's columns arrive right to left and are written downwards, the right phase's left to right and upwards;
+// a byte outside [lo, hi) is not written (the cursor moves on, so the count still says how many columns there were).
+struct PathCursor {
+    uint8_t *p;                   // the next column's byte
+    uint8_t *lo, *hi;             // the bytes this phase may write
+    int dir;                      // -1 left phase, +1 right phase
+};
+
 // The chain kernels' walker: traceback (align.cpp:185-230) fused with the rescoring
 // of gact.cpp:197-210, written for few instructions per step -- every step of a
 // walker is a whole wave instruction however few lanes walk, and a tile's walk is
@@ -527,14 +536,16 @@ __device__ __forceinline__ void walk_chain_lin_team(uint32_t *scratch, const boo
 // rrow/qrow point at the LDS byte of DP row 1 / column 1; rstride is the ref stream's
 // byte stride.  (l0, c0, k0) = lane, column-in-lane and stored step of the start cell
 // (R, Q) in the pass's layout; CW columns per lane, QN column quads stored per lane.
+// PATH (FMT 0 only, the path run's int32 chain kernel): every column's GACT_PATH_OP_* byte goes out through *path.
 //
-template <int CW, int FMT, int QN = CW / 4, int ROW = kGroup>
+template <int CW, int FMT, int QN = CW / 4, int ROW = kGroup, bool PATH = false>
 __device__ __forceinline__ void walk_chain(const uint32_t *ws, uint32_t *scratch, int R, int Q, int l0, int c0, int k0,
                                            int early, const uint8_t *rrow, int rstride, const uint8_t *qrow,
                                            int phase, const KParams &kp, ScoreWalk &wk, int &ref_steps,
                                            int &query_steps, int &nst, int v0 = 0, const uint32_t *ws_all = nullptr,
-                                           const int band_lim = -1, bool *redo = nullptr)
+                                           const int band_lim = -1, bool *redo = nullptr, PathCursor *path = nullptr)
 {
+    static_assert(!PATH || FMT == 0, "paths are emitted by the int32 chain kernel's walk");
     if constexpr (FMT == 3) {
         bool rd = false;
         walk_chain_lin<CW, QN, ROW>(ws, scratch, R, Q, l0, c0, k0, early, rrow, rstride, qrow, kp, wk, ref_steps,
@@ -602,6 +613,23 @@ __device__ __forceinline__ void walk_chain(const uint32_t *ws, uint32_t *scratch
     // flags that say the opposite (set = the gap was opened here), and the walk uses them as they are
     constexpr uint32_t kM = (FMT == 2 || AFF) ? 3u : 1u, kI = 2u, kD = (FMT == 2 || AFF) ? 1u : 3u;
     if (left && !wk.have_left && cur != 0) { wk.have_left = 1; wk.left_first_gap = cur != kM; }
+    // PATH: the codes of up to eight columns wait in a register and are stored right behind the refill that follows them
+    // (a store counts in vmcnt like the refill's loads: one stored in front of a refill makes that refill wait for it)
+    uint64_t path_pend = 0;
+    int path_n = 0;
+    auto path_flush = [&]() {
+        if constexpr (PATH) {
+#pragma unroll
+            for (int b = 0; b < 8; b++) {
+                if (b < path_n) {
+                    if (path->p >= path->lo && path->p < path->hi) *path->p = (uint8_t)(path_pend >> (8 * b));
+                    path->p += path->dir;
+                }
+            }
+            path_pend = 0;
+            path_n = 0;
+        }
+    };
     // conditions live as lane masks on the scalar unit; a counter takes one as the carry of a single VALU op
     const uint64_t left_m = lanes(left);
     uint64_t gprev = lanes(left ? wk.pend_gap != 0 : wk.open_flag == 0);
@@ -613,6 +641,13 @@ __device__ __forceinline__ void walk_chain(const uint32_t *ws, uint32_t *scratch
         n_open = add_lane_bit(n_open, (gprev ^ g) & ((left_m & gprev) | (~left_m & g)));
         n_m = add_lane_bit(n_m, ~g);
         n_eq = add_lane_bit(n_eq, ~g & eq);
+        if constexpr (PATH) {
+            // kI (INSERT, GACT_STATE_I) consumes a ref base: SAM's D; kD (DELETE, GACT_STATE_D) a query base: SAM's I
+            const bool same = (eq >> (threadIdx.x & 63)) & 1;
+            const uint32_t op = cur == kM ? (same ? GACT_PATH_OP_EQ : GACT_PATH_OP_X) : cur == kI ? GACT_PATH_OP_D : GACT_PATH_OP_I;
+            path_pend |= (uint64_t)op << (8 * path_n);
+            path_n++;
+        }
         gprev = (gprev & ~lanes(true)) | g;                       // walkers that have stopped keep their last column
         // ---- move (align.cpp:210-229): INSERT / DELETE stay unless their flag says the gap was opened here
         nis = sub_lane_bit(nis, lanes(cur != kD));
@@ -636,12 +671,14 @@ __device__ __forceinline__ void walk_chain(const uint32_t *ws, uint32_t *scratch
             refill(l, c, k);
             // banded stores (gact_lin.hpp LinBand), as in walk_chain_lin
             rd = rd | ((band_lim >= 0) & ((unsigned)(nis - njs + band_lim) > (unsigned)(2 * band_lim)));
+            path_flush();
         }
         uint32_t code;
         fetch(l, c, k, code, fl);
         const uint32_t nxt = cur == kM ? ((AFF && v == 0) ? 0u : code) : forced;
         cur = (nis <= nlim_i || njs <= nlim_j || rd) ? 0u : nxt;       // align.cpp:205, borders :101-107
     }
+    path_flush();
     if (redo) *redo = rd;
     ref_steps = -nis; query_steps = -njs;
     nst = -nis - njs - n_m;

@@ -38,6 +38,7 @@
 #include "gact_coop.hpp"
 #include "gact_policy.hpp"
 #include "gact_big.hpp"
+#include "gact_path.hpp"
 #include "dsoft_device.hpp"
 
 namespace {
@@ -189,6 +190,28 @@ struct Slot {
     size_t reg_bytes = 0;
     int64_t cands_epoch = -1;           // sets_epoch at which the device filter made this slot's list (-1: uploaded list)
     SeqSet inline_ref, inline_query;   // Align_Batch_GPU-style inline tiles
+    // gact_hip_candidates_paths (gact_path.hpp): the path run's own arrays, made on its first call
+    struct PathBufs {
+        DevBuf<gact_candidate> cands;
+        DevBuf<gact_overlap> records;
+        DevBuf<int64_t> col_off, op_off;
+        DevBuf<int32_t> n_cols, n_ops;
+        DevBuf<uint8_t> cols;
+        DevBuf<uint32_t> ops;
+        int *d_counter = nullptr;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;       // around the whole call (gact_hip_last_paths_stats)
+        gact_paths_stats stats{};
+        bool timed = false;
+        void release()
+        {
+            cands.release(); records.release(); col_off.release(); op_off.release();
+            n_cols.release(); n_ops.release(); cols.release(); ops.release();
+            if (d_counter) (void)hipFree(d_counter);
+            if (ev0) (void)hipEventDestroy(ev0);
+            if (ev1) (void)hipEventDestroy(ev1);
+            d_counter = nullptr; ev0 = ev1 = nullptr;
+        }
+    } path;
 };
 
 // device-side D-SOFT filter (dsoft_device.hpp)
@@ -269,6 +292,7 @@ static const OptionDef kOptions[] = {
     {"sdma_copies", "GACT_HIP_SDMA_COPIES", 'c', 's', "candidate lists and records through hipMemcpyAsync instead of a copy kernel"},
     {"dsoft_temp_cap", "GACT_HIP_DSOFT_TEMP_CAP", 'c', 'k', "initial size of the device filter's candidate staging area (tests: forces the regrow path)"},
     {"rccl_lib", "GACT_HIP_RCCL_LIB", 'c', 's', "<file>: the RCCL library gact_hip_comm_create loads"},
+    {"path_budget_mb", "GACT_HIP_PATH_BUDGET_MB", 'c', 's', "<n>: MiB of column buffers a path run (gact_hip_candidates_paths) takes at most; larger selections run in chunks (default 1024)"},
     // diagnostic / tuning: -DGACT_EXPERIMENTS builds only
     {"no_aff_seed", "GACT_HIP_NO_AFF_SEED", 'c', 'd', "round 1's packed seed pass for affine scorings"},
     {"lane_blocks", "GACT_HIP_LANE_BLOCKS", 'c', 'd', "<n>: blocks of the critical lane"},
@@ -368,6 +392,7 @@ struct gact_hip_engine {
     bool overlap_big = false;   // GACT_HIP_OVERLAP_BIG / set_option "overlap_big" (gact_policy.hpp Caps::overlap_big)
     int coop = 0;               // GACT_HIP_COOP / set_option "coop": two banks of tiles per wave and cooperative, batched walks (gact_coop.hpp):
                                 // 0 where throughput bounds the launch (gact_policy.hpp), 1 always, -1 never
+    int64_t path_budget = 1024ll << 20;   // GACT_HIP_PATH_BUDGET_MB: column bytes of one chunk of a path run (gact_hip_candidates_paths)
     int aff_grid_blocks = 0;    // ... of the drifted affine split launch (two blocks per CU)
     int wide_lin_grid_blocks = 0;       // ... of the linear-gap wide launch
     gact::P16Consts kc;
@@ -1312,6 +1337,7 @@ int gact_hip_create(const gact_hip_params *p, gact_hip_engine **out)
         if (p->max_blocks > 0) e->big_blocks = std::max(1, std::min(e->big_blocks, (int)p->max_blocks));
         e->ws_words_total = (size_t)e->big_blocks * per_block / sizeof(uint32_t);
     }
+    if (const char *v = opt_env("path_budget_mb")) e->path_budget = std::max<int64_t>(1, atoll(v)) << 20;
     e->n_user = p->n_slots;
     e->cb.enabled = opt_env("no_combine") == nullptr && !big;
     if (const char *v = opt_env("combine_window_us")) e->cb.window_us = std::max(0, atoi(v));
@@ -1335,6 +1361,7 @@ void gact_hip_destroy(gact_hip_engine *e)
         sl.tiles.release(); sl.results.release(); sl.states.release();
         sl.cands.release(); sl.overlaps.release(); sl.live.release(); sl.chain_states.release(); sl.deferred.release();
         sl.inline_ref.release(); sl.inline_query.release();
+        sl.path.release();
         if (sl.d_counter) (void)hipFree(sl.d_counter);
         if (sl.d_flags) (void)hipFree(sl.d_flags);
         if (sl.d_ws) (void)hipFree(sl.d_ws);
@@ -1974,6 +2001,172 @@ int gact_hip_extend_candidates(gact_hip_engine *e, int slot, int32_t n, const ga
     if (rc) return rc;
     if ((rc = gact_hip_candidates_run(e, slot, n, complement, same_file))) return rc;
     return gact_hip_candidates_fetch(e, slot, n, out);
+}
+
+// The path run (gact_path.hpp).  The host takes the selected candidates (its copy of an uploaded list, else the device
+// filter's list copied back), tags each with its strand (kCompInCand, as a merged run does), and cuts the selection into
+// chunks whose column buffers fit the budget; per chunk: path_kernel, the op count, the counts back, the scan on the host,
+// the op write, the ops back.
+int gact_hip_candidates_paths(gact_hip_engine *e, int slot, int32_t n_sel, const int32_t *sel, int32_t rc_from,
+                              int same_file, gact_overlap *records, gact_path *paths,
+                              uint32_t *ops, int64_t ops_cap, int64_t *ops_needed)
+{
+    int rc = check_slot(e, slot);
+    if (rc) return rc;
+    if (n_sel < 0 || (n_sel > 0 && (!records || !paths)) || ops_cap < 0)
+        return fail(GACT_HIP_EINVAL, "candidates_paths: bad arguments");
+    if (e->big_cb)
+        return fail(GACT_HIP_EINVAL, "candidates_paths: tile_size %d > GACT_HIP_FAST_TILE (%d): paths come from the register-tiled "
+                                     "int32 chain kernel, which the tiles of gact_big.hpp do not run on", e->params.tile_size,
+                    GACT_HIP_FAST_TILE);
+    Slot &sl = e->slots[slot];
+    if (ops_needed) *ops_needed = 0;
+    if (n_sel == 0) return 0;                 // (nothing asked for: also on a slot without candidates, e.g. a feeder with no reads)
+    if (sl.n_cands == 0)
+        return fail(GACT_HIP_EINVAL, "candidates_paths: slot %d holds no candidates (upload a list or run the device filter first)", slot);
+    for (int32_t k = 0; k < n_sel; k++) {
+        const int64_t idx = sel ? sel[k] : k;
+        if (idx < 0 || (size_t)idx >= sl.n_cands)
+            return fail(GACT_HIP_EINVAL, "candidates_paths: sel[%d] = %lld outside the %zu candidates of slot %d", k, (long long)idx,
+                        sl.n_cands, slot);
+    }
+    if ((rc = set_device(e))) return rc;
+    const SeqSet &rs = e->sets[GACT_SET_REF];
+    const SeqSet &qf = e->sets[GACT_SET_QUERY], &qr = e->sets[GACT_SET_QUERY_RC];
+    // the candidates as the host sees them
+    std::vector<gact_candidate> downloaded;
+    const gact_candidate *hc = sl.h_cands.data();
+    if (sl.h_cands.empty()) {
+        if (sl.cands_epoch != e->sets_epoch)
+            return fail(GACT_HIP_EINVAL, "candidates_paths: a read set was uploaded after the device filter made this slot's "
+                                         "candidates; run gact_hip_dsoft_query again");
+        downloaded.resize(sl.n_cands);
+        HIP_TRY(hipMemcpyAsync(downloaded.data(), sl.cands.p, sl.n_cands * sizeof(gact_candidate), hipMemcpyDeviceToHost, sl.stream));
+        HIP_TRY(hipStreamSynchronize(sl.stream));
+        hc = downloaded.data();
+    }
+    // strands, lengths, checks
+    std::vector<gact_candidate> tagged((size_t)n_sel);
+    std::vector<int64_t> cap((size_t)n_sel);
+    bool need_f = false, need_r = false;
+    for (int32_t k = 0; k < n_sel; k++) {
+        const int32_t idx = sel ? sel[k] : k;
+        gact_candidate c = hc[idx];
+        const bool comp = idx >= rc_from;
+        const SeqSet &qs = comp ? qr : qf;
+        (comp ? need_r : need_f) = true;
+        if (rs.n == 0 || qs.n == 0) return fail(GACT_HIP_EINVAL, "candidates_paths: read sets not uploaded");
+        if (c.ref_id < 0 || c.ref_id >= rs.n || c.query_id < 0 || c.query_id >= qs.n)
+            return fail(GACT_HIP_ERANGE, "candidate %d: sequence id out of range", idx);
+        const int64_t rl = rs.h_offsets[c.ref_id + 1] - rs.h_offsets[c.ref_id];
+        const int64_t ql = qs.h_offsets[c.query_id + 1] - qs.h_offsets[c.query_id];
+        if (c.ref_pos < 0 || c.ref_pos > rl || c.query_pos < 0 || c.query_pos > ql)
+            return fail(GACT_HIP_ERANGE, "candidate %d: position outside its read", idx);
+        if (comp) c.query_id |= gact::kCompBit;
+        tagged[(size_t)k] = c;
+        cap[(size_t)k] = rl + ql;                 // every column consumes a base of one of the two reads
+    }
+    const bool raw = rs.has_other || (need_f && qf.has_other) || (need_r && qr.has_other);
+    const gact::SeqSetDev d_rs = rs.dev(raw), d_qf = qf.dev_or(raw, rs), d_qr = qr.dev_or(raw, rs);
+    Slot::PathBufs &pb = sl.path;
+    if (!pb.d_counter && (hipMalloc((void **)&pb.d_counter, sizeof(int)) != hipSuccess || hipEventCreate(&pb.ev0) != hipSuccess ||
+                          hipEventCreate(&pb.ev1) != hipSuccess))
+        return fail(GACT_HIP_ENOMEM, "candidates_paths: device allocation failed");
+    pb.stats = gact_paths_stats{};
+    pb.timed = false;
+    HIP_TRY(hipEventRecord(pb.ev0, sl.stream));
+    const int groups_per_block = (gact::kBlockThreads / 64) * gact::kGroupsPerWave;
+    int64_t total_ops = 0;
+    bool room = ops != nullptr;
+    std::vector<int64_t> col_off, op_off;
+    std::vector<int32_t> n_cols, n_ops;
+    for (int32_t first = 0; first < n_sel;) {
+        // ---- one chunk: as many candidates as the budget holds (at least one)
+        int32_t end = first;
+        int64_t bytes = 0;
+        while (end < n_sel && (end == first || bytes + cap[(size_t)end] <= e->path_budget)) bytes += cap[(size_t)end++];
+        const int32_t n = end - first;
+        col_off.assign((size_t)n + 1, 0);
+        for (int32_t k = 0; k < n; k++) col_off[(size_t)k + 1] = col_off[(size_t)k] + cap[(size_t)(first + k)];
+        if (pb.cands.reserve((size_t)n) || pb.records.reserve((size_t)n) || pb.col_off.reserve((size_t)n + 1) ||
+            pb.op_off.reserve((size_t)n) || pb.n_cols.reserve(2 * (size_t)n) || pb.n_ops.reserve((size_t)n) ||
+            pb.cols.reserve((size_t)bytes + 64))
+            return fail(GACT_HIP_ENOMEM, "candidates_paths: device allocation failed (%d candidates, %lld column bytes)", n, (long long)bytes);
+        HIP_TRY(hipMemcpyAsync(pb.cands.p, tagged.data() + first, (size_t)n * sizeof(gact_candidate), hipMemcpyHostToDevice, sl.stream));
+        HIP_TRY(hipMemcpyAsync(pb.col_off.p, col_off.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, sl.stream));
+        HIP_TRY(hipMemsetAsync(pb.n_cols.p, 0, 2 * (size_t)n * sizeof(int32_t), sl.stream));
+        HIP_TRY(hipMemsetAsync(pb.d_counter, 0, sizeof(int), sl.stream));
+        gact::ChainQueues q{};
+        q.pop_seed = pb.d_counter;
+        q.list_n = -1;
+        const gact::PathArgs pa{pb.cols.p, pb.col_off.p, pb.n_cols.p};
+        // (the slot's workspace is sized for grid_blocks blocks of the chain kernels)
+        const int blocks = std::max(1, std::min((n + groups_per_block - 1) / groups_per_block, e->grid_blocks));
+        if (e->C == 20)
+            hipLaunchKernelGGL((gact::path_kernel<20>), dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, d_rs, d_qf, d_qr,
+                               pb.cands.p, n, gact::kCompInCand, same_file, pb.records.p, q, pa, sl.d_ws);
+        else
+            hipLaunchKernelGGL((gact::path_kernel<32>), dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, d_rs, d_qf, d_qr,
+                               pb.cands.p, n, gact::kCompInCand, same_file, pb.records.p, q, pa, sl.d_ws);
+        HIP_TRY(hipGetLastError());
+        const int op_blocks = std::max(1, std::min((n + 3) / 4, 4096));
+        hipLaunchKernelGGL(gact::path_ops_kernel<false>, dim3(op_blocks), dim3(256), 0, sl.stream, pb.cols.p, pb.col_off.p, pb.n_cols.p,
+                           n, pb.n_ops.p, nullptr, nullptr);
+        HIP_TRY(hipGetLastError());
+        n_cols.resize(2 * (size_t)n);
+        n_ops.resize((size_t)n);
+        HIP_TRY(hipMemcpyAsync(records + first, pb.records.p, (size_t)n * sizeof(gact_overlap), hipMemcpyDeviceToHost, sl.stream));
+        HIP_TRY(hipMemcpyAsync(n_cols.data(), pb.n_cols.p, 2 * (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
+        HIP_TRY(hipMemcpyAsync(n_ops.data(), pb.n_ops.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
+        HIP_TRY(hipStreamSynchronize(sl.stream));
+        // ---- the exclusive scan of the counts, and the ops themselves where the caller has room for them
+        op_off.resize((size_t)n);
+        int64_t chunk_ops = 0;
+        for (int32_t k = 0; k < n; k++) {
+            op_off[(size_t)k] = chunk_ops;
+            gact_path &p = paths[first + k];
+            p.op_offset = total_ops + chunk_ops;
+            p.n_ops = n_ops[(size_t)k];
+            p.n_columns = n_cols[2 * (size_t)k] + n_cols[2 * (size_t)k + 1];
+            chunk_ops += n_ops[(size_t)k];
+        }
+        room = room && total_ops + chunk_ops <= ops_cap;
+        if (room && chunk_ops > 0) {
+            if (pb.ops.reserve((size_t)chunk_ops)) return fail(GACT_HIP_ENOMEM, "candidates_paths: device allocation failed (%lld ops)", (long long)chunk_ops);
+            HIP_TRY(hipMemcpyAsync(pb.op_off.p, op_off.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, sl.stream));
+            hipLaunchKernelGGL(gact::path_ops_kernel<true>, dim3(op_blocks), dim3(256), 0, sl.stream, pb.cols.p, pb.col_off.p, pb.n_cols.p,
+                               n, nullptr, pb.op_off.p, pb.ops.p);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(ops + total_ops, pb.ops.p, (size_t)chunk_ops * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
+            HIP_TRY(hipStreamSynchronize(sl.stream));
+        }
+        total_ops += chunk_ops;
+        first = end;
+        pb.stats.chunks++;
+        pb.stats.column_bytes = std::max(pb.stats.column_bytes, bytes);
+        for (int32_t k = 0; k < n; k++) pb.stats.columns += n_cols[2 * (size_t)k] + n_cols[2 * (size_t)k + 1];
+    }
+    HIP_TRY(hipEventRecord(pb.ev1, sl.stream));
+    HIP_TRY(hipEventSynchronize(pb.ev1));
+    HIP_TRY(hipEventElapsedTime(&pb.stats.device_ms, pb.ev0, pb.ev1));
+    pb.stats.ops = total_ops;
+    pb.timed = true;
+    if (ops_needed) *ops_needed = total_ops;
+    if (!room && total_ops > 0)
+        return fail(GACT_HIP_EINVAL, "candidates_paths: the ops need room for %lld words, ops_cap is %lld", (long long)total_ops,
+                    (long long)ops_cap);
+    return 0;
+}
+
+int gact_hip_last_paths_stats(gact_hip_engine *e, int slot, gact_paths_stats *stats)
+{
+    int rc = check_slot(e, slot);
+    if (rc) return rc;
+    if (!stats) return fail(GACT_HIP_EINVAL, "last_paths_stats: NULL argument");
+    const Slot &sl = e->slots[slot];
+    if (!sl.path.timed) return fail(GACT_HIP_EINVAL, "last_paths_stats: slot %d has made no path run yet", slot);
+    *stats = sl.path.stats;
+    return 0;
 }
 
 int gact_hip_sync(gact_hip_engine *e, int slot)

@@ -14,7 +14,8 @@ _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.path.join(_PKG, "libgact_hip.so")
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in
            ("gact_engine.hip", "gact_kernels.hpp", "gact_device.hpp", "gact_chain.hpp", "gact_p16.hpp", "gact_p16s.hpp", "gact_lin.hpp",
-            "gact_aff.hpp", "gact_roles.hpp", "gact_coop.hpp", "gact_policy.hpp", "gact_big.hpp", "gact_gather.hpp", "dsoft_device.hpp", "dsoft_engine.hpp")] + \
+            "gact_aff.hpp", "gact_roles.hpp", "gact_coop.hpp", "gact_policy.hpp", "gact_big.hpp", "gact_gather.hpp", "gact_path.hpp",
+            "dsoft_device.hpp", "dsoft_engine.hpp")] + \
           [os.path.join(_ROOT, "include", "gact_hip.h")]
 
 SET_REF, SET_QUERY, SET_QUERY_RC = 0, 1, 2
@@ -30,6 +31,32 @@ OVERLAP_DTYPE = np.dtype([(n, "<i4") for n in
                           ("ref_id", "query_id", "ab", "ae", "bb", "be", "score", "comp", "emitted",
                            "first_tile_score", "n_tiles", "reserved")] + [("cells", "<i8")])
 assert TILE_DTYPE.itemsize == 28 and OVERLAP_DTYPE.itemsize == 56
+PATH_DTYPE = np.dtype([("op_offset", "<i8"), ("n_ops", "<i4"), ("n_columns", "<i4")])
+
+# alignment ops (include/gact_hip.h GACT_PATH_OP_*): BAM's CIGAR numbering; an op word is len << 4 | op
+OP_I, OP_D, OP_EQ, OP_X = 1, 2, 7, 8
+_OP_CHARS = {OP_I: "I", OP_D: "D", OP_EQ: "=", OP_X: "X"}
+
+
+def cigar_string(ops):
+    """op words (len << 4 | op) -> "153=1X2I..." """
+    return "".join("%d%s" % (int(w) >> 4, _OP_CHARS[int(w) & 15]) for w in ops)
+
+
+def rescore(ops, scoring=(1, -1, -1, -1)):
+    """the total score of gact.cpp:197-210 from op words: ONE `open` flag for both gap kinds, so an I run straight after a
+    D run (or the other way round) goes on with the gap and is charged gap_extend"""
+    match, mismatch, gap_open, gap_extend = scoring
+    score, open_ = 0, True
+    for w in ops:
+        n, op = int(w) >> 4, int(w) & 15
+        if op in (OP_I, OP_D):
+            score += (gap_open if open_ else gap_extend) + (n - 1) * gap_extend
+            open_ = False
+        else:
+            score += n * (match if op == OP_EQ else mismatch)
+            open_ = True
+    return score
 
 
 class Params(C.Structure):
@@ -50,6 +77,11 @@ class RunStats(C.Structure):
                 ("raw_candidates", C.c_int32), ("band_redos", C.c_int32),
                 ("merged_callers", C.c_int32), ("overlapped_seeding", C.c_int32),
                 ("critical_lane", C.c_int32), ("role_waves", C.c_int32)]
+
+
+class PathsStats(C.Structure):
+    _fields_ = [("device_ms", C.c_float), ("chunks", C.c_int32), ("column_bytes", C.c_int64), ("columns", C.c_int64),
+                ("ops", C.c_int64)]
 
 
 class DsoftParams(C.Structure):
@@ -181,7 +213,14 @@ def load():
     L.gact_hip_derive_revcomp.argtypes = [vp]
     L.gact_hip_register_output.argtypes = [vp, C.c_int, vp, C.c_int64]
     L.gact_hip_unregister_output.argtypes = [vp, C.c_int]
-    try:                                       # (an older build loaded through GACT_HIP_LIB_PATH for an A/B run has none)
+    try:
+        L.gact_hip_candidates_paths.argtypes = [vp, C.c_int, i32, vp, i32, C.c_int, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+        L.gact_hip_candidates_paths.restype = C.c_int
+        L.gact_hip_last_paths_stats.argtypes = [vp, C.c_int, C.POINTER(PathsStats)]
+        L.gact_hip_last_paths_stats.restype = C.c_int
+    except AttributeError:
+        pass
+    try:                                    # (an older build loaded through GACT_HIP_LIB_PATH for an A/B run has none)
         L.gact_hip_comm_create.argtypes = [vp, i32, i32, C.c_char_p, i32, C.POINTER(vp)]
         L.gact_hip_comm_gather_lines.argtypes = [vp, C.c_int, i32, vp, vp, C.c_int64]
         L.gact_hip_comm_destroy.argtypes = [vp]
@@ -210,7 +249,8 @@ EXPORTS = ("gact_hip_create", "gact_hip_destroy", "gact_hip_last_error", "gact_h
            "gact_hip_measure_valu_rate", "gact_hip_format_overlap", "gact_hip_dsoft_build", "gact_hip_dsoft_query",
            "gact_hip_candidates_download", "gact_hip_derive_revcomp", "gact_hip_register_output",
            "gact_hip_unregister_output", "gact_hip_set_option", "gact_hip_prepare",
-           "gact_hip_comm_create", "gact_hip_comm_gather_lines", "gact_hip_comm_destroy", "gact_hip_options_describe", "gact_hip_plan_describe")
+           "gact_hip_comm_create", "gact_hip_comm_gather_lines", "gact_hip_comm_destroy", "gact_hip_options_describe", "gact_hip_plan_describe",
+           "gact_hip_candidates_paths", "gact_hip_last_paths_stats")
 
 
 def plan(count, flags=0, compute_units=256, tile_size=320, tile_overlap=120, scoring=(1, -1, -1, -1), threshold=35):
@@ -359,6 +399,39 @@ class Engine:
         assert out.dtype == OVERLAP_DTYPE and len(out) >= n and out.flags["C_CONTIGUOUS"]
         self._check(self.L.gact_hip_candidates_fetch(self.h, slot, n, out.ctypes.data))
         return out
+
+    def candidates_paths(self, sel=None, n=None, rc_from=0x7fffffff, same_file=True, slot=0, ops_cap=None):
+        """alignments of candidates `sel` of the slot's candidate array (sel None: the first n), index >= rc_from =>
+        reverse-complement strand: (records OVERLAP_DTYPE, paths PATH_DTYPE, ops uint32), candidate k's ops at
+        ops[paths[k]["op_offset"] : + paths[k]["n_ops"]] (include/gact_hip.h gact_hip_candidates_paths).  ops_cap: room
+        for the first attempt; too little costs a second path run"""
+        if sel is not None:
+            sel = np.ascontiguousarray(sel, dtype=np.int32)
+            n = len(sel)
+        n = int(n or 0)
+        records = np.zeros(n, dtype=OVERLAP_DTYPE)
+        paths = np.zeros(n, dtype=PATH_DTYPE)
+        # (a guess that rarely needs the retry: 10 kb overlaps of reads with 15 % error have ~2,500 ops; the pages an
+        #  unused tail would take are never touched)
+        cap = int(ops_cap) if ops_cap is not None else 4096 * n + 1024
+        needed = C.c_int64()
+        for attempt in (0, 1):
+            ops = np.empty(cap, dtype=np.uint32)
+            rc = self.L.gact_hip_candidates_paths(self.h, slot, n, sel.ctypes.data if sel is not None else None, int(rc_from),
+                                                  int(same_file), records.ctypes.data, paths.ctypes.data, ops.ctypes.data, cap,
+                                                  C.byref(needed))
+            if rc == -1 and attempt == 0 and needed.value > cap:
+                cap = int(needed.value)              # too little room: once more with what the call said it needs
+                continue
+            self._check(rc)
+            return records, paths, ops[:int(needed.value)]
+
+    def last_paths_stats(self, slot=0):
+        """the slot's last path run: device ms (HIP events around the whole call), chunks, most column bytes of one chunk,
+        columns, ops"""
+        st = PathsStats()
+        self._check(self.L.gact_hip_last_paths_stats(self.h, slot, C.byref(st)))
+        return {n: getattr(st, n) for n, _ in PathsStats._fields_}
 
     def register_output(self, out, slot=0):
         """page-locks a caller-owned record array that will be fetched into repeatedly (opt-in; it must outlive the

@@ -2,7 +2,7 @@
 //
 //   darwin_hip <REF.fasta> <READS.fasta> CPU_THREADS [--params params.cfg]
 //              [--candidates FILE | --dump-candidates FILE [--dsoft-only]] [--device-dsoft]
-//              [--device D] [--shard R/W] [--recode]
+//              [--device D] [--shard R/W] [--recode] [--cigar]
 //
 // Plays the part of reference darwin.cpp:451-646 for the GACT stage: owns the
 // globals gact.cpp reads, loads params.cfg and the two FASTA files, builds the
@@ -17,6 +17,8 @@
 // same format; --dsoft-only stops after the filter (no GPU is touched).
 // --device-dsoft runs the filter on the GPU as well (gact_hip_dsoft_build / _query): every feeder thread
 // filters its read range straight into its slot's device candidate array and extends it from there.
+// --cigar (with --device-dsoft): every line gets ", cigar: <CIGAR>" appended, the alignment of that overlap from a second
+// pass over the emitted candidates (gact_hip_candidates_paths; '=' / 'X' / 'I' / 'D' relative to the reference).
 //
 // --device D: the GPU this process uses (the reference is single-device, cuda_host.cu:195).  --shard R/W: this
 // process is rank R of W -- it extends every W-th candidate (host filter) or the R-th contiguous range of reads
@@ -53,6 +55,7 @@ int match_score = 1, mismatch_score = -1, gap_open = -1, gap_extend = -1;
 int first_tile_score_threshold = 35;
 int tile_size = 320, tile_overlap = 120;
 int num_threads = 1;
+static bool want_cigar = false;                  // --cigar
 std::vector<long long int> reference_lengths, reads_lengths;
 std::vector<std::string> reference_seqs, reads_seqs, rev_reads_seqs;
 std::vector<std::vector<std::string> > reference_descrips, reads_descrips;
@@ -203,12 +206,50 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
     std::vector<gact_overlap> o((size_t)n);
     check(gact_hip_candidates_run_mixed(e, s.slot, 0, n, nf, same_file), "gact_hip_candidates_run_mixed");
     check(gact_hip_candidates_fetch(e, s.slot, n, o.data()), "gact_hip_candidates_fetch");
+    // --cigar: the alignments of the emitted candidates, a second pass on the device (gact_hip_candidates_paths)
+    std::vector<int32_t> sel;
+    std::vector<gact_path> paths;
+    std::vector<uint32_t> ops;
+    if (want_cigar) {
+        // room for every op at once: an alignment has no more ops than columns, and no more columns than the bases of its
+        // record's two spans (its ops end at (ae, be) and start at (ab, bb) or inside those spans, include/gact_hip.h)
+        size_t room = 1;
+        for (int32_t k = 0; k < n; k++)
+            if (o[(size_t)k].emitted) {
+                sel.push_back(k);
+                room += (size_t)(o[(size_t)k].ae - o[(size_t)k].ab) + (size_t)(o[(size_t)k].be - o[(size_t)k].bb);
+            }
+        std::vector<gact_overlap> rec(sel.size());
+        paths.resize(sel.size());
+        ops.resize(room);
+        int64_t needed = 0;
+        int rc = sel.empty() ? 0 : gact_hip_candidates_paths(e, s.slot, (int32_t)sel.size(), sel.data(), nf, same_file, rec.data(),
+                                                             paths.data(), ops.data(), (int64_t)ops.size(), &needed);
+        if (rc == GACT_HIP_EINVAL && needed > (int64_t)ops.size()) {
+            ops.resize((size_t)needed);
+            rc = gact_hip_candidates_paths(e, s.slot, (int32_t)sel.size(), sel.data(), nf, same_file, rec.data(), paths.data(),
+                                           ops.data(), (int64_t)ops.size(), &needed);
+        }
+        check(rc, "gact_hip_candidates_paths");
+    }
     char line[1024];
+    size_t next = 0;                              // (the emitted records in order: paths[next] is this one's)
     for (const gact_overlap &r : o) {
         if (!r.emitted) continue;
         const int len = gact_hip_format_overlap(&r, reference_descrips[r.ref_id][0].c_str(),
                                                 reads_descrips[r.query_id][0].c_str(), line, sizeof line);
-        fout.write(line, len);
+        if (!want_cigar) { fout.write(line, len); continue; }
+        static const char kOp[16] = {'?', 'I', 'D', '?', '?', '?', '?', '=', 'X', '?', '?', '?', '?', '?', '?', '?'};
+        const gact_path &p = paths[next++];
+        std::string text(line, (size_t)(len - 1));            // (without its newline)
+        text += ", cigar: ";
+        for (int32_t k = 0; k < p.n_ops; k++) {
+            const uint32_t w = ops[(size_t)(p.op_offset + k)];
+            text += std::to_string(w >> 4);
+            text += kOp[w & 15];
+        }
+        text += '\n';
+        fout.write(text.data(), (std::streamsize)text.size());
     }
     print_stage("Time GACT calling", t1, now());                 // darwin.cpp:441
 }
@@ -390,6 +431,7 @@ int main(int argc, char *argv[])
         else if (!strcmp(argv[a], "--dsoft-only")) dsoft_only = true;
         else if (!strcmp(argv[a], "--device-dsoft")) device_dsoft = true;
         else if (!strcmp(argv[a], "--recode")) recode = true;
+        else if (!strcmp(argv[a], "--cigar")) want_cigar = true;
         else if (!strcmp(argv[a], "--rccl-gather") && a + 1 < argc) gather_id = argv[++a];
         else if (!strcmp(argv[a], "--device") && a + 1 < argc) setenv("GACT_HIP_DEVICE", argv[++a], 1);   // read by GPU_init
         else if (!strcmp(argv[a], "--shard") && a + 1 < argc) {
@@ -398,6 +440,12 @@ int main(int argc, char *argv[])
         } else { fprintf(stderr, "unknown option %s\n", argv[a]); return 1; }
     }
     if (recode && device_dsoft) { fprintf(stderr, "--recode: the device filter reads ASCII sets\n"); return 1; }
+    if (want_cigar && (!device_dsoft || !gather_id.empty())) {
+        // the host-filter mode writes through the reference-signature GACT_Batch, which has no alignment to give; the gathered
+        // output would need the CIGARs gathered too
+        fprintf(stderr, "--cigar: only with --device-dsoft, and not with --rccl-gather\n");
+        return 1;
+    }
     std::map<std::string, double> cfg = parse_cfg(cfg_path);
     auto get = [&](const char *k, int dflt) { return cfg.count(k) ? (int)cfg[k] : dflt; };
     match_score = get("GACT_scoring/match", 1); mismatch_score = get("GACT_scoring/mismatch", -1);

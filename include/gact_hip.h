@@ -48,6 +48,18 @@ extern "C" {
 #define GACT_STATE_I 2   /* '-' in query, consumes a ref base (gact.cpp:121-125) */
 #define GACT_STATE_M 3
 
+/* Ops of an alignment path (gact_hip_candidates_paths), BAM's CIGAR numbering and SAM's names, relative to the
+ * reference -- the inverse of GACT's own state names:
+ *   GACT_STATE_M, equal bases   -> '=' GACT_PATH_OP_EQ   (raw sets: raw byte equality, case matters, N == N: align.cpp:134)
+ *   GACT_STATE_M, unequal bases -> 'X' GACT_PATH_OP_X
+ *   GACT_STATE_D ('-' in ref)   -> 'I' GACT_PATH_OP_I    (consumes a query base)
+ *   GACT_STATE_I ('-' in query) -> 'D' GACT_PATH_OP_D    (consumes a ref base)
+ * An op word is len << 4 | op. */
+#define GACT_PATH_OP_I   1
+#define GACT_PATH_OP_D   2
+#define GACT_PATH_OP_EQ  7
+#define GACT_PATH_OP_X   8
+
 /* which resident sequence set a descriptor addresses */
 #define GACT_SET_REF       0   /* reference_seqs   (gact.cpp:40) */
 #define GACT_SET_QUERY     1   /* reads_seqs       (gact.cpp:42) */
@@ -212,6 +224,47 @@ int gact_hip_candidates_run_range(gact_hip_engine *e, int slot, int32_t first, i
  * forward (GACT_calls_for, :227-238) */
 int gact_hip_candidates_run_mixed(gact_hip_engine *e, int slot, int32_t first, int32_t n,
                                   int32_t rc_from, int same_file);
+
+/* ---- alignment paths: the edit path of every selected candidate, as CIGAR ops ----
+ * The reference builds each candidate's aligned strings (gact.cpp:60-61,111-131,172-192), rescores them (:197-210) and throws
+ * them away; the run entries above fold the rescoring into the traceback and keep coordinates and a score only.  This entry is
+ * an opt-in SECOND pass for the candidates a caller chooses (typically the emitted ones): the int32 chain kernel runs their
+ * chains once more and its walker writes every alignment column, then a compaction kernel turns the columns into ops.
+ *
+ * Candidates sel[0..n_sel) of the slot's candidate array (uploaded, or made by the device filter); sel == NULL: [0, n_sel).
+ * n_sel == 0 returns 0 at once, also on a slot without candidates.
+ * Index >= rc_from: reverse-complement strand, as in gact_hip_candidates_run_mixed.  Synchronous on the slot's stream, never
+ * merged with other slots' runs; the slot's record array and run statistics stay as its last run left them.
+ *   records[k]  the chain's record, equal to what every run path writes for that candidate
+ *   paths[k]    op_offset: where its ops start in `ops`; n_ops; n_columns: alignment columns (= the sum of the op lengths)
+ *   ops         len << 4 | GACT_PATH_OP_*, left to right along the reference, ending at (ae, be) and starting at (ab, bb) --
+ *               except where the left extension aligned nothing (its first tile under the threshold, or a hit at position
+ *               0): there the right extension's first tile moved the start to its arg-max (gact.cpp:162-166) while ab / bb
+ *               stay where the left one stopped (:136-137).  For comp == 1 the query coordinates and ops refer to the
+ *               reverse-complemented read, as bb / be do.  A chain with no tile over the threshold has no columns.
+ * ops_cap too small (or ops == NULL): returns GACT_HIP_EINVAL with records, paths and *ops_needed filled -- call again with
+ * room for *ops_needed ops, as gact_hip_comm_gather_lines does.  The selection runs in chunks whose column buffers (ref_len +
+ * query_len bytes per candidate) fit GACT_HIP_PATH_BUDGET_MB; the buffers are allocated on the first call.  Refused
+ * (GACT_HIP_EINVAL): tile_size > GACT_HIP_FAST_TILE, a slot without candidates, an index outside the slot's array. */
+typedef struct {
+    int64_t op_offset;
+    int32_t n_ops;
+    int32_t n_columns;
+} gact_path;
+int gact_hip_candidates_paths(gact_hip_engine *e, int slot, int32_t n_sel, const int32_t *sel, int32_t rc_from,
+                              int same_file, gact_overlap *records, gact_path *paths,
+                              uint32_t *ops, int64_t ops_cap, int64_t *ops_needed);
+/* What the slot's last gact_hip_candidates_paths call that got as far as the device did: HIP events on the slot's stream
+ * around the whole call (its kernels, copies, and the host's scan between them), chunks it ran, the most column bytes one
+ * chunk took, alignment columns and ops of the selection.  The slot's gact_hip_run_stats are the normal run's. */
+typedef struct {
+    float device_ms;
+    int32_t chunks;
+    int64_t column_bytes;
+    int64_t columns;
+    int64_t ops;
+} gact_paths_stats;
+int gact_hip_last_paths_stats(gact_hip_engine *e, int slot, gact_paths_stats *stats);
 
 /* ------------------------------------------------------------------------
  * D-SOFT seed filter on the device (the stage in front of the path; optional:
