@@ -25,7 +25,8 @@ struct PathArgs {
 // copy and not a template switch on extend_kernel because every way of sharing the body that was tried (an inlined
 // template function, by value or by reference, LDS and __restrict__ left in the kernel) changed extend_kernel's own code
 // (4,735 -> 4,719 instructions at C = 20, differences throughout the loop).  A change to one loop belongs in the other;
-// tests/test_gpu_paths.py holds the two together (records byte for byte, and tile by tile through the model's CIGARs).
+// tests/test_gpu_paths.py and tests/test_gpu_paths_exact.py hold the two together (records byte for byte, and tile by tile
+// through the model's CIGARs, at both scorings and at C = 20 and C = 32).
 template <int C>
 __global__ __launch_bounds__(kBlockThreads, 3) void path_kernel(
     KParams kp, SeqSetDev refs, SeqSetDev qfwd, SeqSetDev qrc,

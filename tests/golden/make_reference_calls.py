@@ -14,6 +14,24 @@ import oracle_py  # noqa: E402
 
 if not oracle_py.ref_available():
     raise SystemExit("oracle/_ref/libdarwin_ref.so is not built: nothing to record from")
-sys.exit(subprocess.call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", "-m", "not gpu", "-k", "reference",
-                          "tests/test_dsoft.py", "tests/test_oracle.py"],
-                         cwd=ROOT, env=dict(os.environ, GACT_RECORD_REFERENCE_CALLS="1")))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_calls.json.gz")
+
+
+def recorded():
+    import gzip
+    import json
+    if not os.path.exists(GOLDEN):
+        return set()
+    with gzip.open(GOLDEN, "rt") as f:
+        return set(json.load(f))
+
+
+before = recorded()
+rc = subprocess.call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", "-m", "not gpu", "-k", "reference",
+                      "tests/test_dsoft.py", "tests/test_oracle.py", "tests/test_paths_model.py"],
+                     cwd=ROOT, env=dict(os.environ, GACT_RECORD_REFERENCE_CALLS="1"))
+# the file is rewritten as a whole: a call that was in it and is gone means a test that replays it lost its answer
+lost = before - recorded()
+if lost:
+    print("%d calls recorded before are no longer in %s" % (len(lost), os.path.relpath(GOLDEN, ROOT)))
+sys.exit(rc or (1 if lost else 0))

@@ -1,7 +1,7 @@
 """GPU suite for alignment paths (gact_hip_candidates_paths): the CIGAR of every candidate of a small workload equals the
 model's (tests/path_model.py, on the oracle's AlignWithBT); on larger sets, every candidate's path is consistent with its
 record and its two reads, and its record equals the normal run's byte for byte; chunking, the ops_cap retry, the refusals,
-and the driver's --cigar lines."""
+and the driver's --cigar lines.  tests/test_gpu_paths_exact.py compares with the model at every other configuration."""
 import ctypes
 import os
 import re
@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import path_cases
 from path_model import check_path, gact_path
 
 pytestmark = pytest.mark.gpu
@@ -35,7 +36,8 @@ def _normal_and_paths(eng, n, nf, sel=None):
     return normal, records, paths, ops
 
 
-def _check_all(rs, cands, nf, normal, records, paths, ops, scoring, sel=None):
+def _check_all(rs, cands, nf, normal, records, paths, ops, scoring, sel=None, left_aligned=None):
+    """left_aligned: per selected candidate, from the model where one is at hand: whether the path must span the record"""
     sel = np.arange(len(cands)) if sel is None else np.asarray(sel)
     assert records.tobytes() == normal[sel].tobytes(), "path records differ from the normal run's"
     exact = 0
@@ -44,8 +46,12 @@ def _check_all(rs, cands, nf, normal, records, paths, ops, scoring, sel=None):
         q = rs.rc(int(c["query_id"])) if idx >= nf else rs.reads[int(c["query_id"])]
         p = paths[k]
         mine = ops[p["op_offset"]:p["op_offset"] + p["n_ops"]]
-        exact += check_path(records[k], mine, int(p["n_columns"]), rs.reads[int(c["ref_id"])], q, scoring)
-    assert exact >= len(sel) // 2                  # (most paths span [ab, ae) exactly; see check_path)
+        exact += check_path(records[k], mine, int(p["n_columns"]), rs.reads[int(c["ref_id"])], q, scoring,
+                            left_aligned=None if left_aligned is None else left_aligned[k])
+    if left_aligned is None:
+        assert exact >= len(sel) // 2              # (most paths span [ab, ae) exactly; see check_path)
+    else:
+        assert exact >= sum(bool(x) for x in left_aligned)
     assert paths["n_columns"].sum() > 0
 
 
@@ -58,11 +64,14 @@ def test_paths_equal_the_model_on_tiny(oracle):
     normal, records, paths, ops = _normal_and_paths(eng, n, nf)
     eng.close()
     assert nf > 0 and n > nf
-    _check_all(blk.rs, cands, nf, normal, records, paths, ops, (1, -1, -1, -1))
+    models = []
     for k in range(n):
         c = cands[k]
         q = blk.rs.rc(int(c["query_id"])) if k >= nf else blk.rs.reads[int(c["query_id"])]
-        m = gact_path(oracle.align_with_bt, blk.rs.reads[int(c["ref_id"])], q, int(c["ref_pos"]), int(c["query_pos"]))
+        models.append(gact_path(oracle.align_with_bt, blk.rs.reads[int(c["ref_id"])], q, int(c["ref_pos"]), int(c["query_pos"])))
+    _check_all(blk.rs, cands, nf, normal, records, paths, ops, (1, -1, -1, -1))
+    _check_all(blk.rs, cands, nf, normal, records, paths, ops, (1, -1, -1, -1), left_aligned=[m["left_aligned"] for m in models])
+    for k, m in enumerate(models):
         p = paths[k]
         got = engine.cigar_string(ops[p["op_offset"]:p["op_offset"] + p["n_ops"]])
         assert got == engine.cigar_string(m["ops"]), (k, got[:80], engine.cigar_string(m["ops"])[:80])
@@ -82,20 +91,10 @@ def test_path_invariants_on_ecoli10x_small(scoring, tile_size, tile_overlap):
 
 def test_path_invariants_with_n_and_lower_case_reads():
     """raw-byte sets: = / X by raw byte equality (case matters, N == N, align.cpp:134)"""
-    from gact_amd import synth
     from conftest import workload_block
     blk = workload_block("tiny")
-    rs = synth.ReadSet()
-    rng = np.random.default_rng(5)
-    for k, r in enumerate(blk.rs.reads):
-        r = r.copy()
-        if k % 3 == 0:
-            r[rng.integers(0, len(r), 40)] = ord("N")
-        if k % 4 == 1:
-            a = int(rng.integers(0, max(1, len(r) - 500)))
-            r[a:a + 500] = np.frombuffer(bytes(r[a:a + 500]).lower(), np.uint8)
-        rs.reads.append(r)
-        rs.names.append(blk.rs.names[k])
+    rs = path_cases.n_and_lower_case(blk.rs, seed=5)
+    assert any(b"N" in bytes(r) for r in rs.reads) and any(bytes(r) != bytes(r).upper() for r in rs.reads)
     eng, n, nf = _engine_with(rs, blk.cf, blk.cr)
     normal, records, paths, ops = _normal_and_paths(eng, n, nf)
     eng.close()
@@ -110,7 +109,10 @@ def test_a_selection_of_many_chunks_equals_one_chunk(monkeypatch):
     eng, n, nf = _engine_with(blk.rs, blk.cf, blk.cr)
     one = eng.candidates_paths(sel=sel, rc_from=nf)
     st_one = eng.last_paths_stats()
+    eng.candidates_run_mixed(n, nf)
+    normal = eng.candidates_fetch(n).copy()
     eng.close()
+    assert (sel < nf).any() and (sel >= nf).any() and np.any(np.diff(sel) < 0)
     monkeypatch.setenv("GACT_HIP_PATH_BUDGET_MB", "1")                   # read at create: a fresh engine
     eng, n, nf = _engine_with(blk.rs, blk.cf, blk.cr)
     many = eng.candidates_paths(sel=sel, rc_from=nf)
@@ -124,6 +126,9 @@ def test_a_selection_of_many_chunks_equals_one_chunk(monkeypatch):
         assert st["device_ms"] > 0 and st["ops"] == len(one[2]) and st["columns"] == int(one[1]["n_columns"].sum())
     for a, b in zip(one, many):
         assert a.tobytes() == b.tobytes()
+    # the selection against the normal run and the reads: sel[k] on its own strand, in its own column buffer
+    assert one[0].tobytes() == normal[sel].tobytes()
+    _check_all(blk.rs, cands, nf, normal, *one, (1, -1, -1, -1), sel=sel)
 
 
 def test_ops_cap_too_small_says_how_much_and_the_retry_succeeds():

@@ -1,13 +1,16 @@
 """CPU suite for alignment paths (gact_hip_candidates_paths): the Python restatement of GACT's tile chain that keeps the
 alignment (tests/path_model.py) is pinned against the oracle -- record and tile sequence -- and, on small cases, against the
-reference's own AlignWithBT; the CIGAR helpers of gact_amd.engine; the gact_path layout as a C compiler sees it."""
+reference's own AlignWithBT; the crafted candidates of tests/path_cases.py reach, on the model, the edges the GPU suite
+counts on them to reach; the CIGAR helpers of gact_amd.engine; the gact_path layout as a C compiler sees it."""
 import ctypes
 import os
+import re
 import subprocess
 
 import numpy as np
 import pytest
 
+import path_cases
 from path_model import columns_to_ops, gact_path, check_path
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -57,6 +60,64 @@ def test_model_on_the_references_own_alignwithbt(reflib, oracle):
         b = gact_path(reflib.align_with_bt, ref, query, rp, qp, tile_size=128, tile_overlap=32)
         assert engine.cigar_string(a["ops"]) == engine.cigar_string(b["ops"])
         assert (a["ab"], a["ae"], a["bb"], a["be"], a["score"]) == (b["ab"], b["ae"], b["bb"], b["be"], b["score"])
+
+
+@pytest.mark.parametrize("scoring", [path_cases.LINEAR, path_cases.AFFINE])
+def test_crafted_cases_reach_the_edges_they_are_made_for(oracle, scoring):
+    """asserted on the model's output at tile 320 / 120, so that a change of the helper or the simulator cannot quietly
+    empty tests/test_gpu_paths_exact.py: path_ops_kernel works in steps of 64 columns and carries the open run between them"""
+    cr = path_cases.crafted()
+    cands, nf = np.concatenate([cr.cf, cr.cr]), len(cr.cf)
+    assert len(cr.names) == len(cands) == len(set(cr.names))
+    exp = path_cases.expected(oracle, cr.rs, cands, nf, scoring=scoring)
+    starts = set()
+    for e in exp:
+        lens = [int(n) for n in re.findall(r"(\d+)[=XID]", e["cigar"])]
+        assert sum(lens) == e["n_columns"] and len(lens) == e["n_ops"]
+        starts |= {int(c) % 64 for c in np.cumsum(lens)[:-1]}          # (every run but a path's first, which starts at 0)
+    assert {0, 1, 62, 63} <= starts
+    assert any(e["n_columns"] > 0 and e["n_columns"] % 64 == 0 for e in exp)
+    assert any(e["n_ops"] == 1 and e["n_columns"] > 128 for e in exp)
+    assert sum(e["n_columns"] == 0 for e in exp) >= 5
+    assert all(e["n_ops"] == 0 and e["score"] == 0 for e in exp if e["n_columns"] == 0)
+    assert sum(e["n_columns"] > 0 and not e["left_aligned"] for e in exp) >= 5
+    for op in "IDX":
+        assert any(op in e["cigar"] for e in exp), op
+    for strand, names in (("forward", cr.names[:nf]), ("reverse-complement", cr.names[nf:])):
+        assert {nm.split("/")[0] for nm in names} == set(path_cases.FAMILIES), strand
+    # the two read sets differ in the raw family's stretches only, and only one of them has a byte outside ACGT
+    plain = path_cases.crafted(raw=False)
+    assert plain.names == cr.names and np.array_equal(plain.cf, cr.cf) and np.array_equal(plain.cr, cr.cr)
+    assert all(set(bytes(r)) <= set(b"ACGT") for r in plain.rs.reads)
+    assert any(b"N" in bytes(r) for r in cr.rs.reads) and any(bytes(r) != bytes(r).upper() for r in cr.rs.reads)
+    # a read against itself, on both strands
+    assert sum(c["ref_id"] == c["query_id"] for c in cr.cf) >= 1 and sum(c["ref_id"] == c["query_id"] for c in cr.cr) >= 1
+
+
+def test_sample_draws_both_strands_unsorted_and_is_fixed_by_its_seed():
+    sel = path_cases.sample(1000, 700, 200, seed=3)
+    assert sel.dtype == np.int32 and len(sel) == len(set(sel.tolist())) == 200
+    assert (sel < 1000).sum() == (sel >= 1000).sum() == 100 and sel.max() < 1700
+    assert np.any(np.diff(sel) < 0) and np.array_equal(sel, path_cases.sample(1000, 700, 200, seed=3))
+    assert not np.array_equal(sel, path_cases.sample(1000, 700, 200, seed=4))
+    assert (path_cases.sample(1000, 30, 200, seed=3) >= 1000).sum() == 30          # a short strand gives all it has
+    assert sorted(path_cases.sample(5, 3, 200, seed=3).tolist()) == list(range(8))
+
+
+@pytest.mark.parametrize("scoring", [path_cases.LINEAR, path_cases.AFFINE])
+def test_crafted_cases_on_the_references_own_alignwithbt(reflib, oracle, scoring):
+    """every crafted pair of reads of at most 1,000 bases, at tile 128 / 32: the model driven by the reference's AlignWithBT
+    gives the oracle-driven CIGAR and record"""
+    cr = path_cases.crafted()
+    cands, nf = np.concatenate([cr.cf, cr.cr]), len(cr.cf)
+    small = np.array([k for k in range(len(cands))
+                      if max(len(r) for r in path_cases.reads_of(cr.rs, cands, nf, k)) <= 1000], dtype=np.int32)
+    assert len(small) > 100 and {cr.names[k].split("/")[0] for k in small} >= set(path_cases.FAMILIES) - {"inside", "edge", "unrelated"}
+    kw = dict(tile_size=128, tile_overlap=32, scoring=scoring)
+    a = path_cases.expected(oracle, cr.rs, cands, nf, small, **kw)
+    b = path_cases.expected(oracle, cr.rs, cands, nf, small, align=reflib.align_with_bt, **kw)
+    for k, x, y in zip(small.tolist(), a, b):
+        assert x == y, (cr.names[k], x, y)
 
 
 def test_cigar_string_and_rescore():
