@@ -514,6 +514,17 @@ struct PathCursor {
     int dir;                      // -1 left phase, +1 right phase
 };
 
+// Summary runs (gact_summary.hpp): what walk_chain<..., COUNT = true> adds up over a candidate's columns instead of
+// storing them -- columns and runs (= CIGAR ops) of each kind.  Runs are counted where they start: a column whose op
+// differs from the op of the column emitted before it.  `prev` carries that op from tile to tile of a phase (0: there is
+// no column yet); `first` keeps the first op the left phase emitted -- that phase emits right to left, so it is the column
+// next to the junction, and the right phase starts with it as its `prev` (summary_kernel).
+struct PathCount {
+    int prev, first;              // GACT_PATH_OP_*, 0 = none
+    int n_eq, n_x, n_i, n_d;      // columns
+    int r_eq, r_x, r_i, r_d;      // runs
+};
+
 // The chain kernels' walker: traceback (align.cpp:185-230) fused with the rescoring
 // of gact.cpp:197-210, written for few instructions per step -- every step of a
 // walker is a whole wave instruction however few lanes walk, and a tile's walk is
@@ -537,15 +548,18 @@ struct PathCursor {
 // byte stride.  (l0, c0, k0) = lane, column-in-lane and stored step of the start cell
 // (R, Q) in the pass's layout; CW columns per lane, QN column quads stored per lane.
 // PATH (FMT 0 only, the path run's int32 chain kernel): every column's GACT_PATH_OP_* byte goes out through *path.
+// COUNT (FMT 0 only, the summary run's): columns and run starts of each kind are added to *count; nothing is stored.
 //
-template <int CW, int FMT, int QN = CW / 4, int ROW = kGroup, bool PATH = false>
+template <int CW, int FMT, int QN = CW / 4, int ROW = kGroup, bool PATH = false, bool COUNT = false>
 __device__ __forceinline__ void walk_chain(const uint32_t *ws, uint32_t *scratch, int R, int Q, int l0, int c0, int k0,
                                            int early, const uint8_t *rrow, int rstride, const uint8_t *qrow,
                                            int phase, const KParams &kp, ScoreWalk &wk, int &ref_steps,
                                            int &query_steps, int &nst, int v0 = 0, const uint32_t *ws_all = nullptr,
-                                           const int band_lim = -1, bool *redo = nullptr, PathCursor *path = nullptr)
+                                           const int band_lim = -1, bool *redo = nullptr, PathCursor *path = nullptr,
+                                           PathCount *count = nullptr)
 {
     static_assert(!PATH || FMT == 0, "paths are emitted by the int32 chain kernel's walk");
+    static_assert(!COUNT || FMT == 0, "summaries are counted by the int32 chain kernel's walk");
     if constexpr (FMT == 3) {
         bool rd = false;
         walk_chain_lin<CW, QN, ROW>(ws, scratch, R, Q, l0, c0, k0, early, rrow, rstride, qrow, kp, wk, ref_steps,
@@ -633,6 +647,17 @@ __device__ __forceinline__ void walk_chain(const uint32_t *ws, uint32_t *scratch
     // conditions live as lane masks on the scalar unit; a counter takes one as the carry of a single VALU op
     const uint64_t left_m = lanes(left);
     uint64_t gprev = lanes(left ? wk.pend_gap != 0 : wk.open_flag == 0);
+    // COUNT: the kind of the column emitted last, one lane mask per kind (none set: no column yet), and the run starts
+    uint64_t p_eq = 0, p_x = 0, p_d = 0, p_i = 0;
+    int r_eq = 0, r_x = 0, r_d = 0, r_i = 0;
+    if constexpr (COUNT) {
+        p_eq = lanes(count->prev == GACT_PATH_OP_EQ);
+        p_x = lanes(count->prev == GACT_PATH_OP_X);
+        p_d = lanes(count->prev == GACT_PATH_OP_D);
+        p_i = lanes(count->prev == GACT_PATH_OP_I);
+        if (left && count->first == 0 && cur != 0)
+            count->first = cur == kM ? (ra[0] == qa[0] ? GACT_PATH_OP_EQ : GACT_PATH_OP_X) : cur == kI ? GACT_PATH_OP_D : GACT_PATH_OP_I;
+    }
     for (int it = 0; cur != 0; it++) {
         // ---- one alignment column (gact.cpp:115-130 / :176-191 and :202-209)
         const uint64_t g = lanes(cur != kM);
@@ -647,6 +672,19 @@ __device__ __forceinline__ void walk_chain(const uint32_t *ws, uint32_t *scratch
             const uint32_t op = cur == kM ? (same ? GACT_PATH_OP_EQ : GACT_PATH_OP_X) : cur == kI ? GACT_PATH_OP_D : GACT_PATH_OP_I;
             path_pend |= (uint64_t)op << (8 * path_n);
             path_n++;
+        }
+        if constexpr (COUNT) {
+            // (columns are derived after the loop: n_eq and n_m are counted above, a gap column took one step, an M column two)
+            const uint64_t act = lanes(true), m = act & ~g;
+            const uint64_t k_eq = m & eq, k_x = m & ~eq, k_d = lanes(cur == kI), k_i = g & ~k_d;   // kI is SAM's D (see PATH)
+            r_eq = add_lane_bit(r_eq, k_eq & ~p_eq);
+            r_x = add_lane_bit(r_x, k_x & ~p_x);
+            r_d = add_lane_bit(r_d, k_d & ~p_d);
+            r_i = add_lane_bit(r_i, k_i & ~p_i);
+            p_eq = (p_eq & ~act) | k_eq;                          // (walkers that have stopped keep theirs, as gprev)
+            p_x = (p_x & ~act) | k_x;
+            p_d = (p_d & ~act) | k_d;
+            p_i = (p_i & ~act) | k_i;
         }
         gprev = (gprev & ~lanes(true)) | g;                       // walkers that have stopped keep their last column
         // ---- move (align.cpp:210-229): INSERT / DELETE stay unless their flag says the gap was opened here
@@ -679,6 +717,14 @@ __device__ __forceinline__ void walk_chain(const uint32_t *ws, uint32_t *scratch
         cur = (nis <= nlim_i || njs <= nlim_j || rd) ? 0u : nxt;       // align.cpp:205, borders :101-107
     }
     path_flush();
+    if constexpr (COUNT) {
+        const int me = threadIdx.x & 63;
+        count->prev = ((p_eq >> me) & 1) ? GACT_PATH_OP_EQ : ((p_x >> me) & 1) ? GACT_PATH_OP_X : ((p_d >> me) & 1) ? GACT_PATH_OP_D
+                    : ((p_i >> me) & 1) ? GACT_PATH_OP_I : 0;
+        count->n_eq += n_eq; count->n_x += n_m - n_eq;
+        count->n_d += -nis - n_m; count->n_i += -njs - n_m;       // ref / query steps that were not M columns
+        count->r_eq += r_eq; count->r_x += r_x; count->r_d += r_d; count->r_i += r_i;
+    }
     if (redo) *redo = rd;
     ref_steps = -nis; query_steps = -njs;
     nst = -nis - njs - n_m;

@@ -39,6 +39,7 @@
 #include "gact_policy.hpp"
 #include "gact_big.hpp"
 #include "gact_path.hpp"
+#include "gact_summary.hpp"
 #include "dsoft_device.hpp"
 
 namespace {
@@ -212,6 +213,21 @@ struct Slot {
             d_counter = nullptr; ev0 = ev1 = nullptr;
         }
     } path;
+    // gact_hip_candidates_summaries (gact_summary.hpp): one allocation, exactly what the largest selection so far needed
+    struct SummaryBufs {
+        uint8_t *p = nullptr;                          // candidates | records | summaries | pop counter
+        size_t bytes = 0;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;       // around the whole call (gact_hip_last_summaries_stats)
+        gact_summaries_stats stats{};
+        bool timed = false;
+        void release()
+        {
+            if (p) (void)hipFree(p);
+            if (ev0) (void)hipEventDestroy(ev0);
+            if (ev1) (void)hipEventDestroy(ev1);
+            p = nullptr; bytes = 0; ev0 = ev1 = nullptr;
+        }
+    } summary;
 };
 
 // device-side D-SOFT filter (dsoft_device.hpp)
@@ -1362,6 +1378,7 @@ void gact_hip_destroy(gact_hip_engine *e)
         sl.cands.release(); sl.overlaps.release(); sl.live.release(); sl.chain_states.release(); sl.deferred.release();
         sl.inline_ref.release(); sl.inline_query.release();
         sl.path.release();
+        sl.summary.release();
         if (sl.d_counter) (void)hipFree(sl.d_counter);
         if (sl.d_flags) (void)hipFree(sl.d_flags);
         if (sl.d_ws) (void)hipFree(sl.d_ws);
@@ -2003,6 +2020,68 @@ int gact_hip_extend_candidates(gact_hip_engine *e, int slot, int32_t n, const ga
     return gact_hip_candidates_fetch(e, slot, n, out);
 }
 
+// The selection of a path run or a summary run (`who` names the entry in the refusals): the selected candidates as the host
+// sees them (its copy of an uploaded list, else the device filter's list copied back), each tagged with its strand
+// (kCompInCand, as a merged run does), the reads' lengths, and the read sets the chains are to read.
+struct Selection {
+    std::vector<gact_candidate> tagged;
+    std::vector<int64_t> cap;                 // ref_len + query_len of each: every column consumes a base of one of the two reads
+    gact::SeqSetDev d_rs, d_qf, d_qr;
+};
+static int select_candidates(gact_hip_engine *e, int slot, int32_t n_sel, const int32_t *sel, int32_t rc_from, const char *who,
+                             Selection &sn)
+{
+    int rc;
+    Slot &sl = e->slots[slot];
+    if (sl.n_cands == 0)
+        return fail(GACT_HIP_EINVAL, "%s: slot %d holds no candidates (upload a list or run the device filter first)", who, slot);
+    for (int32_t k = 0; k < n_sel; k++) {
+        const int64_t idx = sel ? sel[k] : k;
+        if (idx < 0 || (size_t)idx >= sl.n_cands)
+            return fail(GACT_HIP_EINVAL, "%s: sel[%d] = %lld outside the %zu candidates of slot %d", who, k, (long long)idx,
+                        sl.n_cands, slot);
+    }
+    if ((rc = set_device(e))) return rc;
+    const SeqSet &rs = e->sets[GACT_SET_REF];
+    const SeqSet &qf = e->sets[GACT_SET_QUERY], &qr = e->sets[GACT_SET_QUERY_RC];
+    // the candidates as the host sees them
+    std::vector<gact_candidate> downloaded;
+    const gact_candidate *hc = sl.h_cands.data();
+    if (sl.h_cands.empty()) {
+        if (sl.cands_epoch != e->sets_epoch)
+            return fail(GACT_HIP_EINVAL, "%s: a read set was uploaded after the device filter made this slot's "
+                                         "candidates; run gact_hip_dsoft_query again", who);
+        downloaded.resize(sl.n_cands);
+        HIP_TRY(hipMemcpyAsync(downloaded.data(), sl.cands.p, sl.n_cands * sizeof(gact_candidate), hipMemcpyDeviceToHost, sl.stream));
+        HIP_TRY(hipStreamSynchronize(sl.stream));
+        hc = downloaded.data();
+    }
+    // strands, lengths, checks
+    sn.tagged.resize((size_t)n_sel);
+    sn.cap.resize((size_t)n_sel);
+    bool need_f = false, need_r = false;
+    for (int32_t k = 0; k < n_sel; k++) {
+        const int32_t idx = sel ? sel[k] : k;
+        gact_candidate c = hc[idx];
+        const bool comp = idx >= rc_from;
+        const SeqSet &qs = comp ? qr : qf;
+        (comp ? need_r : need_f) = true;
+        if (rs.n == 0 || qs.n == 0) return fail(GACT_HIP_EINVAL, "%s: read sets not uploaded", who);
+        if (c.ref_id < 0 || c.ref_id >= rs.n || c.query_id < 0 || c.query_id >= qs.n)
+            return fail(GACT_HIP_ERANGE, "candidate %d: sequence id out of range", idx);
+        const int64_t rl = rs.h_offsets[c.ref_id + 1] - rs.h_offsets[c.ref_id];
+        const int64_t ql = qs.h_offsets[c.query_id + 1] - qs.h_offsets[c.query_id];
+        if (c.ref_pos < 0 || c.ref_pos > rl || c.query_pos < 0 || c.query_pos > ql)
+            return fail(GACT_HIP_ERANGE, "candidate %d: position outside its read", idx);
+        if (comp) c.query_id |= gact::kCompBit;
+        sn.tagged[(size_t)k] = c;
+        sn.cap[(size_t)k] = rl + ql;
+    }
+    const bool raw = rs.has_other || (need_f && qf.has_other) || (need_r && qr.has_other);
+    sn.d_rs = rs.dev(raw); sn.d_qf = qf.dev_or(raw, rs); sn.d_qr = qr.dev_or(raw, rs);
+    return 0;
+}
+
 // The path run (gact_path.hpp).  The host takes the selected candidates (its copy of an uploaded list, else the device
 // filter's list copied back), tags each with its strand (kCompInCand, as a merged run does), and cuts the selection into
 // chunks whose column buffers fit the budget; per chunk: path_kernel, the op count, the counts back, the scan on the host,
@@ -2022,52 +2101,11 @@ int gact_hip_candidates_paths(gact_hip_engine *e, int slot, int32_t n_sel, const
     Slot &sl = e->slots[slot];
     if (ops_needed) *ops_needed = 0;
     if (n_sel == 0) return 0;                 // (nothing asked for: also on a slot without candidates, e.g. a feeder with no reads)
-    if (sl.n_cands == 0)
-        return fail(GACT_HIP_EINVAL, "candidates_paths: slot %d holds no candidates (upload a list or run the device filter first)", slot);
-    for (int32_t k = 0; k < n_sel; k++) {
-        const int64_t idx = sel ? sel[k] : k;
-        if (idx < 0 || (size_t)idx >= sl.n_cands)
-            return fail(GACT_HIP_EINVAL, "candidates_paths: sel[%d] = %lld outside the %zu candidates of slot %d", k, (long long)idx,
-                        sl.n_cands, slot);
-    }
-    if ((rc = set_device(e))) return rc;
-    const SeqSet &rs = e->sets[GACT_SET_REF];
-    const SeqSet &qf = e->sets[GACT_SET_QUERY], &qr = e->sets[GACT_SET_QUERY_RC];
-    // the candidates as the host sees them
-    std::vector<gact_candidate> downloaded;
-    const gact_candidate *hc = sl.h_cands.data();
-    if (sl.h_cands.empty()) {
-        if (sl.cands_epoch != e->sets_epoch)
-            return fail(GACT_HIP_EINVAL, "candidates_paths: a read set was uploaded after the device filter made this slot's "
-                                         "candidates; run gact_hip_dsoft_query again");
-        downloaded.resize(sl.n_cands);
-        HIP_TRY(hipMemcpyAsync(downloaded.data(), sl.cands.p, sl.n_cands * sizeof(gact_candidate), hipMemcpyDeviceToHost, sl.stream));
-        HIP_TRY(hipStreamSynchronize(sl.stream));
-        hc = downloaded.data();
-    }
-    // strands, lengths, checks
-    std::vector<gact_candidate> tagged((size_t)n_sel);
-    std::vector<int64_t> cap((size_t)n_sel);
-    bool need_f = false, need_r = false;
-    for (int32_t k = 0; k < n_sel; k++) {
-        const int32_t idx = sel ? sel[k] : k;
-        gact_candidate c = hc[idx];
-        const bool comp = idx >= rc_from;
-        const SeqSet &qs = comp ? qr : qf;
-        (comp ? need_r : need_f) = true;
-        if (rs.n == 0 || qs.n == 0) return fail(GACT_HIP_EINVAL, "candidates_paths: read sets not uploaded");
-        if (c.ref_id < 0 || c.ref_id >= rs.n || c.query_id < 0 || c.query_id >= qs.n)
-            return fail(GACT_HIP_ERANGE, "candidate %d: sequence id out of range", idx);
-        const int64_t rl = rs.h_offsets[c.ref_id + 1] - rs.h_offsets[c.ref_id];
-        const int64_t ql = qs.h_offsets[c.query_id + 1] - qs.h_offsets[c.query_id];
-        if (c.ref_pos < 0 || c.ref_pos > rl || c.query_pos < 0 || c.query_pos > ql)
-            return fail(GACT_HIP_ERANGE, "candidate %d: position outside its read", idx);
-        if (comp) c.query_id |= gact::kCompBit;
-        tagged[(size_t)k] = c;
-        cap[(size_t)k] = rl + ql;                 // every column consumes a base of one of the two reads
-    }
-    const bool raw = rs.has_other || (need_f && qf.has_other) || (need_r && qr.has_other);
-    const gact::SeqSetDev d_rs = rs.dev(raw), d_qf = qf.dev_or(raw, rs), d_qr = qr.dev_or(raw, rs);
+    Selection sn;
+    if ((rc = select_candidates(e, slot, n_sel, sel, rc_from, "candidates_paths", sn))) return rc;
+    const std::vector<gact_candidate> &tagged = sn.tagged;
+    const std::vector<int64_t> &cap = sn.cap;
+    const gact::SeqSetDev &d_rs = sn.d_rs, &d_qf = sn.d_qf, &d_qr = sn.d_qr;
     Slot::PathBufs &pb = sl.path;
     if (!pb.d_counter && (hipMalloc((void **)&pb.d_counter, sizeof(int)) != hipSuccess || hipEventCreate(&pb.ev0) != hipSuccess ||
                           hipEventCreate(&pb.ev1) != hipSuccess))
@@ -2166,6 +2204,83 @@ int gact_hip_last_paths_stats(gact_hip_engine *e, int slot, gact_paths_stats *st
     const Slot &sl = e->slots[slot];
     if (!sl.path.timed) return fail(GACT_HIP_EINVAL, "last_paths_stats: slot %d has made no path run yet", slot);
     *stats = sl.path.stats;
+    return 0;
+}
+
+// The summary run (gact_summary.hpp): the same selection, one summary_kernel launch over all of it, records and summaries back.
+int gact_hip_candidates_summaries(gact_hip_engine *e, int slot, int32_t n_sel, const int32_t *sel, int32_t rc_from,
+                                  int same_file, gact_overlap *records, gact_path_summary *sums)
+{
+    int rc = check_slot(e, slot);
+    if (rc) return rc;
+    if (n_sel < 0 || (n_sel > 0 && (!records || !sums)))
+        return fail(GACT_HIP_EINVAL, "candidates_summaries: bad arguments");
+    if (e->big_cb)
+        return fail(GACT_HIP_EINVAL, "candidates_summaries: tile_size %d > GACT_HIP_FAST_TILE (%d): summaries come from the "
+                                     "register-tiled int32 chain kernel, which the tiles of gact_big.hpp do not run on",
+                    e->params.tile_size, GACT_HIP_FAST_TILE);
+    Slot &sl = e->slots[slot];
+    if (n_sel == 0) return 0;                 // (as gact_hip_candidates_paths)
+    Selection sn;
+    if ((rc = select_candidates(e, slot, n_sel, sel, rc_from, "candidates_summaries", sn))) return rc;
+    Slot::SummaryBufs &sb = sl.summary;
+    if (!sb.ev0 && (hipEventCreate(&sb.ev0) != hipSuccess || hipEventCreate(&sb.ev1) != hipSuccess))
+        return fail(GACT_HIP_ENOMEM, "candidates_summaries: device allocation failed");
+    // candidates | records | summaries | pop counter: 16 + 56 + 32 bytes per candidate, each array 16-byte aligned
+    const size_t n = (size_t)n_sel;
+    const size_t at_records = n * sizeof(gact_candidate);
+    const size_t at_sums = (at_records + n * sizeof(gact_overlap) + 15) & ~(size_t)15;
+    const size_t at_counter = at_sums + n * sizeof(gact_path_summary);
+    const size_t bytes = at_counter + 16;
+    if (bytes > sb.bytes) {
+        if (sb.p) (void)hipFree(sb.p);
+        sb.p = nullptr; sb.bytes = 0;
+        if (hipMalloc((void **)&sb.p, bytes) != hipSuccess)
+            return fail(GACT_HIP_ENOMEM, "candidates_summaries: device allocation failed (%d candidates, %zu bytes)", n_sel, bytes);
+        sb.bytes = bytes;
+    }
+    gact_candidate *d_cands = (gact_candidate *)sb.p;
+    gact_overlap *d_records = (gact_overlap *)(sb.p + at_records);
+    gact_path_summary *d_sums = (gact_path_summary *)(sb.p + at_sums);
+    int *d_counter = (int *)(sb.p + at_counter);
+    sb.stats = gact_summaries_stats{};
+    sb.timed = false;
+    HIP_TRY(hipEventRecord(sb.ev0, sl.stream));
+    HIP_TRY(hipMemcpyAsync(d_cands, sn.tagged.data(), n * sizeof(gact_candidate), hipMemcpyHostToDevice, sl.stream));
+    // (a chain with no tile over the threshold never walks: its summary stays zero; the counter starts at zero)
+    HIP_TRY(hipMemsetAsync(d_sums, 0, n * sizeof(gact_path_summary) + 16, sl.stream));
+    gact::ChainQueues q{};
+    q.pop_seed = d_counter;
+    q.list_n = -1;
+    const int groups_per_block = (gact::kBlockThreads / 64) * gact::kGroupsPerWave;
+    // (the slot's workspace is sized for grid_blocks blocks of the chain kernels)
+    const int blocks = std::max(1, std::min((n_sel + groups_per_block - 1) / groups_per_block, e->grid_blocks));
+    if (e->C == 20)
+        hipLaunchKernelGGL((gact::summary_kernel<20>), dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, sn.d_rs, sn.d_qf,
+                           sn.d_qr, d_cands, n_sel, gact::kCompInCand, same_file, d_records, q, d_sums, sl.d_ws);
+    else
+        hipLaunchKernelGGL((gact::summary_kernel<32>), dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, sn.d_rs, sn.d_qf,
+                           sn.d_qr, d_cands, n_sel, gact::kCompInCand, same_file, d_records, q, d_sums, sl.d_ws);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(records, d_records, n * sizeof(gact_overlap), hipMemcpyDeviceToHost, sl.stream));
+    HIP_TRY(hipMemcpyAsync(sums, d_sums, n * sizeof(gact_path_summary), hipMemcpyDeviceToHost, sl.stream));
+    HIP_TRY(hipEventRecord(sb.ev1, sl.stream));
+    HIP_TRY(hipEventSynchronize(sb.ev1));
+    HIP_TRY(hipEventElapsedTime(&sb.stats.device_ms, sb.ev0, sb.ev1));
+    sb.stats.launches = 1;
+    sb.stats.scratch_bytes = (int64_t)sb.bytes;
+    sb.timed = true;
+    return 0;
+}
+
+int gact_hip_last_summaries_stats(gact_hip_engine *e, int slot, gact_summaries_stats *stats)
+{
+    int rc = check_slot(e, slot);
+    if (rc) return rc;
+    if (!stats) return fail(GACT_HIP_EINVAL, "last_summaries_stats: NULL argument");
+    const Slot &sl = e->slots[slot];
+    if (!sl.summary.timed) return fail(GACT_HIP_EINVAL, "last_summaries_stats: slot %d has made no summary run yet", slot);
+    *stats = sl.summary.stats;
     return 0;
 }
 
@@ -2544,6 +2659,24 @@ int gact_hip_format_overlap(const gact_overlap *o, const char *ref_name, const c
     // exact bytes of gact.cpp:214-224
     return snprintf(buf, (size_t)cap, "ref_id: %s, query_id: %s, ab: %d, ae: %d, bb: %d, be: %d, score: %d, comp: %d\n",
                     ref_name, query_name, o->ab, o->ae, o->bb, o->be, o->score, o->comp);
+}
+
+int gact_hip_format_paf(const gact_overlap *o, const gact_path_summary *s, const char *query_name, int64_t query_len,
+                        const char *ref_name, int64_t ref_len, char *buf, int32_t cap)
+{
+    if (!o || !s || !ref_name || !query_name || !buf || cap <= 0) return fail(GACT_HIP_EINVAL, "format_paf: bad arguments");
+    const int64_t m = (int64_t)s->n_eq + s->n_x, block = m + s->ins_bases + s->del_bases;
+    if (block <= 0) return fail(GACT_HIP_EINVAL, "format_paf: the summary has no columns");
+    // the span the alignment covers, ending at (ae, be); the query span on the record's strand, then on the read itself
+    const int64_t tend = o->ae, tstart = tend - (m + s->del_bases);
+    const int64_t end = o->be, start = end - (m + s->ins_bases);
+    const int64_t qstart = o->comp ? query_len - end : start, qend = o->comp ? query_len - start : end;
+    const int64_t events = m + s->ins_runs + s->del_runs;      // a gap counts once, whatever its length
+    const double de = 1.0 - (double)s->n_eq / (double)events;
+    return snprintf(buf, (size_t)cap, "%s\t%lld\t%lld\t%lld\t%c\t%s\t%lld\t%lld\t%lld\t%lld\t%lld\t255\tAS:i:%d\tNM:i:%lld\tde:f:%.4f\n",
+                    query_name, (long long)query_len, (long long)qstart, (long long)qend, o->comp ? '-' : '+', ref_name,
+                    (long long)ref_len, (long long)tstart, (long long)tend, (long long)s->n_eq, (long long)block, o->score,
+                    (long long)(block - s->n_eq), de);
 }
 
 }  // extern "C"

@@ -14,7 +14,7 @@ _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.path.join(_PKG, "libgact_hip.so")
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in
            ("gact_engine.hip", "gact_kernels.hpp", "gact_device.hpp", "gact_chain.hpp", "gact_p16.hpp", "gact_p16s.hpp", "gact_lin.hpp",
-            "gact_aff.hpp", "gact_roles.hpp", "gact_coop.hpp", "gact_policy.hpp", "gact_big.hpp", "gact_gather.hpp", "gact_path.hpp",
+            "gact_aff.hpp", "gact_roles.hpp", "gact_coop.hpp", "gact_policy.hpp", "gact_big.hpp", "gact_gather.hpp", "gact_path.hpp", "gact_summary.hpp",
             "dsoft_device.hpp", "dsoft_engine.hpp")] + \
           [os.path.join(_ROOT, "include", "gact_hip.h")]
 
@@ -32,6 +32,8 @@ OVERLAP_DTYPE = np.dtype([(n, "<i4") for n in
                            "first_tile_score", "n_tiles", "reserved")] + [("cells", "<i8")])
 assert TILE_DTYPE.itemsize == 28 and OVERLAP_DTYPE.itemsize == 56
 PATH_DTYPE = np.dtype([("op_offset", "<i8"), ("n_ops", "<i4"), ("n_columns", "<i4")])
+SUMMARY_DTYPE = np.dtype([(n, "<i4") for n in ("n_eq", "n_x", "ins_bases", "del_bases", "eq_runs", "x_runs", "ins_runs", "del_runs")])
+assert SUMMARY_DTYPE.itemsize == 32
 
 # alignment ops (include/gact_hip.h GACT_PATH_OP_*): BAM's CIGAR numbering; an op word is len << 4 | op
 OP_I, OP_D, OP_EQ, OP_X = 1, 2, 7, 8
@@ -41,6 +43,19 @@ _OP_CHARS = {OP_I: "I", OP_D: "D", OP_EQ: "=", OP_X: "X"}
 def cigar_string(ops):
     """op words (len << 4 | op) -> "153=1X2I..." """
     return "".join("%d%s" % (int(w) >> 4, _OP_CHARS[int(w) & 15]) for w in ops)
+
+
+def summarise(ops):
+    """op words -> one SUMMARY_DTYPE record: columns and ops of each kind (what gact_hip_candidates_summaries returns for the
+    candidate whose ops these are, include/gact_hip.h gact_path_summary)"""
+    s = np.zeros((), dtype=SUMMARY_DTYPE)
+    cols = {OP_EQ: "n_eq", OP_X: "n_x", OP_I: "ins_bases", OP_D: "del_bases"}
+    runs = {OP_EQ: "eq_runs", OP_X: "x_runs", OP_I: "ins_runs", OP_D: "del_runs"}
+    for w in ops:
+        n, op = int(w) >> 4, int(w) & 15
+        s[cols[op]] += n
+        s[runs[op]] += 1
+    return s
 
 
 def rescore(ops, scoring=(1, -1, -1, -1)):
@@ -82,6 +97,10 @@ class RunStats(C.Structure):
 class PathsStats(C.Structure):
     _fields_ = [("device_ms", C.c_float), ("chunks", C.c_int32), ("column_bytes", C.c_int64), ("columns", C.c_int64),
                 ("ops", C.c_int64)]
+
+
+class SummariesStats(C.Structure):
+    _fields_ = [("device_ms", C.c_float), ("launches", C.c_int32), ("scratch_bytes", C.c_int64)]
 
 
 class DsoftParams(C.Structure):
@@ -220,6 +239,15 @@ def load():
         L.gact_hip_last_paths_stats.restype = C.c_int
     except AttributeError:
         pass
+    try:
+        L.gact_hip_candidates_summaries.argtypes = [vp, C.c_int, i32, vp, i32, C.c_int, vp, vp]
+        L.gact_hip_candidates_summaries.restype = C.c_int
+        L.gact_hip_last_summaries_stats.argtypes = [vp, C.c_int, C.POINTER(SummariesStats)]
+        L.gact_hip_last_summaries_stats.restype = C.c_int
+        L.gact_hip_format_paf.argtypes = [vp, vp, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_char_p, i32]
+        L.gact_hip_format_paf.restype = C.c_int
+    except AttributeError:
+        pass
     try:                                    # (an older build loaded through GACT_HIP_LIB_PATH for an A/B run has none)
         L.gact_hip_comm_create.argtypes = [vp, i32, i32, C.c_char_p, i32, C.POINTER(vp)]
         L.gact_hip_comm_gather_lines.argtypes = [vp, C.c_int, i32, vp, vp, C.c_int64]
@@ -250,7 +278,8 @@ EXPORTS = ("gact_hip_create", "gact_hip_destroy", "gact_hip_last_error", "gact_h
            "gact_hip_candidates_download", "gact_hip_derive_revcomp", "gact_hip_register_output",
            "gact_hip_unregister_output", "gact_hip_set_option", "gact_hip_prepare",
            "gact_hip_comm_create", "gact_hip_comm_gather_lines", "gact_hip_comm_destroy", "gact_hip_options_describe", "gact_hip_plan_describe",
-           "gact_hip_candidates_paths", "gact_hip_last_paths_stats")
+           "gact_hip_candidates_paths", "gact_hip_last_paths_stats", "gact_hip_candidates_summaries",
+           "gact_hip_last_summaries_stats", "gact_hip_format_paf")
 
 
 def plan(count, flags=0, compute_units=256, tile_size=320, tile_overlap=120, scoring=(1, -1, -1, -1), threshold=35):
@@ -433,6 +462,26 @@ class Engine:
         self._check(self.L.gact_hip_last_paths_stats(self.h, slot, C.byref(st)))
         return {n: getattr(st, n) for n, _ in PathsStats._fields_}
 
+    def candidates_summaries(self, sel=None, n=None, rc_from=0x7fffffff, same_file=True, slot=0):
+        """the alignments of candidates_paths reduced on the device, same selection: (records OVERLAP_DTYPE, sums
+        SUMMARY_DTYPE), sums[k] == summarise(candidate k's ops) (include/gact_hip.h gact_hip_candidates_summaries)"""
+        if sel is not None:
+            sel = np.ascontiguousarray(sel, dtype=np.int32)
+            n = len(sel)
+        n = int(n or 0)
+        records = np.zeros(n, dtype=OVERLAP_DTYPE)
+        sums = np.zeros(n, dtype=SUMMARY_DTYPE)
+        self._check(self.L.gact_hip_candidates_summaries(self.h, slot, n, sel.ctypes.data if sel is not None else None,
+                                                         int(rc_from), int(same_file), records.ctypes.data, sums.ctypes.data))
+        return records, sums
+
+    def last_summaries_stats(self, slot=0):
+        """the slot's last summary run: device ms (HIP events around the whole call), chain-kernel launches, device bytes
+        the call holds for itself"""
+        st = SummariesStats()
+        self._check(self.L.gact_hip_last_summaries_stats(self.h, slot, C.byref(st)))
+        return {n: getattr(st, n) for n, _ in SummariesStats._fields_}
+
     def register_output(self, out, slot=0):
         """page-locks a caller-owned record array that will be fetched into repeatedly (opt-in; it must outlive the
         registration)"""
@@ -512,6 +561,19 @@ class Engine:
         n = self._check(self.L.gact_hip_format_overlap(rec.ctypes.data, ref_name.encode(), query_name.encode(),
                                                        buf, 512))
         return buf.raw[:n].decode()
+
+
+def format_paf(rec, summary, query_name, query_len, ref_name, ref_len, cap=1024):
+    """one PAF line for a record and its summary (include/gact_hip.h gact_hip_format_paf; no engine, no device)"""
+    L = load()
+    rec = np.ascontiguousarray(rec, dtype=OVERLAP_DTYPE)
+    summary = np.ascontiguousarray(summary, dtype=SUMMARY_DTYPE)
+    buf = C.create_string_buffer(cap)
+    n = L.gact_hip_format_paf(rec.ctypes.data, summary.ctypes.data, query_name.encode(), int(query_len), ref_name.encode(),
+                              int(ref_len), buf, cap)
+    if n < 0:
+        raise GactHipError("gact_hip error %d: %s" % (n, L.gact_hip_last_error().decode()))
+    return buf.raw[:min(n, cap - 1)].decode()
 
 
 class Comm:

@@ -2,7 +2,7 @@
 //
 //   darwin_hip <REF.fasta> <READS.fasta> CPU_THREADS [--params params.cfg]
 //              [--candidates FILE | --dump-candidates FILE [--dsoft-only]] [--device-dsoft]
-//              [--device D] [--shard R/W] [--recode] [--cigar]
+//              [--device D] [--shard R/W] [--recode] [--cigar] [--paf]
 //
 // Plays the part of reference darwin.cpp:451-646 for the GACT stage: owns the
 // globals gact.cpp reads, loads params.cfg and the two FASTA files, builds the
@@ -19,6 +19,10 @@
 // filters its read range straight into its slot's device candidate array and extends it from there.
 // --cigar (with --device-dsoft): every line gets ", cigar: <CIGAR>" appended, the alignment of that overlap from a second
 // pass over the emitted candidates (gact_hip_candidates_paths; '=' / 'X' / 'I' / 'D' relative to the reference).
+// --paf (with --device-dsoft): every feeder also writes darwin.<thread>.paf beside its unchanged .out file, one PAF line per
+// emitted overlap that has an alignment, in the .out file's order -- matches, block length and the span the alignment covers
+// from the device's summaries of the emitted candidates (gact_hip_candidates_summaries, gact_hip_format_paf).  With --cigar
+// as well each PAF line carries cg:Z:<CIGAR>.
 //
 // --device D: the GPU this process uses (the reference is single-device, cuda_host.cu:195).  --shard R/W: this
 // process is rank R of W -- it extends every W-th candidate (host filter) or the R-th contiguous range of reads
@@ -56,6 +60,7 @@ int first_tile_score_threshold = 35;
 int tile_size = 320, tile_overlap = 120;
 int num_threads = 1;
 static bool want_cigar = false;                  // --cigar
+static bool want_paf = false;                    // --paf
 std::vector<long long int> reference_lengths, reads_lengths;
 std::vector<std::string> reference_seqs, reads_seqs, rev_reads_seqs;
 std::vector<std::vector<std::string> > reference_descrips, reads_descrips;
@@ -153,6 +158,13 @@ static std::string out_name(int cpu_id)
                            : "darwin." + std::to_string(cpu_id) + ".out";
 }
 
+// --paf: darwin.<thread>.paf beside darwin.<thread>.out
+static std::string paf_name(int cpu_id)
+{
+    const std::string out = out_name(cpu_id);
+    return out.substr(0, out.size() - 3) + "paf";
+}
+
 // darwin.cpp:314-398: the -DGPU build recodes every base in place before GACT_Batch; anything else stays
 static void recode_in_place(std::vector<std::string> &seqs)
 {
@@ -210,15 +222,16 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
     std::vector<int32_t> sel;
     std::vector<gact_path> paths;
     std::vector<uint32_t> ops;
-    if (want_cigar) {
-        // room for every op at once: an alignment has no more ops than columns, and no more columns than the bases of its
-        // record's two spans (its ops end at (ae, be) and start at (ab, bb) or inside those spans, include/gact_hip.h)
-        size_t room = 1;
+    // room for every op at once: an alignment has no more ops than columns, and no more columns than the bases of its
+    // record's two spans (its ops end at (ae, be) and start at (ab, bb) or inside those spans, include/gact_hip.h)
+    size_t room = 1;
+    if (want_cigar || want_paf)
         for (int32_t k = 0; k < n; k++)
             if (o[(size_t)k].emitted) {
                 sel.push_back(k);
                 room += (size_t)(o[(size_t)k].ae - o[(size_t)k].ab) + (size_t)(o[(size_t)k].be - o[(size_t)k].bb);
             }
+    if (want_cigar) {
         std::vector<gact_overlap> rec(sel.size());
         paths.resize(sel.size());
         ops.resize(room);
@@ -232,24 +245,53 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
         }
         check(rc, "gact_hip_candidates_paths");
     }
+    // --paf: their summaries, one more pass on the device that keeps no alignment (gact_hip_candidates_summaries)
+    std::vector<gact_path_summary> sums(sel.size());
+    std::ofstream fpaf;
+    if (want_paf) {
+        std::vector<gact_overlap> rec(sel.size());
+        check(gact_hip_candidates_summaries(e, s.slot, (int32_t)sel.size(), sel.data(), nf, same_file, rec.data(), sums.data()),
+              "gact_hip_candidates_summaries");
+        fpaf.open(paf_name(cpu_id));
+    }
     char line[1024];
-    size_t next = 0;                              // (the emitted records in order: paths[next] is this one's)
+    size_t next = 0;                              // (the emitted records in order: paths[next], sums[next] are this one's)
     for (const gact_overlap &r : o) {
         if (!r.emitted) continue;
         const int len = gact_hip_format_overlap(&r, reference_descrips[r.ref_id][0].c_str(),
                                                 reads_descrips[r.query_id][0].c_str(), line, sizeof line);
-        if (!want_cigar) { fout.write(line, len); continue; }
-        static const char kOp[16] = {'?', 'I', 'D', '?', '?', '?', '?', '=', 'X', '?', '?', '?', '?', '?', '?', '?'};
-        const gact_path &p = paths[next++];
-        std::string text(line, (size_t)(len - 1));            // (without its newline)
-        text += ", cigar: ";
-        for (int32_t k = 0; k < p.n_ops; k++) {
-            const uint32_t w = ops[(size_t)(p.op_offset + k)];
-            text += std::to_string(w >> 4);
-            text += kOp[w & 15];
+        std::string cigar;
+        if (want_cigar) {
+            static const char kOp[16] = {'?', 'I', 'D', '?', '?', '?', '?', '=', 'X', '?', '?', '?', '?', '?', '?', '?'};
+            const gact_path &p = paths[next];
+            for (int32_t k = 0; k < p.n_ops; k++) {
+                const uint32_t w = ops[(size_t)(p.op_offset + k)];
+                cigar += std::to_string(w >> 4);
+                cigar += kOp[w & 15];
+            }
+            std::string text(line, (size_t)(len - 1));            // (without its newline)
+            text += ", cigar: ";
+            text += cigar;
+            text += '\n';
+            fout.write(text.data(), (std::streamsize)text.size());
+        } else {
+            fout.write(line, len);
         }
-        text += '\n';
-        fout.write(text.data(), (std::streamsize)text.size());
+        if (want_paf) {
+            const gact_path_summary &sm = sums[next];
+            if (sm.n_eq + sm.n_x + sm.ins_bases + sm.del_bases > 0) {        // (a record without an alignment has no PAF line)
+                char paf[2048];
+                const int plen = gact_hip_format_paf(&r, &sm, reads_descrips[r.query_id][0].c_str(),
+                                                     (int64_t)reads_seqs[r.query_id].size(), reference_descrips[r.ref_id][0].c_str(),
+                                                     (int64_t)reference_seqs[r.ref_id].size(), paf, sizeof paf);
+                if (plen <= 0 || plen >= (int)sizeof paf) { printf("\ngact_hip_format_paf failed: %s\n\n", gact_hip_last_error()); exit(-1); }
+                std::string text(paf, (size_t)(plen - 1));
+                if (want_cigar) { text += "\tcg:Z:"; text += cigar; }
+                text += '\n';
+                fpaf.write(text.data(), (std::streamsize)text.size());
+            }
+        }
+        next++;
     }
     print_stage("Time GACT calling", t1, now());                 // darwin.cpp:441
 }
@@ -419,7 +461,7 @@ int main(int argc, char *argv[])
     if (argc >= 3 && strcmp(argv[1], "--selftest") == 0) return selftest(argv[2]);
     if (argc < 4) {
         fprintf(stderr, "Usage: darwin_hip <REFERENCE>.fasta <READS>.fasta CPU_THREADS --candidates FILE "
-                        "[--params params.cfg]\n");
+                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf]]\n");
         return 1;
     }
     std::string cand_path, dump_path, cfg_path = "params.cfg", gather_id;
@@ -432,6 +474,7 @@ int main(int argc, char *argv[])
         else if (!strcmp(argv[a], "--device-dsoft")) device_dsoft = true;
         else if (!strcmp(argv[a], "--recode")) recode = true;
         else if (!strcmp(argv[a], "--cigar")) want_cigar = true;
+        else if (!strcmp(argv[a], "--paf")) want_paf = true;
         else if (!strcmp(argv[a], "--rccl-gather") && a + 1 < argc) gather_id = argv[++a];
         else if (!strcmp(argv[a], "--device") && a + 1 < argc) setenv("GACT_HIP_DEVICE", argv[++a], 1);   // read by GPU_init
         else if (!strcmp(argv[a], "--shard") && a + 1 < argc) {
@@ -444,6 +487,11 @@ int main(int argc, char *argv[])
         // the host-filter mode writes through the reference-signature GACT_Batch, which has no alignment to give; the gathered
         // output would need the CIGARs gathered too
         fprintf(stderr, "--cigar: only with --device-dsoft, and not with --rccl-gather\n");
+        return 1;
+    }
+    if (want_paf && (!device_dsoft || !gather_id.empty())) {
+        // (for the same reasons: the summaries come from the engine's own candidate arrays, and would have to be gathered)
+        fprintf(stderr, "--paf: only with --device-dsoft, and not with --rccl-gather\n");
         return 1;
     }
     std::map<std::string, double> cfg = parse_cfg(cfg_path);

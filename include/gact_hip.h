@@ -266,6 +266,30 @@ typedef struct {
 } gact_paths_stats;
 int gact_hip_last_paths_stats(gact_hip_engine *e, int slot, gact_paths_stats *stats);
 
+/* ---- alignment summaries: what identity, NM or a PAF line need of every selected candidate's alignment, without the ops ----
+ * A second opt-in pass like the one above, for the caller that does not want the alignment itself: the int32 chain kernel runs
+ * the selected chains once more and its walker COUNTS the columns instead of storing them (csrc/gact_summary.hpp).
+ *   sums[k]  exactly what reducing candidate k's ops of gact_hip_candidates_paths gives: columns per kind and ops (runs) per
+ *            kind over the whole alignment, the left part followed by the right part -- a run that goes on from one tile into
+ *            the next, or across the junction of the two parts, is one run.  eq_runs + x_runs + ins_runs + del_runs = n_ops,
+ *            n_eq + n_x + ins_bases + del_bases = n_columns.  A chain with no tile over the threshold: all eight fields 0.
+ * Selection (sel, sel == NULL, rc_from, same_file, n_sel == 0), records[k] and the refusals are those of
+ * gact_hip_candidates_paths.  Synchronous on the slot's stream, never merged with other slots' runs; the slot's record array,
+ * run statistics and paths statistics stay as they were.  One chain-kernel launch for any selection, whatever
+ * GACT_HIP_PATH_BUDGET_MB says, and no device memory but the selection's candidates, records and summaries. */
+typedef struct {
+    int32_t n_eq, n_x;             /* '=' columns, 'X' columns */
+    int32_t ins_bases, del_bases;  /* 'I' columns (query base against a gap), 'D' columns (ref base against a gap) */
+    int32_t eq_runs, x_runs, ins_runs, del_runs;   /* ops of each kind in the candidate's CIGAR */
+} gact_path_summary;               /* 32 bytes */
+int gact_hip_candidates_summaries(gact_hip_engine *e, int slot, int32_t n_sel, const int32_t *sel, int32_t rc_from,
+                                  int same_file, gact_overlap *records, gact_path_summary *sums);
+/* What the slot's last gact_hip_candidates_summaries call that got as far as the device did: HIP events on the slot's stream
+ * around the whole call, chain-kernel launches (1), and the device memory the call holds for itself (candidates, records,
+ * summaries and one counter: proportional to n_sel, nothing sized by read length). */
+typedef struct { float device_ms; int32_t launches; int64_t scratch_bytes; } gact_summaries_stats;
+int gact_hip_last_summaries_stats(gact_hip_engine *e, int slot, gact_summaries_stats *stats);
+
 /* ------------------------------------------------------------------------
  * D-SOFT seed filter on the device (the stage in front of the path; optional:
  * the reference's host filter keeps working against the calls above).
@@ -430,6 +454,17 @@ int gact_hip_measure_valu_rate(gact_hip_engine *e, double *lane_ops_per_s);
 /* formats the exact bytes of gact.cpp:214-224 */
 int gact_hip_format_overlap(const gact_overlap *o, const char *ref_name, const char *query_name,
                             char *buf, int32_t cap);
+
+/* One PAF line for a record and its summary (no engine, no device), returning its length as gact_hip_format_overlap does:
+ *   qname qlen qstart qend strand tname tlen tstart tend nmatch blocklen 255 AS:i:<score> NM:i:<n_x + ins_bases + del_bases>
+ *   de:f:<1 - n_eq / (n_eq + n_x + ins_runs + del_runs), four decimals>
+ * nmatch = n_eq, blocklen = the four column counts together.  Coordinates are 0-based, half-open, and the span the alignment
+ * really covers: target [ae - (n_eq + n_x + del_bases), ae), query [be - (n_eq + n_x + ins_bases), be) on the record's strand --
+ * not ab / bb, which stay where the left extension stopped when it aligned nothing (see gact_hip_candidates_paths).  For
+ * comp == 1 the query span is mapped to the original read (qstart = qlen - end, qend = qlen - start) and the strand is '-'.
+ * The line ends in '\n'; a caller that appends a cg:Z: tag overwrites it.  GACT_HIP_EINVAL for a summary without columns. */
+int gact_hip_format_paf(const gact_overlap *o, const gact_path_summary *s, const char *query_name, int64_t query_len,
+                        const char *ref_name, int64_t ref_len, char *buf, int32_t cap);
 
 #ifdef __cplusplus
 }
