@@ -195,6 +195,7 @@ int gact_hip_dsoft_query(gact_hip_engine *e, int slot, int32_t first_query, int3
     scr.staged_cap = d.staged_cap;
 
     HIP_TRY(hipEventRecord(sl.ev0, sl.stream));
+    sl.forget_times();
     std::vector<int32_t> counts((size_t)n_tasks);
     for (int attempt = 0;; attempt++) {
         dsoft::QueryOut qo;

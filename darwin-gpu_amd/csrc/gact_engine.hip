@@ -135,6 +135,12 @@ struct Slot {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_mid = nullptr;
     bool timed = false, two_phase = false, wide = false, lin = false, aff = false;
+    // the run's three times as gact_hip_last_run_stats first read them: the runtime makes an elapsed time from its events anew
+    // at every reading and two readings of the same events differ by a nanosecond now and then, so a run's times are read once
+    // and kept until the slot's events are recorded again (forget_times)
+    float run_ms[3] = {0, 0, 0};
+    bool run_ms_kept = false;
+    void forget_times() { run_ms_kept = false; }
     DevBuf<gact_tile> tiles;
     DevBuf<gact_tile_result> results;
     DevBuf<uint8_t> states;
@@ -228,6 +234,21 @@ struct Slot {
             p = nullptr; bytes = 0; ev0 = ev1 = nullptr;
         }
     } summary;
+    // gact_hip_select_overlaps (gact_select.hpp): one allocation, grown to what the largest selection so far needed
+    struct SelectBufs {
+        uint8_t *p = nullptr;                          // host records | table | positions | flags | counts | sel
+        size_t bytes = 0;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;       // around the whole call (gact_hip_last_select_stats)
+        gact_select_stats stats{};
+        bool timed = false;
+        void release()
+        {
+            if (p) (void)hipFree(p);
+            if (ev0) (void)hipEventDestroy(ev0);
+            if (ev1) (void)hipEventDestroy(ev1);
+            p = nullptr; bytes = 0; ev0 = ev1 = nullptr;
+        }
+    } select;
 };
 
 // device-side D-SOFT filter (dsoft_device.hpp)
@@ -1133,6 +1154,7 @@ int run_tiles(gact_hip_engine *e, Slot &sl, const SeqSet &rs, const SeqSet &qf, 
     HIP_TRY(hipMemsetAsync(sl.results.p, 0, (size_t)n * sizeof(gact_tile_result), sl.stream));
     { int prc = poison_ws(e, sl, 0x2545f491u); if (prc) return prc; }
     HIP_TRY(hipEventRecord(sl.ev0, sl.stream));
+    sl.forget_times();
     int rc = e->big_cb ? launch_big_tiles(e, sl, rs, qf, qr, n, states_stride)
            : (e->C == 20) ? launch_tiles<20>(e, sl, rs, qf, qr, n, states_stride)
                           : launch_tiles<32>(e, sl, rs, qf, qr, n, states_stride);
@@ -1379,6 +1401,7 @@ void gact_hip_destroy(gact_hip_engine *e)
         sl.inline_ref.release(); sl.inline_query.release();
         sl.path.release();
         sl.summary.release();
+        sl.select.release();
         if (sl.d_counter) (void)hipFree(sl.d_counter);
         if (sl.d_flags) (void)hipFree(sl.d_flags);
         if (sl.d_ws) (void)hipFree(sl.d_ws);
@@ -1663,6 +1686,7 @@ static int launch_run(gact_hip_engine *e, Slot &sl, int first, int n, int rc_fro
     HIP_TRY(hipMemsetAsync(sl.d_counter, 0, kCounterInts * sizeof(int), sl.stream));
     if ((rc = poison_ws(e, sl, 0))) return rc;
     HIP_TRY(hipEventRecord(sl.ev0, sl.stream));
+    sl.forget_times();
     sl.two_phase = false;
     sl.merged_into = -1; sl.merged_callers = 1;
     if (n > 0) {
@@ -1758,6 +1782,7 @@ static int launch_merged(gact_hip_engine *e, const std::vector<RunReq *> &batch)
         dst.merge_prev_gen = dst.merge_gen;
         dst.merge_gen = cb.merged_launches;
         dst.timed = true;
+        dst.forget_times();
     }
     cb.merged_launches++; cb.merged_runs += (long)batch.size();
     return 0;
@@ -2318,6 +2343,17 @@ int gact_hip_last_kernel_ms(gact_hip_engine *e, int slot, float *ms)
     return 0;
 }
 
+// the times of one run are the same at every reading (Slot::run_ms): the first reading's
+static void keep_times(Slot &sl, gact_hip_run_stats *st)
+{
+    if (sl.run_ms_kept) {
+        st->total_ms = sl.run_ms[0]; st->seed_ms = sl.run_ms[1]; st->main_ms = sl.run_ms[2];
+    } else {
+        sl.run_ms[0] = st->total_ms; sl.run_ms[1] = st->seed_ms; sl.run_ms[2] = st->main_ms;
+        sl.run_ms_kept = true;
+    }
+}
+
 int gact_hip_last_run_stats(gact_hip_engine *e, int slot, gact_hip_run_stats *st)
 {
     int rc = check_slot(e, slot);
@@ -2358,6 +2394,7 @@ int gact_hip_last_run_stats(gact_hip_engine *e, int slot, gact_hip_run_stats *st
                 st->seed_cells += sc;
             }
         }
+        keep_times(e->slots[slot], st);
         return 0;
     }
     Slot &sl = e->slots[slot];
@@ -2390,6 +2427,7 @@ int gact_hip_last_run_stats(gact_hip_engine *e, int slot, gact_hip_run_stats *st
             st->seed_cells += sc;
         }
     }
+    keep_times(sl, st);
     return 0;
 }
 
@@ -2587,6 +2625,7 @@ int gact_hip_measure_valu_rate(gact_hip_engine *e, double *lane_ops_per_s)
 
 #include "dsoft_engine.hpp"      // gact_hip_dsoft_build / _query / candidates_download
 #include "gact_gather.hpp"       // gact_hip_comm_*: the RCCL gather of a sharded job
+#include "gact_select.hpp"       // gact_hip_select_overlaps: one overlap per class, behind every other kernel
 
 #ifdef GACT_STAMPS
 // diagnostic build: per-wave (start, queues empty, end, iterations) of the last main launch

@@ -14,7 +14,7 @@ _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.path.join(_PKG, "libgact_hip.so")
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in
            ("gact_engine.hip", "gact_kernels.hpp", "gact_device.hpp", "gact_chain.hpp", "gact_p16.hpp", "gact_p16s.hpp", "gact_lin.hpp",
-            "gact_aff.hpp", "gact_roles.hpp", "gact_coop.hpp", "gact_policy.hpp", "gact_big.hpp", "gact_gather.hpp", "gact_path.hpp", "gact_summary.hpp",
+            "gact_aff.hpp", "gact_roles.hpp", "gact_coop.hpp", "gact_policy.hpp", "gact_big.hpp", "gact_gather.hpp", "gact_path.hpp", "gact_summary.hpp", "gact_select.hpp",
             "dsoft_device.hpp", "dsoft_engine.hpp")] + \
           [os.path.join(_ROOT, "include", "gact_hip.h")]
 
@@ -101,6 +101,15 @@ class PathsStats(C.Structure):
 
 class SummariesStats(C.Structure):
     _fields_ = [("device_ms", C.c_float), ("launches", C.c_int32), ("scratch_bytes", C.c_int64)]
+
+
+class SelectStats(C.Structure):
+    _fields_ = [("device_ms", C.c_float), ("emitted", C.c_int32), ("selected", C.c_int32), ("table_slots", C.c_int64),
+                ("scratch_bytes", C.c_int64)]
+
+
+SELECT_EXACT, SELECT_PAIR = 0, 1
+_SELECT_MODES = {"exact": SELECT_EXACT, "pair": SELECT_PAIR}
 
 
 class DsoftParams(C.Structure):
@@ -248,6 +257,13 @@ def load():
         L.gact_hip_format_paf.restype = C.c_int
     except AttributeError:
         pass
+    try:
+        L.gact_hip_select_overlaps.argtypes = [vp, C.c_int, i32, vp, i32, vp, i32, C.POINTER(i32)]
+        L.gact_hip_select_overlaps.restype = C.c_int
+        L.gact_hip_last_select_stats.argtypes = [vp, C.c_int, C.POINTER(SelectStats)]
+        L.gact_hip_last_select_stats.restype = C.c_int
+    except AttributeError:
+        pass
     try:                                    # (an older build loaded through GACT_HIP_LIB_PATH for an A/B run has none)
         L.gact_hip_comm_create.argtypes = [vp, i32, i32, C.c_char_p, i32, C.POINTER(vp)]
         L.gact_hip_comm_gather_lines.argtypes = [vp, C.c_int, i32, vp, vp, C.c_int64]
@@ -279,7 +295,7 @@ EXPORTS = ("gact_hip_create", "gact_hip_destroy", "gact_hip_last_error", "gact_h
            "gact_hip_unregister_output", "gact_hip_set_option", "gact_hip_prepare",
            "gact_hip_comm_create", "gact_hip_comm_gather_lines", "gact_hip_comm_destroy", "gact_hip_options_describe", "gact_hip_plan_describe",
            "gact_hip_candidates_paths", "gact_hip_last_paths_stats", "gact_hip_candidates_summaries",
-           "gact_hip_last_summaries_stats", "gact_hip_format_paf")
+           "gact_hip_last_summaries_stats", "gact_hip_format_paf", "gact_hip_select_overlaps", "gact_hip_last_select_stats")
 
 
 def plan(count, flags=0, compute_units=256, tile_size=320, tile_overlap=120, scoring=(1, -1, -1, -1), threshold=35):
@@ -321,6 +337,7 @@ class Engine:
                         threshold, device_id, n_slots, max_blocks)
         self.h = C.c_void_p()
         self._registered = {}
+        self._n_cands = {}                            # slot -> candidates it holds (select_overlaps' default n)
         self._check(self.L.gact_hip_create(C.byref(self.p), C.byref(self.h)))
         self.tile_size = tile_size
         self.tile_overlap = tile_overlap
@@ -408,11 +425,13 @@ class Engine:
         out = np.zeros(len(cands), dtype=OVERLAP_DTYPE)
         self._check(self.L.gact_hip_extend_candidates(self.h, slot, len(cands), cands.ctypes.data,
                                                       int(complement), int(same_file), out.ctypes.data))
+        self._n_cands[slot] = len(cands)
         return out
 
     def candidates_upload(self, cands, slot=0):
         cands = np.ascontiguousarray(cands, dtype=CAND_DTYPE)
         self._check(self.L.gact_hip_candidates_upload(self.h, slot, len(cands), cands.ctypes.data))
+        self._n_cands[slot] = len(cands)
 
     def candidates_run(self, n, complement=False, same_file=True, slot=0, first=0):
         self._check(self.L.gact_hip_candidates_run_range(self.h, slot, first, n, int(complement), int(same_file)))
@@ -482,6 +501,36 @@ class Engine:
         self._check(self.L.gact_hip_last_summaries_stats(self.h, slot, C.byref(st)))
         return {n: getattr(st, n) for n, _ in SummariesStats._fields_}
 
+    def select_overlaps(self, n=None, records=None, mode="pair", slot=0):
+        """every overlap once, chosen on the device: the ascending int32 indices of the records to keep, usable as `sel` of
+        candidates_paths / candidates_summaries.  records None: records [0, n) of the slot's device array as its last run
+        left them (n None: as many as the slot holds candidates); else the caller's OVERLAP_DTYPE records (n None: all of them).  mode "exact": the lowest index of every
+        set of emitted records that print the same line; "pair": per (ref_id, query_id, comp) the record with the highest
+        score, then the larger (ae - ab) + (be - bb), then the lower index (include/gact_hip.h gact_hip_select_overlaps)"""
+        if isinstance(mode, str):
+            if mode not in _SELECT_MODES:
+                raise GactHipError("select_overlaps: unknown mode %r (\"exact\" or \"pair\")" % (mode,))
+            mode = _SELECT_MODES[mode]
+        if records is not None:
+            records = np.ascontiguousarray(records, dtype=OVERLAP_DTYPE)
+            n = len(records) if n is None else n
+            assert n <= len(records)
+        elif n is None:
+            n = self._n_cands.get(slot, 0)
+        n = int(n)
+        sel = np.empty(max(n, 0), dtype=np.int32)
+        n_sel = C.c_int32()
+        self._check(self.L.gact_hip_select_overlaps(self.h, slot, n, records.ctypes.data if records is not None else None,
+                                                    mode, sel.ctypes.data, n, C.byref(n_sel)))
+        return sel[:n_sel.value].copy()
+
+    def last_select_stats(self, slot=0):
+        """the slot's last selection: device ms (HIP events around the whole call), emitted records, selected records,
+        table slots, device bytes the call holds for itself"""
+        st = SelectStats()
+        self._check(self.L.gact_hip_last_select_stats(self.h, slot, C.byref(st)))
+        return {n: getattr(st, n) for n, _ in SelectStats._fields_}
+
     def register_output(self, out, slot=0):
         """page-locks a caller-owned record array that will be fetched into repeatedly (opt-in; it must outlive the
         registration)"""
@@ -522,6 +571,7 @@ class Engine:
         nf, nr, ms = C.c_int32(), C.c_int32(), C.c_float()
         self._check(self.L.gact_hip_dsoft_query(self.h, slot, first_query, n_queries, C.byref(nf), C.byref(nr),
                                                 C.byref(ms)))
+        self._n_cands[slot] = nf.value + nr.value
         return nf.value, nr.value, float(ms.value)
 
     def candidates_download(self, n, slot=0):

@@ -2,7 +2,7 @@
 //
 //   darwin_hip <REF.fasta> <READS.fasta> CPU_THREADS [--params params.cfg]
 //              [--candidates FILE | --dump-candidates FILE [--dsoft-only]] [--device-dsoft]
-//              [--device D] [--shard R/W] [--recode] [--cigar] [--paf]
+//              [--device D] [--shard R/W] [--recode] [--cigar] [--paf] [--unique exact|pair]
 //
 // Plays the part of reference darwin.cpp:451-646 for the GACT stage: owns the
 // globals gact.cpp reads, loads params.cfg and the two FASTA files, builds the
@@ -23,6 +23,10 @@
 // emitted overlap that has an alignment, in the .out file's order -- matches, block length and the span the alignment covers
 // from the device's summaries of the emitted candidates (gact_hip_candidates_summaries, gact_hip_format_paf).  With --cigar
 // as well each PAF line carries cg:Z:<CIGAR>.
+// --unique exact|pair (with --device-dsoft, not with --shard): every feeder selects among its run's records on the device
+// (gact_hip_select_overlaps) -- exact: each line once, what `sort | uniq` of its file would leave; pair: one line per (ref, query,
+// strand), the overlap with the highest score, then the longer one, then the earlier one.  The .out file keeps its order and
+// gets the selected lines only, and --cigar / --paf make their second pass over the selected records only.
 //
 // --device D: the GPU this process uses (the reference is single-device, cuda_host.cu:195).  --shard R/W: this
 // process is rank R of W -- it extends every W-th candidate (host filter) or the R-th contiguous range of reads
@@ -61,6 +65,7 @@ int tile_size = 320, tile_overlap = 120;
 int num_threads = 1;
 static bool want_cigar = false;                  // --cigar
 static bool want_paf = false;                    // --paf
+static int unique_mode = -1;                     // --unique: GACT_SELECT_EXACT / GACT_SELECT_PAIR, -1: every emitted record
 std::vector<long long int> reference_lengths, reads_lengths;
 std::vector<std::string> reference_seqs, reads_seqs, rev_reads_seqs;
 std::vector<std::vector<std::string> > reference_descrips, reads_descrips;
@@ -218,7 +223,16 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
     std::vector<gact_overlap> o((size_t)n);
     check(gact_hip_candidates_run_mixed(e, s.slot, 0, n, nf, same_file), "gact_hip_candidates_run_mixed");
     check(gact_hip_candidates_fetch(e, s.slot, n, o.data()), "gact_hip_candidates_fetch");
-    // --cigar: the alignments of the emitted candidates, a second pass on the device (gact_hip_candidates_paths)
+    // --unique: which of the records to keep, chosen on the device among the slot's records (ascending, emitted ones only)
+    std::vector<char> keep((size_t)n, 1);
+    if (unique_mode >= 0) {
+        std::vector<int32_t> kept((size_t)n);
+        int32_t n_kept = 0;
+        check(gact_hip_select_overlaps(e, s.slot, n, nullptr, unique_mode, kept.data(), n, &n_kept), "gact_hip_select_overlaps");
+        std::fill(keep.begin(), keep.end(), 0);
+        for (int32_t k = 0; k < n_kept; k++) keep[(size_t)kept[(size_t)k]] = 1;
+    }
+    // --cigar: the alignments of the emitted (--unique: selected) candidates, a second pass on the device (gact_hip_candidates_paths)
     std::vector<int32_t> sel;
     std::vector<gact_path> paths;
     std::vector<uint32_t> ops;
@@ -227,7 +241,7 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
     size_t room = 1;
     if (want_cigar || want_paf)
         for (int32_t k = 0; k < n; k++)
-            if (o[(size_t)k].emitted) {
+            if (o[(size_t)k].emitted && keep[(size_t)k]) {
                 sel.push_back(k);
                 room += (size_t)(o[(size_t)k].ae - o[(size_t)k].ab) + (size_t)(o[(size_t)k].be - o[(size_t)k].bb);
             }
@@ -256,8 +270,9 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
     }
     char line[1024];
     size_t next = 0;                              // (the emitted records in order: paths[next], sums[next] are this one's)
-    for (const gact_overlap &r : o) {
-        if (!r.emitted) continue;
+    for (int32_t at = 0; at < n; at++) {
+        const gact_overlap &r = o[(size_t)at];
+        if (!r.emitted || !keep[(size_t)at]) continue;
         const int len = gact_hip_format_overlap(&r, reference_descrips[r.ref_id][0].c_str(),
                                                 reads_descrips[r.query_id][0].c_str(), line, sizeof line);
         std::string cigar;
@@ -461,7 +476,7 @@ int main(int argc, char *argv[])
     if (argc >= 3 && strcmp(argv[1], "--selftest") == 0) return selftest(argv[2]);
     if (argc < 4) {
         fprintf(stderr, "Usage: darwin_hip <REFERENCE>.fasta <READS>.fasta CPU_THREADS --candidates FILE "
-                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf]]\n");
+                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair]]\n");
         return 1;
     }
     std::string cand_path, dump_path, cfg_path = "params.cfg", gather_id;
@@ -475,6 +490,12 @@ int main(int argc, char *argv[])
         else if (!strcmp(argv[a], "--recode")) recode = true;
         else if (!strcmp(argv[a], "--cigar")) want_cigar = true;
         else if (!strcmp(argv[a], "--paf")) want_paf = true;
+        else if (!strcmp(argv[a], "--unique")) {
+            const char *v = a + 1 < argc ? argv[++a] : "";
+            if (!strcmp(v, "exact")) unique_mode = GACT_SELECT_EXACT;
+            else if (!strcmp(v, "pair")) unique_mode = GACT_SELECT_PAIR;
+            else { fprintf(stderr, "--unique wants exact or pair, not '%s'\n", v); return 1; }
+        }
         else if (!strcmp(argv[a], "--rccl-gather") && a + 1 < argc) gather_id = argv[++a];
         else if (!strcmp(argv[a], "--device") && a + 1 < argc) setenv("GACT_HIP_DEVICE", argv[++a], 1);   // read by GPU_init
         else if (!strcmp(argv[a], "--shard") && a + 1 < argc) {
@@ -492,6 +513,12 @@ int main(int argc, char *argv[])
     if (want_paf && (!device_dsoft || !gather_id.empty())) {
         // (for the same reasons: the summaries come from the engine's own candidate arrays, and would have to be gathered)
         fprintf(stderr, "--paf: only with --device-dsoft, and not with --rccl-gather\n");
+        return 1;
+    }
+    if (unique_mode >= 0 && (!device_dsoft || shard_world > 1)) {
+        // the selection runs over the records of one engine slot: the host-filter mode writes through GACT_Batch, and the ranks of
+        // a sharded job each hold part of a pair's candidates, so a selection per rank would be incomplete
+        fprintf(stderr, "--unique: only with --device-dsoft, and not with --shard\n");
         return 1;
     }
     std::map<std::string, double> cfg = parse_cfg(cfg_path);

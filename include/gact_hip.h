@@ -290,6 +290,37 @@ int gact_hip_candidates_summaries(gact_hip_engine *e, int slot, int32_t n_sel, c
 typedef struct { float device_ms; int32_t launches; int64_t scratch_bytes; } gact_summaries_stats;
 int gact_hip_last_summaries_stats(gact_hip_engine *e, int slot, gact_summaries_stats *stats);
 
+/* ---- selection: every overlap once, chosen on the device ahead of the fetch and of the second passes above ----
+ * D-SOFT emits one candidate per diagonal bin over the threshold and a long overlap drifts over several bins, so a read pair is
+ * extended more than once and the chains converge on the same or nearly the same overlap; the reference leaves the repeats to
+ * `cat darwin.*.out | sort | uniq` (README:25).  This entry returns the indices of the records to keep (csrc/gact_select.hpp):
+ *   GACT_SELECT_EXACT  class: emitted records that agree in ref_id, query_id, comp, ab, ae, bb, be and score -- the fields a line
+ *                      is printed from (gact.cpp:214-224), what `sort | uniq` compares.  Kept: the lowest index of each class.
+ *   GACT_SELECT_PAIR   class: emitted records that agree in (ref_id, query_id, comp).  Kept: the best record of each class
+ *                      under the total order 1. higher score, 2. larger (ae - ab) + (be - bb), 3. lower index.
+ * Records with emitted == 0 are never selected and belong to no class.
+ *   records == NULL  records [0, n) of the slot's device-resident array as its last run left them; the call waits for that run
+ *                    on the slot's stream, as gact_hip_comm_gather_lines does
+ *   records != NULL  the caller's n host records, copied to the device first (rank 0 of a sharded job over the records it
+ *                    gathered; records that come from no alignment)
+ *   sel, *n_sel      the selected indices, ascending, the same list on every call; sel can be passed unchanged as `sel` to
+ *                    gact_hip_candidates_paths and gact_hip_candidates_summaries
+ * Synchronous on the slot's stream; the slot's record array, run statistics, paths statistics and summaries statistics stay as
+ * they were.  Device memory of its own (the table, 4 bytes per slot, and about 8 bytes per record; 56 more per host record),
+ * allocated on the first call and grown on demand.  n == 0 returns 0 with *n_sel = 0.  sel_cap < *n_sel (or sel == NULL):
+ * returns GACT_HIP_EINVAL with *n_sel filled -- call again with room for it, as with gact_hip_candidates_paths.  Refused
+ * (GACT_HIP_EINVAL, *n_sel = 0): an unknown mode, n < 0 or n > 2^30, records == NULL on a slot without records or with n beyond
+ * them. */
+#define GACT_SELECT_EXACT 0
+#define GACT_SELECT_PAIR  1
+int gact_hip_select_overlaps(gact_hip_engine *e, int slot, int32_t n, const gact_overlap *records,
+                             int32_t mode, int32_t *sel, int32_t sel_cap, int32_t *n_sel);
+/* What the slot's last gact_hip_select_overlaps call that got as far as the device did: HIP events on the slot's stream around
+ * the whole call (copies and kernels), emitted records among the n, records selected, slots of the table (a power of two
+ * >= 2 n), and the device memory the call holds for itself. */
+typedef struct { float device_ms; int32_t emitted, selected; int64_t table_slots, scratch_bytes; } gact_select_stats;
+int gact_hip_last_select_stats(gact_hip_engine *e, int slot, gact_select_stats *stats);
+
 /* ------------------------------------------------------------------------
  * D-SOFT seed filter on the device (the stage in front of the path; optional:
  * the reference's host filter keeps working against the calls above).
@@ -339,7 +370,8 @@ int gact_hip_last_kernel_ms(gact_hip_engine *e, int slot, float *ms);
  * candidate, arg-max + full pointer matrix) and the main launch (packed-int16
  * kernel, every later tile). */
 typedef struct {
-    float total_ms, seed_ms, main_ms;   /* HIP events on the slot's stream */
+    float total_ms, seed_ms, main_ms;   /* HIP events on the slot's stream; read once per run, so every reading of a run gives
+                                           the same three values */
     int32_t packed16;                   /* 0: one int32 launch; 1: seed + packed-int16 main launch, uniform
                                            column layout; 2: the same, split (two-region) layout; 3: wide layout
                                            (32 lanes per tile pair, chosen when there are few chains) */
