@@ -138,11 +138,14 @@ int DsoftIndex::query(const char *q, uint32_t len, int query_id, DsoftScratch &s
                 const uint32_t new_count = ((offset - last_offset > k) || curr_count == 0)
                                                ? curr_count + k : curr_count + (offset - last_offset);   // :137
                 sc.bin_count_offset[bin] = ((uint64_t)new_count << 32) + offset;
+                // :146-149, but ahead of the `break`: the reference leaves a bin that crosses on its first hit
+                // (threshold <= k) counted for the next query of the thread; every query starts clean here, as on
+                // the device
+                if (curr_count == 0) sc.nz_bins.push_back(bin);
                 if (new_count >= (uint32_t)p_.threshold) {
                     if ((int)sc.hits.size() >= p_.max_candidates) break;    // :141-143 (leaves the hit loop only)
                     sc.hits.push_back(((uint64_t)hit << 32) + offset);
                 }
-                if (curr_count == 0) sc.nz_bins.push_back(bin);             // :146-149
             }
         }
     });

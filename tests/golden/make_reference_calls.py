@@ -28,7 +28,7 @@ def recorded():
 
 before = recorded()
 rc = subprocess.call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", "-m", "not gpu", "-k", "reference",
-                      "tests/test_dsoft.py", "tests/test_oracle.py", "tests/test_paths_model.py"],
+                      "tests/test_dsoft.py", "tests/test_dsoft_model.py", "tests/test_oracle.py", "tests/test_paths_model.py"],
                      cwd=ROOT, env=dict(os.environ, GACT_RECORD_REFERENCE_CALLS="1"))
 # the file is rewritten as a whole: a call that was in it and is gone means a test that replays it lost its answer
 lost = before - recorded()
