@@ -249,6 +249,21 @@ struct Slot {
             p = nullptr; bytes = 0; ev0 = ev1 = nullptr;
         }
     } select;
+    // gact_hip_read_coverage (gact_cover.hpp): one allocation, grown to what the largest call so far needed
+    struct CoverBufs {
+        uint8_t *p = nullptr;                          // host records | sel | sums | offsets | cover | flag | differences | depth
+        size_t bytes = 0;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;       // around the whole call (gact_hip_last_cover_stats)
+        gact_cover_stats stats{};
+        bool timed = false;
+        void release()
+        {
+            if (p) (void)hipFree(p);
+            if (ev0) (void)hipEventDestroy(ev0);
+            if (ev1) (void)hipEventDestroy(ev1);
+            p = nullptr; bytes = 0; ev0 = ev1 = nullptr;
+        }
+    } cover;
 };
 
 // device-side D-SOFT filter (dsoft_device.hpp)
@@ -1402,6 +1417,7 @@ void gact_hip_destroy(gact_hip_engine *e)
         sl.path.release();
         sl.summary.release();
         sl.select.release();
+        sl.cover.release();
         if (sl.d_counter) (void)hipFree(sl.d_counter);
         if (sl.d_flags) (void)hipFree(sl.d_flags);
         if (sl.d_ws) (void)hipFree(sl.d_ws);
@@ -2626,6 +2642,7 @@ int gact_hip_measure_valu_rate(gact_hip_engine *e, double *lane_ops_per_s)
 #include "dsoft_engine.hpp"      // gact_hip_dsoft_build / _query / candidates_download
 #include "gact_gather.hpp"       // gact_hip_comm_*: the RCCL gather of a sharded job
 #include "gact_select.hpp"       // gact_hip_select_overlaps: one overlap per class, behind every other kernel
+#include "gact_cover.hpp"        // gact_hip_read_coverage: per-read coverage of an overlap set, behind those
 
 #ifdef GACT_STAMPS
 // diagnostic build: per-wave (start, queues empty, end, iterations) of the last main launch

@@ -14,7 +14,7 @@ _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.path.join(_PKG, "libgact_hip.so")
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in
            ("gact_engine.hip", "gact_kernels.hpp", "gact_device.hpp", "gact_chain.hpp", "gact_p16.hpp", "gact_p16s.hpp", "gact_lin.hpp",
-            "gact_aff.hpp", "gact_roles.hpp", "gact_coop.hpp", "gact_policy.hpp", "gact_big.hpp", "gact_gather.hpp", "gact_path.hpp", "gact_summary.hpp", "gact_select.hpp",
+            "gact_aff.hpp", "gact_roles.hpp", "gact_coop.hpp", "gact_policy.hpp", "gact_big.hpp", "gact_gather.hpp", "gact_path.hpp", "gact_summary.hpp", "gact_select.hpp", "gact_cover.hpp",
             "dsoft_device.hpp", "dsoft_engine.hpp")] + \
           [os.path.join(_ROOT, "include", "gact_hip.h")]
 
@@ -34,6 +34,9 @@ assert TILE_DTYPE.itemsize == 28 and OVERLAP_DTYPE.itemsize == 56
 PATH_DTYPE = np.dtype([("op_offset", "<i8"), ("n_ops", "<i4"), ("n_columns", "<i4")])
 SUMMARY_DTYPE = np.dtype([(n, "<i4") for n in ("n_eq", "n_x", "ins_bases", "del_bases", "eq_runs", "x_runs", "ins_runs", "del_runs")])
 assert SUMMARY_DTYPE.itemsize == 32
+COVER_DTYPE = np.dtype([(n, "<i4") for n in ("n_intervals", "max_depth", "covered", "well_covered", "span_begin", "span_end")] +
+                       [("depth_sum", "<i8")])
+assert COVER_DTYPE.itemsize == 32
 
 # alignment ops (include/gact_hip.h GACT_PATH_OP_*): BAM's CIGAR numbering; an op word is len << 4 | op
 OP_I, OP_D, OP_EQ, OP_X = 1, 2, 7, 8
@@ -110,6 +113,15 @@ class SelectStats(C.Structure):
 
 SELECT_EXACT, SELECT_PAIR = 0, 1
 _SELECT_MODES = {"exact": SELECT_EXACT, "pair": SELECT_PAIR}
+
+
+class CoverStats(C.Structure):
+    _fields_ = [("device_ms", C.c_float), ("reads", C.c_int32), ("intervals", C.c_int64), ("positions", C.c_int64),
+                ("scratch_bytes", C.c_int64)]
+
+
+COVER_REF, COVER_QUERY, COVER_BOTH = 1, 2, 3
+_COVER_SIDES = {"ref": COVER_REF, "query": COVER_QUERY, "both": COVER_BOTH}
 
 
 class DsoftParams(C.Structure):
@@ -264,6 +276,13 @@ def load():
         L.gact_hip_last_select_stats.restype = C.c_int
     except AttributeError:
         pass
+    try:
+        L.gact_hip_read_coverage.argtypes = [vp, C.c_int, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp]
+        L.gact_hip_read_coverage.restype = C.c_int
+        L.gact_hip_last_cover_stats.argtypes = [vp, C.c_int, C.POINTER(CoverStats)]
+        L.gact_hip_last_cover_stats.restype = C.c_int
+    except AttributeError:
+        pass
     try:                                    # (an older build loaded through GACT_HIP_LIB_PATH for an A/B run has none)
         L.gact_hip_comm_create.argtypes = [vp, i32, i32, C.c_char_p, i32, C.POINTER(vp)]
         L.gact_hip_comm_gather_lines.argtypes = [vp, C.c_int, i32, vp, vp, C.c_int64]
@@ -295,7 +314,8 @@ EXPORTS = ("gact_hip_create", "gact_hip_destroy", "gact_hip_last_error", "gact_h
            "gact_hip_unregister_output", "gact_hip_set_option", "gact_hip_prepare",
            "gact_hip_comm_create", "gact_hip_comm_gather_lines", "gact_hip_comm_destroy", "gact_hip_options_describe", "gact_hip_plan_describe",
            "gact_hip_candidates_paths", "gact_hip_last_paths_stats", "gact_hip_candidates_summaries",
-           "gact_hip_last_summaries_stats", "gact_hip_format_paf", "gact_hip_select_overlaps", "gact_hip_last_select_stats")
+           "gact_hip_last_summaries_stats", "gact_hip_format_paf", "gact_hip_select_overlaps", "gact_hip_last_select_stats",
+           "gact_hip_read_coverage", "gact_hip_last_cover_stats")
 
 
 def plan(count, flags=0, compute_units=256, tile_size=320, tile_overlap=120, scoring=(1, -1, -1, -1), threshold=35):
@@ -530,6 +550,47 @@ class Engine:
         st = SelectStats()
         self._check(self.L.gact_hip_last_select_stats(self.h, slot, C.byref(st)))
         return {n: getattr(st, n) for n, _ in SelectStats._fields_}
+
+    def read_coverage(self, read_lens, n=None, records=None, sel=None, sums=None, sides="both", min_depth=3, depth=False, slot=0):
+        """per-read coverage of an overlap set, swept on the device: one COVER_DTYPE record per read of `read_lens` -- intervals
+        counted, highest depth, positions covered, positions covered min_depth deep, the longest (leftmost) run of those, the
+        sum of the depth -- or (cover, depth) with the int32 depth of every position, read after read, when `depth` is set.
+        records None: records [0, n) of the slot's device array as its last run left them (n None: as many as the slot holds
+        candidates); else the caller's OVERLAP_DTYPE records.  sel: the indices that count (select_overlaps' list), None: all;
+        records that were not emitted never count.  sums: SUMMARY_DTYPE, one per chosen record: the begins become the
+        alignment's, as the PAF lines have them.  sides "ref" / "query" / "both" or COVER_REF / COVER_QUERY / COVER_BOTH
+        (include/gact_hip.h gact_hip_read_coverage)"""
+        if isinstance(sides, str):
+            if sides not in _COVER_SIDES:
+                raise GactHipError("read_coverage: unknown sides %r (\"ref\", \"query\" or \"both\")" % (sides,))
+            sides = _COVER_SIDES[sides]
+        read_lens = np.ascontiguousarray(read_lens, dtype=np.int32)
+        if records is not None:
+            records = np.ascontiguousarray(records, dtype=OVERLAP_DTYPE)
+            n = len(records) if n is None else n
+            assert n <= len(records)
+        elif n is None:
+            n = self._n_cands.get(slot, 0)
+        n = int(n)
+        if sel is not None:
+            sel = np.ascontiguousarray(sel, dtype=np.int32)
+        if sums is not None:
+            sums = np.ascontiguousarray(sums, dtype=SUMMARY_DTYPE)
+            assert len(sums) == (len(sel) if sel is not None else n)
+        cover = np.zeros(len(read_lens), dtype=COVER_DTYPE)
+        per_base = np.zeros(int(read_lens.astype(np.int64).clip(0).sum()), dtype=np.int32) if depth else None
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        self._check(self.L.gact_hip_read_coverage(self.h, slot, n, ptr(records), len(sel) if sel is not None else 0, ptr(sel),
+                                                  ptr(sums), int(sides), int(min_depth), len(read_lens), ptr(read_lens),
+                                                  ptr(cover), ptr(per_base)))
+        return (cover, per_base) if depth else cover
+
+    def last_cover_stats(self, slot=0):
+        """the slot's last coverage call: device ms (HIP events around the whole call), reads, intervals counted, positions,
+        device bytes the call holds for itself"""
+        st = CoverStats()
+        self._check(self.L.gact_hip_last_cover_stats(self.h, slot, C.byref(st)))
+        return {n: getattr(st, n) for n, _ in CoverStats._fields_}
 
     def register_output(self, out, slot=0):
         """page-locks a caller-owned record array that will be fetched into repeatedly (opt-in; it must outlive the

@@ -2,7 +2,7 @@
 //
 //   darwin_hip <REF.fasta> <READS.fasta> CPU_THREADS [--params params.cfg]
 //              [--candidates FILE | --dump-candidates FILE [--dsoft-only]] [--device-dsoft]
-//              [--device D] [--shard R/W] [--recode] [--cigar] [--paf] [--unique exact|pair]
+//              [--device D] [--shard R/W] [--recode] [--cigar] [--paf] [--unique exact|pair] [--coverage K]
 //
 // Plays the part of reference darwin.cpp:451-646 for the GACT stage: owns the
 // globals gact.cpp reads, loads params.cfg and the two FASTA files, builds the
@@ -27,6 +27,12 @@
 // (gact_hip_select_overlaps) -- exact: each line once, what `sort | uniq` of its file would leave; pair: one line per (ref, query,
 // strand), the overlap with the highest score, then the longer one, then the earlier one.  The .out file keeps its order and
 // gets the selected lines only, and --cigar / --paf make their second pass over the selected records only.
+// --coverage K (with --device-dsoft, not with --shard; K >= 1): after the feeders have finished, the records they wrote (the
+// emitted ones; with --unique the selected ones) go through one gact_hip_read_coverage call, and darwin.cover.tsv gets one line
+// per sequence in id order: name, len, n_intervals, max_depth, covered, well_covered (depth >= K), span_begin, span_end (the
+// longest stretch that is covered K deep) and mean_depth, tab-separated.  Same file: both sides of every record over the
+// reads; different files: the ref side over the reference sequences.  With --paf the summaries go along, so the table is what
+// the .paf files' own columns give.  Every other output byte is as without the flag.
 //
 // --device D: the GPU this process uses (the reference is single-device, cuda_host.cu:195).  --shard R/W: this
 // process is rank R of W -- it extends every W-th candidate (host filter) or the R-th contiguous range of reads
@@ -66,6 +72,10 @@ int num_threads = 1;
 static bool want_cigar = false;                  // --cigar
 static bool want_paf = false;                    // --paf
 static int unique_mode = -1;                     // --unique: GACT_SELECT_EXACT / GACT_SELECT_PAIR, -1: every emitted record
+static int coverage_depth = 0;                   // --coverage K: min_depth of darwin.cover.tsv, 0: no table
+// --coverage: the records every feeder wrote a line for, in its file's order, and with --paf their summaries
+static std::vector<std::vector<gact_overlap> > cover_records;
+static std::vector<std::vector<gact_path_summary> > cover_sums;
 std::vector<long long int> reference_lengths, reads_lengths;
 std::vector<std::string> reference_seqs, reads_seqs, rev_reads_seqs;
 std::vector<std::vector<std::string> > reference_descrips, reads_descrips;
@@ -273,6 +283,10 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
     for (int32_t at = 0; at < n; at++) {
         const gact_overlap &r = o[(size_t)at];
         if (!r.emitted || !keep[(size_t)at]) continue;
+        if (coverage_depth) {
+            cover_records[(size_t)cpu_id].push_back(r);
+            if (want_paf) cover_sums[(size_t)cpu_id].push_back(sums[next]);
+        }
         const int len = gact_hip_format_overlap(&r, reference_descrips[r.ref_id][0].c_str(),
                                                 reads_descrips[r.query_id][0].c_str(), line, sizeof line);
         std::string cigar;
@@ -309,6 +323,33 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
         next++;
     }
     print_stage("Time GACT calling", t1, now());                 // darwin.cpp:441
+}
+
+// --coverage: one call over the records all feeders kept, on slot 0, then darwin.cover.tsv
+static int write_coverage(gact_hip_engine *e)
+{
+    std::vector<gact_overlap> rec;
+    std::vector<gact_path_summary> sums;
+    for (const auto &v : cover_records) rec.insert(rec.end(), v.begin(), v.end());
+    for (const auto &v : cover_sums) sums.insert(sums.end(), v.begin(), v.end());
+    const std::vector<std::string> &seqs = same_file ? reads_seqs : reference_seqs;
+    const std::vector<std::vector<std::string> > &names = same_file ? reads_descrips : reference_descrips;
+    std::vector<int32_t> lens(seqs.size());
+    for (size_t i = 0; i < seqs.size(); i++) lens[i] = (int32_t)seqs[i].size();
+    std::vector<gact_read_cover> cover(seqs.size());
+    const int rc = gact_hip_read_coverage(e, 0, (int32_t)rec.size(), rec.data(), 0, nullptr, want_paf ? sums.data() : nullptr,
+                                          same_file ? GACT_COVER_BOTH : GACT_COVER_REF, coverage_depth, (int32_t)lens.size(),
+                                          lens.data(), cover.data(), nullptr);
+    if (rc != 0) { printf("\ngact_hip_read_coverage failed: %s\n\n", gact_hip_last_error()); return 1; }
+    FILE *f = fopen("darwin.cover.tsv", "w");
+    if (!f) { fprintf(stderr, "--coverage: cannot write darwin.cover.tsv\n"); return 1; }
+    for (size_t i = 0; i < cover.size(); i++) {
+        const gact_read_cover &c = cover[i];
+        fprintf(f, "%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.3f\n", names[i][0].c_str(), lens[i], c.n_intervals, c.max_depth, c.covered,
+                c.well_covered, c.span_begin, c.span_end, lens[i] ? (double)c.depth_sum / lens[i] : 0.0);
+    }
+    fclose(f);
+    return 0;
 }
 
 // --rccl-gather IDFILE (with --shard R/W): this rank's share as ONE run on the engine (no feeder threads: a run is fastest
@@ -476,11 +517,11 @@ int main(int argc, char *argv[])
     if (argc >= 3 && strcmp(argv[1], "--selftest") == 0) return selftest(argv[2]);
     if (argc < 4) {
         fprintf(stderr, "Usage: darwin_hip <REFERENCE>.fasta <READS>.fasta CPU_THREADS --candidates FILE "
-                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair]]\n");
+                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K]]\n");
         return 1;
     }
     std::string cand_path, dump_path, cfg_path = "params.cfg", gather_id;
-    bool dsoft_only = false, device_dsoft = false, recode = false;
+    bool dsoft_only = false, device_dsoft = false, recode = false, shard_given = false;
     for (int a = 4; a < argc; a++) {
         if (!strcmp(argv[a], "--candidates") && a + 1 < argc) cand_path = argv[++a];
         else if (!strcmp(argv[a], "--dump-candidates") && a + 1 < argc) dump_path = argv[++a];
@@ -496,9 +537,17 @@ int main(int argc, char *argv[])
             else if (!strcmp(v, "pair")) unique_mode = GACT_SELECT_PAIR;
             else { fprintf(stderr, "--unique wants exact or pair, not '%s'\n", v); return 1; }
         }
+        else if (!strcmp(argv[a], "--coverage")) {
+            const char *v = a + 1 < argc ? argv[++a] : "";
+            char *end = nullptr;
+            const long k = strtol(v, &end, 10);
+            if (!*v || *end || k < 1 || k > 0x7fffffffL) { fprintf(stderr, "--coverage wants an integer >= 1, not '%s'\n", v); return 1; }
+            coverage_depth = (int)k;
+        }
         else if (!strcmp(argv[a], "--rccl-gather") && a + 1 < argc) gather_id = argv[++a];
         else if (!strcmp(argv[a], "--device") && a + 1 < argc) setenv("GACT_HIP_DEVICE", argv[++a], 1);   // read by GPU_init
         else if (!strcmp(argv[a], "--shard") && a + 1 < argc) {
+            shard_given = true;
             if (sscanf(argv[++a], "%d/%d", &shard_rank, &shard_world) != 2 || shard_world < 1 || shard_rank < 0 ||
                 shard_rank >= shard_world) { fprintf(stderr, "--shard wants R/W with 0 <= R < W\n"); return 1; }
         } else { fprintf(stderr, "unknown option %s\n", argv[a]); return 1; }
@@ -519,6 +568,12 @@ int main(int argc, char *argv[])
         // the selection runs over the records of one engine slot: the host-filter mode writes through GACT_Batch, and the ranks of
         // a sharded job each hold part of a pair's candidates, so a selection per rank would be incomplete
         fprintf(stderr, "--unique: only with --device-dsoft, and not with --shard\n");
+        return 1;
+    }
+    if (coverage_depth && (!device_dsoft || shard_given)) {
+        // the table is made from the records of one process's feeders: the host-filter mode keeps none (it writes through
+        // GACT_Batch), and a rank of a sharded job holds part of every read's overlaps
+        fprintf(stderr, "--coverage: only with --device-dsoft, and not with --shard\n");
         return 1;
     }
     std::map<std::string, double> cfg = parse_cfg(cfg_path);
@@ -575,6 +630,8 @@ int main(int argc, char *argv[])
         const int reads_per_thread = (int)std::ceil(1.0 * num_reads / num_threads);
         std::vector<std::vector<Cand> > dumps(num_threads);
         const bool dumping = !dump_path.empty() && dsoft_only;
+        cover_records.resize((size_t)num_threads);
+        cover_sums.resize((size_t)num_threads);
         std::vector<std::thread> threads;
         t_stage = now();
         for (int i = 0; i < num_threads; i++) {
@@ -589,8 +646,9 @@ int main(int argc, char *argv[])
             for (auto &v : dumps) { out.write((const char *)v.data(), (std::streamsize)(v.size() * sizeof(Cand))); total += v.size(); }
             printf("num_candidates: %zu\n", total);
         }
+        const int cover_rc = coverage_depth && !dumping ? write_coverage(e) : 0;
         GPU_close(&s, num_threads);
-        return 0;
+        return cover_rc;
     }
 
     // per-thread candidate lists, contiguous read ranges like darwin.cpp:619-629

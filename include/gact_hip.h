@@ -321,6 +321,65 @@ int gact_hip_select_overlaps(gact_hip_engine *e, int slot, int32_t n, const gact
 typedef struct { float device_ms; int32_t emitted, selected; int64_t table_slots, scratch_bytes; } gact_select_stats;
 int gact_hip_last_select_stats(gact_hip_engine *e, int slot, gact_select_stats *stats);
 
+/* ---- per-read coverage: how deep every read is covered by an overlap set, and where it is covered min_depth deep ----
+ * What a consumer of the overlaps (miniasm, racon) computes first: the depth along every read, and the stretch of it that is
+ * covered at least min_depth deep -- the rest is adapter or chimera and gets clipped; for reads against contigs, the depth the
+ * reads give each contig.  A read-level statistic: containment and transitive reduction stay with the assembler.  The records
+ * are on the device when a run ends, and so are the indices of gact_hip_select_overlaps and the summaries of
+ * gact_hip_candidates_summaries; this entry sweeps them there (csrc/gact_cover.hpp).
+ *   records          as in gact_hip_select_overlaps: NULL = records [0, n) of the slot's device-resident array as its last run
+ *                    left them (the call waits for that run on the slot's stream); else the caller's n host records, copied over
+ *   sel, n_sel       which records count: sel == NULL, every record of [0, n) (n_sel is ignored); else sel[0..n_sel), the list of
+ *                    gact_hip_select_overlaps unchanged.  A record with emitted == 0 never counts, named by sel or not
+ *   sides            GACT_COVER_REF: a counted record puts [ab, ae) on read ref_id.  GACT_COVER_QUERY: it puts [bb, be) of its
+ *                    strand on read query_id -- [bb, be) for comp == 0, [len - be, len - bb) for comp == 1, len =
+ *                    read_lens[query_id].  GACT_COVER_BOTH: both; ref and query ids name the same reads (self-overlap).  No
+ *                    special rule for ref_id == query_id (the run paths emit no such record with same_file, gact.cpp:213)
+ *   sums             NULL, or sums[k] = the summary of the k-th chosen record (sel[k]; record k when sel == NULL).  The begins
+ *                    are then ae - (n_eq + n_x + del_bases) and be - (n_eq + n_x + ins_bases): the spans gact_hip_format_paf
+ *                    prints, so the result agrees with the PAF lines also where the left extension aligned nothing and ab / bb
+ *                    stayed at the hit.  A summary without columns gives empty intervals
+ *   read_lens        the n_reads lengths; every interval is clipped to [0, len) of its read, and an interval that is empty then
+ *                    is dropped and not counted
+ *   cover[i]         read i: intervals counted, the highest depth, positions with depth >= 1, positions with depth >= min_depth,
+ *                    the longest run of such positions [span_begin, span_end) -- of several longest the leftmost, 0, 0 when there
+ *                    is none -- and the sum of the depth over the read.  The depth of a position is the number of counted
+ *                    intervals that contain it; intervals are half-open: [a, b) and [b, c) make no dip and no spike at b
+ *   depth            NULL, or room for sum(read_lens) values: the depth of every position, read after read, no padding
+ * Synchronous on the slot's stream; the slot's records and its run, paths, summaries and select statistics stay as they were.
+ * All results are integers, the same on every call and every slot.  A read of length 0 gets all zeros; n_reads == 0 returns 0;
+ * n == 0 returns 0 with every cover[i] (and depth) zero.
+ * Refused with GACT_HIP_EINVAL: min_depth < 1, sides not 1, 2 or 3, n < 0 or n > 2^30, n_reads < 0, a negative length (or one
+ * above 2^31 - 65), records == NULL on a slot without records or with n beyond them, n_sel < 0 with sel, an index in sel outside
+ * [0, n).  Refused with GACT_HIP_ERANGE: a counted record whose read id for a requested side is outside [0, n_reads).  On a
+ * refusal cover and depth are untouched.
+ * Device memory of its own, one allocation per slot made on the first call, grown on demand and released with the engine:
+ * 4 (sum(len) + n_reads) bytes of depth differences and 40 bytes per read, 4 sum(len) more when depth is asked for, 56 per
+ * host record, 4 per sel entry, 32 per summary -- 1.7 GB for 418 Mb of reads (3.3 GB with depth).  An allocation that fails
+ * returns GACT_HIP_ENOMEM.  One wave sweeps one read: right for reads, correct and slow for a chromosome-length sequence. */
+#define GACT_COVER_REF   1   /* the interval a record puts on its ref_id   */
+#define GACT_COVER_QUERY 2   /* the interval a record puts on its query_id */
+#define GACT_COVER_BOTH  3   /* both; ref and query ids name the same read set (self-overlap) */
+typedef struct {
+    int32_t n_intervals;          /* intervals counted on this read (after clipping, empty ones dropped) */
+    int32_t max_depth;
+    int32_t covered;              /* positions with depth >= 1 */
+    int32_t well_covered;         /* positions with depth >= min_depth */
+    int32_t span_begin, span_end; /* the longest run of positions with depth >= min_depth, [begin, end);
+                                     of several longest runs the leftmost; 0, 0 when there is none */
+    int64_t depth_sum;            /* sum of depth over the read's positions */
+} gact_read_cover;                /* 32 bytes */
+int gact_hip_read_coverage(gact_hip_engine *e, int slot, int32_t n, const gact_overlap *records,
+                           int32_t n_sel, const int32_t *sel, const gact_path_summary *sums,
+                           int32_t sides, int32_t min_depth,
+                           int32_t n_reads, const int32_t *read_lens,
+                           gact_read_cover *cover, int32_t *depth);
+/* What the slot's last gact_hip_read_coverage call that got as far as the device did: HIP events on the slot's stream around
+ * the whole call (copies and kernels), the reads, the intervals counted on them, their positions (sum(read_lens)), and the
+ * device memory the call holds for itself. */
+typedef struct { float device_ms; int32_t reads; int64_t intervals, positions, scratch_bytes; } gact_cover_stats;
+int gact_hip_last_cover_stats(gact_hip_engine *e, int slot, gact_cover_stats *stats);
+
 /* ------------------------------------------------------------------------
  * D-SOFT seed filter on the device (the stage in front of the path; optional:
  * the reference's host filter keeps working against the calls above).
