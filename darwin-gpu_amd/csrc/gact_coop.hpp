@@ -202,8 +202,10 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
     __shared__ int bank_lds[kGroupsPerBlock][kCoopBanks][6];   // {R_A, Q_A, R_B, Q_B, state word of the jobs in flight (0: none), -}
     __shared__ uint32_t walk_lock;
 
+    uint32_t *const lin_lut = LinLutLds<L::kLutWords>::get();      // the pass's table of look-up words (gact_lin.hpp 8.)
     for (int n = threadIdx.x; n < kCoopJobs; n += kBlockThreads) jstate[n] = 0;
     if (threadIdx.x == 0) walk_lock = 0;
+    lin_lut_fill(lin_lut, kc, (int)threadIdx.x);
     __syncthreads();
 
     const int wave_in_block = threadIdx.x >> 6;
@@ -434,13 +436,14 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
         const int tB = wave_min_groups<LANES>(imin(reach0, reach1));
         pt.col_from = imax(imin(have[0] ? pt.Q[0] : 0x7fff, have[1] ? pt.Q[1] : 0x7fff) - kp.early, 0);
         pt.band = kp.band;
+        pt.lut = lin_lut;
         pt.shift[0] = have[0] ? T_end - Tend_h[0] : 0;
         pt.shift[1] = have[1] ? T_end - Tend_h[1] : 0;
 
         GACT_STAMP(t_b);
         uint32_t qb[L::kSlotsPerLane];
         uint32_t *stage = stage_lds[group_in_block][bank];
-        load_pair_packed<L::kSlotsPerLane, LANES, typename L::Cols, false>(refs, qfwd, qrc, pt, w.gl, ref8, G::kRefBytes, G::kRow0, q8, G::kTileMax, qb,
+        load_pair_packed<L::kSlotsPerLane, LANES, typename L::Cols, false, kLinPadRow>(refs, qfwd, qrc, pt, w.gl, ref8, G::kRefBytes, G::kRow0, q8, G::kTileMax, qb,
                                                                           stage, typename L::Cols{});
         wave_sync();
         GACT_STAMP(t_c);

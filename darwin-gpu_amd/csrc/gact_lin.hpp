@@ -98,6 +98,15 @@ __device__ __forceinline__ uint32_t pk_ashr2(uint32_t a)
     return r;
 }
 
+// 8. Look-up words out of LDS (round 6).  A row's look-up word -- the one-hot byte table the v_perm of every column slot
+//    reads -- used to be made per row and tile with a shift by the stream byte, a byte extraction and, in the pointer phase,
+//    the +1 per byte: 8 of the 18 VALU instructions a step of the split pass spent outside its recurrence.  There are only
+//    five such words per phase, so the block keeps them in LDS, [code 3, 2, 1, 0, pad] x [plain, pointer phase]
+//    interleaved, and the stream byte (24 - 8 code, kLinPadRow for a row outside the tile) is the byte offset of the
+//    pair: a ds_read_u8 and a ds_read_b32 with an immediate table address per row and tile, no VALU instruction.
+//    word(b, plain) = dsub >> b, word(b, pointer phase) = (dsub4 >> b) + 0x01010101, the pad's 0 and 0x01010101.
+//    (lin_lut_fill and LinLutLds: gact_p16.hpp, beside the loader that writes the stream)
+
 // Pointer words of this pass (walk_chain's FMT 3): two bits per cell, the op code alone.  A half-word holds eight
 // stored steps of one column (first step on top), a dword two adjacent columns (the even one low), a uint4 eight
 // columns; a flush block is [uint4 n][lane], n < kUint4 (ws_quad_addr, gact_device.hpp).
@@ -160,7 +169,8 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
                                                       const uint32_t (&qb)[C1 + C2],
                                                       const int T_end, const int tB,
                                                       uint32_t *__restrict__ wsA, uint32_t *__restrict__ wsB,
-                                                      const int band, const bool fullA, const bool fullB)
+                                                      const int band, const bool fullA, const bool fullB,
+                                                      const uint32_t *lut_lds)
 {
     constexpr int CT = C1 + C2;
     constexpr int NW = LinWords<C2>::kWords, QD = LinWords<C2>::kUint4;
@@ -168,7 +178,7 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
     const int g = (int)(int16_t)(kc.ext & 0xffffu);
     const uint32_t gv = vconst(kc.next), g4v = vconst(kc.next4), c3v = vconst(kc.c3), onev = vconst(kc.one),
                    dtv = vconst(kc.next4 + kc.tag1),               // 4|g| + 1: G'' (tagged 2) -> D'' tagged 1
-                   c2v = vconst(kc.tag2), lut1v = vconst(0x01010101u);
+                   c2v = vconst(kc.tag2);
     // zero level of the row a lane did "before step 1": region 1 is at row t - gl, region 2 at row t - gl - LAG
     uint32_t Z1 = pk2(lin_base(g) + gl * g), Z2 = pk2(lin_base(g) + (gl + LAG) * g);
     uint32_t G[CT];                         // H of the previous row (drifted)
@@ -181,13 +191,18 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
     uint32_t H1 = Z1, H2 = Z2;
     uint32_t Hdiag1 = Z1, Hdiag2 = Z2;
 
-    auto lut = [&](uint32_t amount) { return kc.dsub >> (amount & 31u); };
-    auto lut4 = [&](uint32_t amount) { return kc.dsub4 >> (amount & 31u); };
-    uint32_t rb1 = 0, rb1b = 0, rb2 = 0, rb2b = 0;
-    {
-        const uint32_t w1 = ref16[1], w2 = ref16[1 - LAG];
-        rb1 = lut(w1 & 0xffu); rb1b = lut(w1 >> 8); rb2 = lut(w2 & 0xffu); rb2b = lut(w2 >> 8);
-    }
+    // Look-up words (LinLut above): a row's byte in the ref stream IS the byte offset of its word in the table, so a row
+    // costs two LDS reads per tile and no VALU instruction.  rp: this lane's stream bytes of region 2's row at the step
+    // to come (tile A, tile B); region 1's are LAG entries further on.  Before step t: rb1 / rb1b = row t of region 1,
+    // rb2 / rb2b = row t - LAG of region 2.
+    typedef __attribute__((address_space(3))) const uint8_t LdsByte;
+    typedef __attribute__((address_space(3))) const uint32_t LdsWord;
+    LdsByte *const lut_plain = (LdsByte *)lut_lds, *const lut_tagged = (LdsByte *)(lut_lds + 1);
+    auto row = [](LdsByte *table, uint32_t stream_byte) { return *(LdsWord *)(table + stream_byte); };
+    LdsByte *rp = (LdsByte *)(ref16 + (1 - LAG));
+    uint32_t rb1 = row(lut_plain, rp[2 * LAG]), rb1b = row(lut_plain, rp[2 * LAG + 1]);
+    uint32_t rb2 = row(lut_plain, rp[0]), rb2b = row(lut_plain, rp[1]);
+    rp += 2;
 
     // Instruction order.  With three waves on a SIMD a v_add / v_sub / v_and / v_or issues in 1.9 cycles when it does
     // not wait for the instruction in front of it, in 3.0 when it does (issue_rate_probe.json, dependent streams).
@@ -195,6 +210,18 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
     // two regions' column chains (H_left -> D -> H, two dependent instructions per slot) run side by side; the
     // scheduling barriers keep the compiler from folding the stages back into per-slot sequences.
 #define GACT_SB() __builtin_amdgcn_sched_barrier(0)
+    // the next step's rows: the stream bytes are asked for when the step begins, their look-up words once the v_perm stage
+    // has read the current ones (the bytes have had that stage's time to arrive, the words have the rest of the step)
+    uint32_t sb1 = 0, sb1b = 0, sb2 = 0, sb2b = 0;
+    auto ask_bytes = [&](const bool r1, const bool r2) {
+        if (r2) { sb2 = rp[0]; sb2b = rp[1]; }
+        if (r1) { sb1 = rp[2 * LAG]; sb1b = rp[2 * LAG + 1]; }
+        rp += 2;
+    };
+    auto ask_rows = [&](const bool r1, const bool r2, const bool tag2) {
+        if (r1) { rb1 = row(lut_plain, sb1); rb1b = row(lut_plain, sb1b); }
+        if (r2) { rb2 = row(tag2 ? lut_tagged : lut_plain, sb2); rb2b = row(tag2 ? lut_tagged : lut_plain, sb2b); }
+    };
     auto upper_all = [&](uint32_t (&U)[CT], const bool tag2, const uint32_t Zr2) {
         uint32_t P[CT];
 #pragma unroll
@@ -204,7 +231,7 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         for (int c = 0; c < CT; c++) U[c] = (c == 0 ? Hdiag1 : c == C1 ? Hdiag2 : G[c - 1]) + P[c];   // align.cpp:134-144
         // (pointer phase: region 2's G is kept tagged 2, so it IS H_up'' as it stands; the look-up words of that phase
         //  carry a +1, so M'' = G_diag'' + 4 (sub - g) + 1 comes out tagged 3 with no instruction of its own)
-        (void)tag2;
+        ask_rows(true, true, tag2);
         GACT_SB();
         if (GACT_LIN_MAX3) {
 #pragma unroll
@@ -220,8 +247,8 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         GACT_SB();
     };
 
-    auto step = [&](const int t) {
-        const uint32_t w1 = ref16[t + 1], w2 = ref16[t + 1 - LAG];
+    auto step = [&]() {
+        ask_bytes(true, true);
         Z1 += gv; Z2 += gv;
         // lane 0 of region 1 sits on the j = 0 border: the zero level
         const uint32_t Hl1 = (uint32_t)dpp_row_shr1((int)H1, (int)Z1);
@@ -243,11 +270,10 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
 #pragma unroll
         for (int c = 2 * C1; c < CT; c++) { G[c] = pk_max(U[c], Hb - gv); Hb = G[c]; }
         H1 = Ha; H2 = Hb;
-        rb1 = lut(w1 & 0xffu); rb1b = lut(w1 >> 8); rb2 = lut(w2 & 0xffu); rb2b = lut(w2 >> 8);
     };
     // a step in which region 2 is in front of its row 1 in every lane (see 7. below): region 1 alone, region 2's zero level
-    auto step_r1 = [&](const int t) {
-        const uint32_t w1 = ref16[t + 1];
+    auto step_r1 = [&]() {
+        ask_bytes(true, false);
         Z1 += gv; Z2 += gv;
         const uint32_t Hl1 = (uint32_t)dpp_row_shr1((int)H1, (int)Z1);
         uint32_t P[C1], U[C1];
@@ -256,6 +282,7 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         GACT_SB();
 #pragma unroll
         for (int c = 0; c < C1; c++) U[c] = (c == 0 ? Hdiag1 : G[c - 1]) + P[c];
+        ask_rows(true, false, false);
         GACT_SB();
 #pragma unroll
         for (int c = 0; c < C1; c++) U[c] = GACT_LIN_MAX3 ? pk_max3f(U[c], Z1, G[c]) : pk_max(pk_max(U[c], Z1), G[c]);
@@ -265,15 +292,14 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
 #pragma unroll
         for (int c = 0; c < C1; c++) { G[c] = pk_max(U[c], Ha - gv); Ha = G[c]; }
         H1 = Ha;
-        rb1 = lut(w1 & 0xffu); rb1b = lut(w1 >> 8);
     };
 
     // ---- pointer phase: region 2 on tagged scores; G = 4H + 2 there: H_up'' without an instruction, the diagonal gets
     //      its tag 3 from the look-up word (+1), the left neighbour its tag 1 from the gap subtraction (4|g| + 1), and
     //      "low bits := 2" is one fast-class v_bitop3_b32
     uint32_t Z24 = 0;
-    auto step_tagged = [&](const int t) {
-        const uint32_t w1 = ref16[t + 1], w2 = ref16[t + 1 - LAG];
+    auto step_tagged = [&]() {
+        ask_bytes(true, true);
         Z1 += gv; Z24 += g4v;
         const uint32_t Hl1 = (uint32_t)dpp_row_shr1((int)H1, (int)Z1);
         // lane 15's region-1 column enters region 2 scaled and tagged 2
@@ -301,12 +327,11 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         }
         acc[C2 - 1] = pk_shl_add4(acc[C2 - 1], tprev);
         H1 = Ha; H2 = Hb;
-        rb1 = lut(w1 & 0xffu); rb1b = lut(w1 >> 8); rb2 = lut4(w2 & 0xffu) + lut1v; rb2b = lut4(w2 >> 8) + lut1v;
     };
     // a step of the pointer phase in which region 1 is past its last row in every lane (see 7. below): region 2 alone; H1
     // stays what lane 15 left at step T_end - LAG
-    auto step_tagged_r2 = [&](const int t) {
-        const uint32_t w2 = ref16[t + 1 - LAG];
+    auto step_tagged_r2 = [&]() {
+        ask_bytes(false, true);
         Z24 += g4v;
         const uint32_t Hl2 = (uint32_t)dpp_row_shr1((int)H2, dpp_row_ror1((int)pk_mad4v(H1, c2v)));
         uint32_t P[C2], U[C2];
@@ -315,6 +340,7 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         GACT_SB();
 #pragma unroll
         for (int c = 0; c < C2; c++) U[c] = (c == 0 ? Hdiag2 : G[C1 + c - 1]) + P[c];
+        ask_rows(false, true, true);
         GACT_SB();
 #pragma unroll
         for (int c = 0; c < C2; c++) U[c] = GACT_LIN_MAX3 ? pk_max3f(U[c], Z24, G[C1 + c]) : pk_max(pk_max(U[c], Z24), G[C1 + c]);
@@ -336,7 +362,6 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         }
         acc[C2 - 1] = pk_shl_add4(acc[C2 - 1], tprev);
         H2 = Hb;
-        rb2 = lut4(w2 & 0xffu) + lut1v; rb2b = lut4(w2 >> 8) + lut1v;
     };
 #undef GACT_SB
     auto enter_tagged = [&]() {
@@ -345,7 +370,8 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         H2 = pk_mad4v(H2, c2v);
         Hdiag2 = pk_mad4v(Hdiag2, c2v);
         Z24 = pk_mad4v(Z2, c3v);                        // the zero level stays tagged 3 (H == 0 reads as MATCH, see 3.)
-        rb2 = (rb2 << 2) + lut1v; rb2b = (rb2b << 2) + lut1v;      // the row already fetched: bonus times four, + 1
+        // the row already fetched, from the pointer phase's table: bonus times four, + 1
+        rb2 = row(lut_tagged, rp[-2]); rb2b = row(lut_tagged, rp[-1]);
     };
 
     int t = 1;
@@ -354,15 +380,17 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
     //    steps region 1 is past its last row in every lane (nothing reads what it would compute: lane 0 of region 2 takes
     //    lane 15's H of step T_end - LAG at step T_end - LAG + 1 and rows past R after that).  Those steps run without the
     //    idle region's column slots: 16 x 65 + up to 16 x 37 of a pass's ~53 k instructions.
-    for (const int tP = imin(LAG, imin(tB - 1, T_end)); t <= tP; t++) step_r1(t);
+    for (const int tP = imin(LAG, imin(tB - 1, T_end)); t <= tP; t++) step_r1();
     if (t > 1) {
 #pragma unroll
         for (int c = C1; c < CT; c++) G[c] = Z2;
         H2 = Z2; Hdiag2 = Z2;
-        const uint32_t w2 = ref16[t - LAG];
-        rb2 = lut(w2 & 0xffu); rb2b = lut(w2 >> 8);
+        rb2 = row(lut_plain, rp[-2]); rb2b = row(lut_plain, rp[-1]);
     }
-    for (; t < tB && t <= T_end; t++) step(t);
+    // (two steps per trip: the hand-over of the diagonal's registers from step to step is then a renaming)
+    const int tU = imin(tB - 1, T_end);
+    for (; t + 1 <= tU; t += 2) { step(); step(); }
+    if (t <= tU) { step(); t++; }
     const bool tagged = t <= T_end;
     if (tagged) enter_tagged();
     uint4 *qA = reinterpret_cast<uint4 *>(wsA) + gl;
@@ -385,23 +413,26 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
     int k = 0;
     // (two loops one behind the other, not one loop with a branch inside: the two kinds of step keep their registers
     //  differently, and a loop that holds both moves ~90 registers per block to reconcile them)
+    // (the eight steps are straight-line code: the stream offsets are immediates, the diagonal's registers are renamed)
     while (t + 7 <= T_end && t <= T_end - LAG) {
-        for (int s8 = 0; s8 < 8; s8++, t++) step_tagged(t);
+#pragma unroll
+        for (int s8 = 0; s8 < 8; s8++, t++) step_tagged();
         k += 8;
         lin_flush<NW, kGroup>(acc, qA, qB, [](uint32_t w) { return w; }, bd.store(0, t - 8, t - 1), bd.store(1, t - 8, t - 1));
         qA += QD * kWsRow;
         qB += QD * kWsRow;
     }
     while (t + 7 <= T_end) {
-        for (int s8 = 0; s8 < 8; s8++, t++) step_tagged_r2(t);
+#pragma unroll
+        for (int s8 = 0; s8 < 8; s8++, t++) step_tagged_r2();
         k += 8;
         lin_flush<NW, kGroup>(acc, qA, qB, [](uint32_t w) { return w; }, bd.store(0, t - 8, t - 1), bd.store(1, t - 8, t - 1));
         qA += QD * kWsRow;
         qB += QD * kWsRow;
     }
     // (what is left are the last seven steps at most: region 2 alone, unless the pointer phase began inside them)
-    for (; t <= T_end - LAG; t++, k++) step_tagged(t);
-    for (; t <= T_end; t++, k++) step_tagged_r2(t);
+    for (; t <= T_end - LAG; t++, k++) step_tagged();
+    for (; t <= T_end; t++, k++) step_tagged_r2();
     if (k & 7) {
         const int sh = 2 * (8 - (k & 7));
         lin_flush<NW, kGroup>(acc, qA, qB, [sh](uint32_t w) { return ((w & 0xffffu) << sh & 0xffffu) | ((w >> 16) << sh << 16); },
@@ -681,12 +712,22 @@ template <int C1, int C2> struct SplitLayoutLin : SplitLayout<C1, C2, true> {
     static constexpr int kWalkFmt = 3, kWalkQuads = LinWords<C2>::kUint4;
     static constexpr int kWalkSpan = GACT_WALK_SPAN;
     static constexpr bool kEndAligned = true;       // every tile's last row on the wave's last step
+    static constexpr int kLutWords = kLinLutWords;  // the kernel keeps lin_lut_fill's table and hands it over in PairTile::lut
+    using Base = SplitLayout<C1, C2, true>;
+    template <bool RAW>
+    __device__ static void load(const SeqSetDev &rs, const SeqSetDev &qf, const SeqSetDev &qr,
+                                const PairTile &pt, int gl, uint8_t *ref8, uint8_t *q8, uint32_t (&qb)[C1 + C2], uint32_t *stage)
+    {
+        static_assert(!RAW, "the linear-gap pass reads 2-bit sets");
+        load_pair_packed<C1 + C2, kGroup, typename Base::Cols, true, kLinPadRow>(rs, qf, qr, pt, gl, ref8, Base::G::kRefBytes, Base::G::kRow0, q8,
+                                                                                 Base::G::kTileMax, qb, stage, typename Base::Cols{});
+    }
     template <bool RAW>
     __device__ static uint32_t pass(const P16Consts &kc, int gl, const uint16_t *ref16, const uint32_t (&qb)[C1 + C2],
                                     int T_end, int tB, uint32_t *wsA, uint32_t *wsB, const PairTile &pt)
     {
         static_assert(!RAW, "the linear-gap pass reads 2-bit sets");
-        return dp_pass_lin_split<C1, C2>(kc, gl, ref16, qb, T_end, tB, wsA, wsB, pt.band, pt.full[0], pt.full[1]);
+        return dp_pass_lin_split<C1, C2>(kc, gl, ref16, qb, T_end, tB, wsA, wsB, pt.band, pt.full[0], pt.full[1], pt.lut);
     }
     // lane and half-word of pass()'s return value that hold H[R][Q] of slot h
     __device__ static int fin_lane(int Q) { (void)Q; return kGroup - 1; }

@@ -521,6 +521,10 @@ __device__ __forceinline__ void dp_pass_p16(const P16Consts &kc, const int gl,
 // Otherwise (2-bit sets, LUT form of dp_pass_p16): LDS bytes are 24 - 8 * code, a pad row is 31, a pad column
 // 0xFE; qb = v_perm selector {code of tile A, zero, 4 + code of tile B, zero}, a pad column selects the constant 0.
 constexpr uint32_t kLutPadRow = 31, kPermZero = 0x0c;
+// The split linear-gap pass (gact_lin.hpp) takes a row's look-up word out of a table in LDS whose byte offset IS the
+// stream byte: 24 - 8 * code as everywhere, and a pad row of its own -- the entry behind the four real ones.
+constexpr uint32_t kLinPadRow = 32;
+constexpr int kLinLutWords = 10;                 // {plain, pointer phase} x {code 3, 2, 1, 0, pad}
 struct PairTile {
     int R[kSlots], Q[kSlots], shift[kSlots];
     bool reverse[kSlots];
@@ -529,7 +533,27 @@ struct PairTile {
     int col_from;            // first DP column (1-based) a non-first tile's walk can reach, the smaller of the two tiles'
     int band;                // linear-gap passes: pointer words are stored within this many columns of the diagonal through (R, Q) ...
     bool full[kSlots];       // ... unless the tile stores its whole window (gact_lin.hpp LinBand; 0: every tile does)
+    const uint32_t *lut;     // split linear-gap pass: the block's table of look-up words (lin_lut_fill below)
 };
+
+// word 2 k: the row whose stream byte is 8 k on plain scores, dsub >> 8 k; word 2 k + 1: the same row in the pointer phase,
+// (dsub4 >> 8 k) + 0x01010101; k = 4, the pad row: 0 and 0x01010101 (gact_lin.hpp 8.).  Threads 0 .. 9 of the block write it;
+// the caller puts a barrier behind
+__device__ __forceinline__ void lin_lut_fill(uint32_t *lut, const P16Consts &kc, const int tid)
+{
+    if (tid < kLinLutWords) {
+        const uint32_t b = 8u * ((uint32_t)tid >> 1), base = (tid & 1) ? kc.dsub4 : kc.dsub;
+        lut[tid] = (b < kLinPadRow ? base >> b : 0u) + ((tid & 1) ? 0x01010101u : 0u);
+    }
+}
+// the block's table: a __shared__ array of its own for every kernel that asks (N = 0: the layout has no such pass)
+template <int N> struct LinLutLds {
+    __device__ __forceinline__ static uint32_t *get() { __shared__ __attribute__((aligned(8))) uint32_t words[N]; return words; }
+};
+template <> struct LinLutLds<0> { __device__ __forceinline__ static uint32_t *get() { return nullptr; } };
+
+template <class L, class = void> struct lin_lut_words { static constexpr int value = 0; };
+template <class L> struct lin_lut_words<L, std::void_t<decltype(L::kLutWords)>> { static constexpr int value = L::kLutWords; };
 
 template <int C, bool RAW, int LANES = kGroup>
 __device__ __forceinline__ void load_pair(const SeqSetDev &rs, const SeqSetDev &qfwd, const SeqSetDev &qrc,
@@ -644,7 +668,8 @@ __device__ __forceinline__ void cut_run(const uint32_t *seg_words, int bit0, int
 // COL::runs: the lane's slots as runs of consecutive DP columns -- first slot, slot count, and the column of the
 // run's first slot (which may be negative: pad columns left of the tile).
 // WRITE_Q8 = false: the caller's walker cuts its bases out of the staged words (gact_coop.hpp) and keeps no query bytes
-template <int CT, int LANES, class COL, bool WRITE_Q8 = true>
+// PAD_ROW: the stream byte of a row outside the tile
+template <int CT, int LANES, class COL, bool WRITE_Q8 = true, uint32_t PAD_ROW = kLutPadRow>
 __device__ __forceinline__ void load_pair_packed(const SeqSetDev &rs, const SeqSetDev &qfwd, const SeqSetDev &qrc,
                                                  const PairTile &pt, int gl, uint8_t *ref8, int ref_bytes, int row0,
                                                  uint8_t *q8, int q_stride, uint32_t (&qb)[CT], uint32_t *stage, COL)
@@ -653,7 +678,7 @@ __device__ __forceinline__ void load_pair_packed(const SeqSetDev &rs, const SeqS
     constexpr int kStageSeg = SG::kSeg;
     GACT_STAMP(l_a);
     uint32_t *ref32 = reinterpret_cast<uint32_t *>(ref8);
-    for (int k = gl; k < ref_bytes / 4; k += LANES) ref32[k] = kLutPadRow * 0x01010101u;
+    for (int k = gl; k < ref_bytes / 4; k += LANES) ref32[k] = PAD_ROW * 0x01010101u;
 #pragma unroll
     for (int seg = 0; seg < 4; seg++) {
         const int h = seg >> 1;
@@ -680,7 +705,7 @@ __device__ __forceinline__ void load_pair_packed(const SeqSetDev &rs, const SeqS
 #pragma unroll
         for (int s = 0; s < CT; s++) {
             const int d = gl * CT + s;
-            rrow[imin(d, R) * 2] = (uint8_t)(d < R ? 24u - rc[s] * 8u : kLutPadRow);
+            rrow[imin(d, R) * 2] = (uint8_t)(d < R ? 24u - rc[s] * 8u : PAD_ROW);
         }
         // ---- query: the walker's byte per column, and the slot's v_perm selector
         const uint32_t *qseg = stage + (2 * h + 1) * kStageSeg;
@@ -819,6 +844,12 @@ __global__ __launch_bounds__(kBlockThreads, L::kBlocksPerCu) void extend_p16_ker
     uint8_t *ref8 = lds + group_in_block * G::kGroupLds;
     uint8_t *q8 = ref8 + G::kRefBytes;
     const uint16_t *ref16_lane = reinterpret_cast<const uint16_t *>(ref8) + (L::kRow0 - 1 - w.gl);
+    // the split linear-gap pass's table of look-up words (gact_lin.hpp 8.)
+    uint32_t *const lin_lut = LinLutLds<lin_lut_words<L>::value>::get();
+    if constexpr (lin_lut_words<L>::value > 0) {
+        lin_lut_fill(lin_lut, kc, (int)threadIdx.x);
+        __syncthreads();
+    }
     // a wave owns 8 tile workspaces' worth of kp.ws_words, and its tiles' words are interleaved in it: row =
     // [tile A | tile B][the wave's 64 lanes] uint4 (kWsRow, gact_device.hpp), so a store instruction writes one KB
     constexpr int kWsPerTile = LANES / kGroup;
@@ -947,6 +978,7 @@ __global__ __launch_bounds__(kBlockThreads, L::kBlocksPerCu) void extend_p16_ker
         // the walk starts in column Q and stops after `early` query steps (align.cpp:205)
         pt.col_from = imax(imin(have[0] ? pt.Q[0] : 0x7fff, have[1] ? pt.Q[1] : 0x7fff) - kp.early, 0);
         pt.band = kp.band;
+        pt.lut = lin_lut;
         pt.shift[0] = have[0] ? (L::kEndAligned ? T_end - Tend_h[0] : imax(0, tB - tB_h[0])) : 0;
         pt.shift[1] = have[1] ? (L::kEndAligned ? T_end - Tend_h[1] : imax(0, tB - tB_h[1])) : 0;
 

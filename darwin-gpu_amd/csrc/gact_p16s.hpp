@@ -35,7 +35,9 @@ template <int C1, int C2> struct GeometrySplit {
     static constexpr int kMaxSteps = kTileMax + kGroup + kLag;
     static constexpr int kQuads = (C2 + 3) / 4;
     static constexpr int kRow0 = kGroup + kLag;                   // stream entry of (delay 0, row 1)
-    static constexpr int kRefEntries = kRow0 + kMaxSteps + kGroup + 8;
+    // (a lane reads entry kRow0 - 1 - lane + t + 1 at step t <= kMaxSteps, the loader writes up to entry kRow0 + shift + R
+    //  with shift + R <= kMaxSteps: kRow0 + kMaxSteps entries are in use, a row of lanes' worth is margin)
+    static constexpr int kRefEntries = kRow0 + kMaxSteps + kGroup;
     static constexpr int kRefBytes = kRefEntries * 2;
     static constexpr int kQueryBytes = kTileMax * kSlots;
     static constexpr int kGroupLds = (kRefBytes + kQueryBytes + 15) & ~15;

@@ -239,6 +239,8 @@ __global__ __launch_bounds__(kRoleThreads, 3) void extend_roles_kernel(
         (&done[0][0])[n].seq = 0;
     }
     if (threadIdx.x == 0) dp_finished = 0;
+    uint32_t *const lin_lut = LinLutLds<L::kLutWords>::get();      // the pass's table of look-up words (gact_lin.hpp 8.)
+    lin_lut_fill(lin_lut, kc, (int)threadIdx.x);
     __syncthreads();
 
     const int wave_in_block = threadIdx.x >> 6;
@@ -441,6 +443,7 @@ __global__ __launch_bounds__(kRoleThreads, 3) void extend_roles_kernel(
         const int tB = wave_min_groups<LANES>(imin(reach0, reach1));
         pt.col_from = imax(imin(have[0] ? pt.Q[0] : 0x7fff, have[1] ? pt.Q[1] : 0x7fff) - kp.early, 0);
         pt.band = kp.band;
+        pt.lut = lin_lut;
         pt.shift[0] = have[0] ? T_end - Tend_h[0] : 0;
         pt.shift[1] = have[1] ? T_end - Tend_h[1] : 0;
 
