@@ -71,6 +71,34 @@ __host__ inline bool p16_lin_ok(int tile, int match, int mismatch, int open, int
            4 * ((long long)match * (tile + 2) + (long long)(-ext) * steps + kLinFloor) + 3 <= 30000 && match - ext <= 63;
 }
 
+// 10. Builtins in place of inline assembly (round 7): a switch, off.  Between an inline-asm VALU instruction and a VALU
+//     instruction that reads its result the hazard recogniser puts an s_nop 0: it cannot see that the instruction has no
+//     dst-forwarding hazard.  With GACT_LIN_BUILTINS=1 the helpers of the linear-gap passes that still come out as the ONE
+//     instruction meant are builtins or vector expressions (v_pk_max_i16, v_bitop3_b32, v_pk_sub_i16, v_pk_ashrrev_i16;
+//     stages and scheduling barriers as they were): VALU counts are the same and the s_nop per step fall to a third.  Not
+//     v_pk_mad_u16 a, 4, c (a shift and an addition as a vector expression) and not v_pk_maximum3_f16 (three more VALU
+//     instructions per remainder step, one per seed step).  Off because the split kernel then spills two SGPRs more than
+//     with the inline-asm forms, whichever of the helpers is switched; what it does to the time: DESIGN 5, round 7.
+#ifndef GACT_LIN_BUILTINS
+#define GACT_LIN_BUILTINS 0
+#endif
+typedef short LinS2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t lin_max(uint32_t a, uint32_t b)        // pk_max (v_pk_max_i16)
+{
+#if GACT_LIN_BUILTINS
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(LinS2, a), __builtin_bit_cast(LinS2, b)));
+#else
+    return pk_max(a, b);
+#endif
+}
+__device__ __forceinline__ uint32_t lin_sub(uint32_t a, uint32_t b)        // pk_sub (v_pk_sub_i16)
+{
+#if GACT_LIN_BUILTINS
+    return __builtin_bit_cast(uint32_t, (LinS2)(__builtin_bit_cast(LinS2, a) - __builtin_bit_cast(LinS2, b)));
+#else
+    return pk_sub(a, b);
+#endif
+}
 __device__ __forceinline__ uint32_t pk_mad4v(uint32_t a, uint32_t v_c)     // a * 4 + c (wrapping halves), c in a VGPR
 {
     uint32_t r;
@@ -87,15 +115,23 @@ __device__ __forceinline__ uint32_t pk_max3f(uint32_t a, uint32_t b, uint32_t c)
 // (a & ~b) | c in one fast-class instruction (v_bitop3_b32, gfx950; truth table over a = 0xF0, b = 0xCC, c = 0xAA)
 __device__ __forceinline__ uint32_t andn_or(uint32_t a, uint32_t b, uint32_t c)
 {
+#if GACT_LIN_BUILTINS
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0xba);
+#else
     uint32_t r;
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xba" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
+#endif
 }
 __device__ __forceinline__ uint32_t pk_ashr2(uint32_t a)
 {
+#if GACT_LIN_BUILTINS
+    return __builtin_bit_cast(uint32_t, (LinS2)(__builtin_bit_cast(LinS2, a) >> (short)2));
+#else
     uint32_t r;
     asm("v_pk_ashrrev_i16 %0, 2, %1 op_sel_hi:[0,1]" : "=v"(r) : "v"(a));
     return r;
+#endif
 }
 
 // 8. Look-up words out of LDS (round 6).  A row's look-up word -- the one-hot byte table the v_perm of every column slot
@@ -106,6 +142,16 @@ __device__ __forceinline__ uint32_t pk_ashr2(uint32_t a)
 //    pair: a ds_read_u8 and a ds_read_b32 with an immediate table address per row and tile, no VALU instruction.
 //    word(b, plain) = dsub >> b, word(b, pointer phase) = (dsub4 >> b) + 0x01010101, the pad's 0 and 0x01010101.
 //    (lin_lut_fill and LinLutLds: gact_p16.hpp, beside the loader that writes the stream)
+
+// a selector of v_perm_b32 (a VOP3 instruction: no literal operand on gfx950) made where it is used.  As a plain constant
+// the compiler hoists its s_mov_b32 out of every loop, the kernel's outermost one included, and the register is then held
+// through the whole kernel: three of them cost the split kernel three more spilled SGPRs.
+__device__ __forceinline__ uint32_t sconst_here(uint32_t lit)
+{
+    uint32_t r;
+    asm volatile("s_mov_b32 %0, %1" : "=s"(r) : "i"(lit));
+    return r;
+}
 
 // Pointer words of this pass (walk_chain's FMT 3): two bits per cell, the op code alone.  A half-word holds eight
 // stored steps of one column (first step on top), a dword two adjacent columns (the even one low), a uint4 eight
@@ -126,6 +172,44 @@ __device__ __forceinline__ void lin_flush(const uint32_t (&acc)[2 * NW], uint4 *
     for (int n = 0; n < QD * 4; n++) {
         wa[n] = n < NW ? fix(__builtin_amdgcn_perm(acc[n < NW ? 2 * n + 1 : 0], acc[n < NW ? 2 * n : 0], 0x05040100u)) : 0u;
         wb[n] = n < NW ? fix(__builtin_amdgcn_perm(acc[n < NW ? 2 * n + 1 : 0], acc[n < NW ? 2 * n : 0], 0x07060302u)) : 0u;
+    }
+    if (storeA) {
+#pragma unroll
+        for (int q = 0; q < QD; q++) qA[q * kWsRow] = make_uint4(wa[4 * q], wa[4 * q + 1], wa[4 * q + 2], wa[4 * q + 3]);
+    }
+    if (storeB) {
+#pragma unroll
+        for (int q = 0; q < QD; q++) qB[q * kWsRow] = make_uint4(wb[4 * q], wb[4 * q + 1], wb[4 * q + 2], wb[4 * q + 3]);
+    }
+}
+
+// 9. Byte groups (round 7).  Inside a whole flush block of the split pass a step's place in the block is a compile-time
+//    fact, and filing a slot's 2-bit code -- a v_and_b32 and a v_pk_mad_u16 per slot and step -- is done for two columns
+//    at once: one v_perm_b32 gathers the low bytes of a pair's two H'' (kLinPairSel: column c tile A, column c + 1 tile A,
+//    column c tile B, column c + 1 tile B), one v_and_b32 cleans the four tags, and a byte takes four steps (first on top;
+//    it starts empty and is shifted three times by two bits, so it never reaches its neighbour).  A block keeps two such
+//    registers per pair, steps 0-3 and steps 4-7; the first step of each is a plain copy.  The flush builds LinWords'
+//    dwords from them with one v_perm_b32 per pair and tile.  The slot without a partner keeps its half-word.
+template <int S> struct LinPos { static constexpr int value = S; };       // a step's place in its block; kLinTail: in none
+constexpr int kLinTail = -1;
+constexpr uint32_t kLinPairSel = 0x06020400u;        // perm(H''[c + 1], H''[c], .)
+constexpr uint32_t kLinPairMask = 0x03030303u;
+constexpr uint32_t kLinFlushSelA = 0x05010400u;      // perm(steps 0-3, steps 4-7, .): {c + 1: 0-3, c + 1: 4-7, c: 0-3, c: 4-7} of tile A
+constexpr uint32_t kLinFlushSelB = 0x07030602u;      // the same of tile B
+// grp[2 p], grp[2 p + 1]: steps 0-3 and 4-7 of the pair of columns 2 p, 2 p + 1; odd: the half-words of column 2 NP (CW odd)
+template <int CW>
+__device__ __forceinline__ void lin_flush_groups(const uint32_t (&grp)[2 * (CW / 2)], const uint32_t odd, uint4 *qA, uint4 *qB,
+                                                 const bool storeA, const bool storeB)
+{
+    constexpr int NP = CW / 2, NW = LinWords<CW>::kWords, QD = LinWords<CW>::kUint4;
+    uint32_t wa[QD * 4], wb[QD * 4];
+    const uint32_t sA = sconst_here(kLinFlushSelA), sB = sconst_here(kLinFlushSelB);
+#pragma unroll
+    for (int n = 0; n < QD * 4; n++) {
+        wa[n] = n < NP ? __builtin_amdgcn_perm(grp[n < NP ? 2 * n : 0], grp[n < NP ? 2 * n + 1 : 0], sA)
+              : n < NW ? odd & 0xffffu : 0u;
+        wb[n] = n < NP ? __builtin_amdgcn_perm(grp[n < NP ? 2 * n : 0], grp[n < NP ? 2 * n + 1 : 0], sB)
+              : n < NW ? odd >> 16 : 0u;
     }
     if (storeA) {
 #pragma unroll
@@ -179,10 +263,13 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
     const uint32_t gv = vconst(kc.next), g4v = vconst(kc.next4), c3v = vconst(kc.c3), onev = vconst(kc.one),
                    dtv = vconst(kc.next4 + kc.tag1),               // 4|g| + 1: G'' (tagged 2) -> D'' tagged 1
                    c2v = vconst(kc.tag2);
+    const uint32_t psel = sconst_here(kLinPairSel);
     // zero level of the row a lane did "before step 1": region 1 is at row t - gl, region 2 at row t - gl - LAG
     uint32_t Z1 = pk2(lin_base(g) + gl * g), Z2 = pk2(lin_base(g) + (gl + LAG) * g);
     uint32_t G[CT];                         // H of the previous row (drifted)
-    uint32_t acc[2 * NW];                   // op codes of the last (up to) eight steps, one column each
+    uint32_t acc[2 * NW];                   // op codes of the last (up to) seven steps, one column each: the steps behind the last whole block
+    uint32_t grp[2 * (C2 / 2)], odd = 0;    // op codes of a whole block, two columns each (9. above); nothing reads them before the
+                                            // block's first step has written them
 #pragma unroll
     for (int c = 0; c < CT; c++) G[c] = c < C1 ? Z1 : Z2;                          // row 0: H = 0
 #pragma unroll
@@ -239,10 +326,10 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
                 U[c] = pk_max3f(U[c], c < C1 ? Z1 : Zr2, G[c]);
         } else {
 #pragma unroll
-            for (int c = 0; c < CT; c++) U[c] = pk_max(U[c], c < C1 ? Z1 : Zr2);     // :145-147
+            for (int c = 0; c < CT; c++) U[c] = lin_max(U[c], c < C1 ? Z1 : Zr2);     // :145-147
             GACT_SB();
 #pragma unroll
-            for (int c = 0; c < CT; c++) U[c] = pk_max(U[c], G[c]);              // the insertion, :149-154
+            for (int c = 0; c < CT; c++) U[c] = lin_max(U[c], G[c]);              // the insertion, :149-154
         }
         GACT_SB();
     };
@@ -263,12 +350,12 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         for (int c = 0; c < C1; c++) {                                           // :151-160 (no borrow)
             const uint32_t Da = Ha - gv, Db = Hb - gv;
             GACT_SB();
-            G[c] = pk_max(U[c], Da); G[C1 + c] = pk_max(U[C1 + c], Db);
+            G[c] = lin_max(U[c], Da); G[C1 + c] = lin_max(U[C1 + c], Db);
             GACT_SB();
             Ha = G[c]; Hb = G[C1 + c];
         }
 #pragma unroll
-        for (int c = 2 * C1; c < CT; c++) { G[c] = pk_max(U[c], Hb - gv); Hb = G[c]; }
+        for (int c = 2 * C1; c < CT; c++) { G[c] = lin_max(U[c], Hb - gv); Hb = G[c]; }
         H1 = Ha; H2 = Hb;
     };
     // a step in which region 2 is in front of its row 1 in every lane (see 7. below): region 1 alone, region 2's zero level
@@ -285,12 +372,12 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         ask_rows(true, false, false);
         GACT_SB();
 #pragma unroll
-        for (int c = 0; c < C1; c++) U[c] = GACT_LIN_MAX3 ? pk_max3f(U[c], Z1, G[c]) : pk_max(pk_max(U[c], Z1), G[c]);
+        for (int c = 0; c < C1; c++) U[c] = GACT_LIN_MAX3 ? pk_max3f(U[c], Z1, G[c]) : lin_max(lin_max(U[c], Z1), G[c]);
         GACT_SB();
         Hdiag1 = Hl1;
         uint32_t Ha = Hl1;
 #pragma unroll
-        for (int c = 0; c < C1; c++) { G[c] = pk_max(U[c], Ha - gv); Ha = G[c]; }
+        for (int c = 0; c < C1; c++) { G[c] = lin_max(U[c], Ha - gv); Ha = G[c]; }
         H1 = Ha;
     };
 
@@ -298,7 +385,18 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
     //      its tag 3 from the look-up word (+1), the left neighbour its tag 1 from the gap subtraction (4|g| + 1), and
     //      "low bits := 2" is one fast-class v_bitop3_b32
     uint32_t Z24 = 0;
-    auto step_tagged = [&]() {
+    // filing the codes.  A step of the remainder (kLinTail): slot c's code goes into acc[c], a v_and_b32 beside the v_bitop3 and a
+    // v_pk_mad_u16 beside the next slot's maximum.  Step S of a whole block: the pair's v_perm_b32 stands where the odd column's
+    // v_and_b32 stood, its v_and_b32 beside the next slot's subtraction, its v_pk_mad_u16 (none at S = 0 and S = 4) beside
+    // that slot's maximum; Hq: the even column's H'' until its partner's exists
+    static_assert(C2 >= 3 && (C2 & 1), "the last pair is filed while the unpaired slot is computed");
+    auto file_group = [&](const int S, const int c, const uint32_t x) {
+        uint32_t &r = grp[c - 2 + (S >> 2)];
+        r = (S & 3) ? pk_shl_add4(r, x) : x;
+    };
+    auto step_tagged = [&](auto pos) {
+        constexpr int S = decltype(pos)::value;
+        constexpr bool blk = S != kLinTail;
         ask_bytes(true, true);
         Z1 += gv; Z24 += g4v;
         const uint32_t Hl1 = (uint32_t)dpp_row_shr1((int)H1, (int)Z1);
@@ -308,29 +406,37 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         upper_all(U, true, Z24);
         Hdiag1 = Hl1; Hdiag2 = Hl2;
         uint32_t Ha = Hl1, Hb = Hl2;
-        uint32_t tprev = 0;
+        uint32_t tprev = 0, Hq = 0, x = 0;
 #pragma unroll
         for (int c = 0; c < C2; c++) {
             const bool both = c < C1;
+            const bool filed = blk && c >= 2 && !(c & 1);                        // the pair (c - 2, c - 1) is filed in this slot
             uint32_t Da = 0;
             const uint32_t Db = Hb - dtv;                                        // G'' tagged 2 -> D'' tagged 1
             if (both) Da = Ha - gv;
+            if (filed) x &= kLinPairMask;
             GACT_SB();
-            const uint32_t Hp = pk_max(U[C1 + c], Db);                           // the low bits: the op (:162-164)
-            if (both) { G[c] = pk_max(U[c], Da); Ha = G[c]; }
-            if (c > 0) acc[c - 1] = pk_shl_add4(acc[c - 1], tprev);
+            const uint32_t Hp = lin_max(U[C1 + c], Db);                           // the low bits: the op (:162-164)
+            if (both) { G[c] = lin_max(U[c], Da); Ha = G[c]; }
+            if (!blk && c > 0) acc[c - 1] = pk_shl_add4(acc[c - 1], tprev);
+            if (filed) file_group(S, c, x);
             GACT_SB();
             G[C1 + c] = andn_or(Hp, c3v, c2v);                                   // low bits := 2
-            tprev = Hp & c3v;
+            if (!blk || c == C2 - 1) tprev = Hp & c3v;
+            else if (c & 1) x = __builtin_amdgcn_perm(Hp, Hq, psel);
+            else Hq = Hp;
             GACT_SB();
             Hb = G[C1 + c];
         }
-        acc[C2 - 1] = pk_shl_add4(acc[C2 - 1], tprev);
+        if (!blk) acc[C2 - 1] = pk_shl_add4(acc[C2 - 1], tprev);
+        else odd = S ? pk_shl_add4(odd, tprev) : tprev;
         H1 = Ha; H2 = Hb;
     };
     // a step of the pointer phase in which region 1 is past its last row in every lane (see 7. below): region 2 alone; H1
     // stays what lane 15 left at step T_end - LAG
-    auto step_tagged_r2 = [&]() {
+    auto step_tagged_r2 = [&](auto pos) {
+        constexpr int S = decltype(pos)::value;
+        constexpr bool blk = S != kLinTail;
         ask_bytes(false, true);
         Z24 += g4v;
         const uint32_t Hl2 = (uint32_t)dpp_row_shr1((int)H2, dpp_row_ror1((int)pk_mad4v(H1, c2v)));
@@ -343,26 +449,35 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         ask_rows(false, true, true);
         GACT_SB();
 #pragma unroll
-        for (int c = 0; c < C2; c++) U[c] = GACT_LIN_MAX3 ? pk_max3f(U[c], Z24, G[C1 + c]) : pk_max(pk_max(U[c], Z24), G[C1 + c]);
+        for (int c = 0; c < C2; c++) U[c] = GACT_LIN_MAX3 ? pk_max3f(U[c], Z24, G[C1 + c]) : lin_max(lin_max(U[c], Z24), G[C1 + c]);
         GACT_SB();
         Hdiag2 = Hl2;
         uint32_t Hb = Hl2;
-        uint32_t tprev = 0;
+        uint32_t tprev = 0, Hq = 0, x = 0;
 #pragma unroll
         for (int c = 0; c < C2; c++) {
+            const bool filed = blk && c >= 2 && !(c & 1);
             const uint32_t Db = Hb - dtv;
+            if (filed) x &= kLinPairMask;
             GACT_SB();
-            const uint32_t Hp = pk_max(U[c], Db);
-            if (c > 0) acc[c - 1] = pk_shl_add4(acc[c - 1], tprev);
+            const uint32_t Hp = lin_max(U[c], Db);
+            if (!blk && c > 0) acc[c - 1] = pk_shl_add4(acc[c - 1], tprev);
+            if (filed) file_group(S, c, x);
             GACT_SB();
             G[C1 + c] = andn_or(Hp, c3v, c2v);
-            tprev = Hp & c3v;
+            if (!blk || c == C2 - 1) tprev = Hp & c3v;
+            else if (c & 1) x = __builtin_amdgcn_perm(Hp, Hq, psel);
+            else Hq = Hp;
             GACT_SB();
             Hb = G[C1 + c];
         }
-        acc[C2 - 1] = pk_shl_add4(acc[C2 - 1], tprev);
+        if (!blk) acc[C2 - 1] = pk_shl_add4(acc[C2 - 1], tprev);
+        else odd = S ? pk_shl_add4(odd, tprev) : tprev;
         H2 = Hb;
     };
+    // the eight steps of a whole block, each with its place
+#define GACT_LIN_BLOCK8(f) do { f(LinPos<0>{}); f(LinPos<1>{}); f(LinPos<2>{}); f(LinPos<3>{}); \
+                                f(LinPos<4>{}); f(LinPos<5>{}); f(LinPos<6>{}); f(LinPos<7>{}); } while (0)
 #undef GACT_SB
     auto enter_tagged = [&]() {
 #pragma unroll
@@ -414,32 +529,32 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
     // (two loops one behind the other, not one loop with a branch inside: the two kinds of step keep their registers
     //  differently, and a loop that holds both moves ~90 registers per block to reconcile them)
     // (the eight steps are straight-line code: the stream offsets are immediates, the diagonal's registers are renamed)
+    // (a whole block keeps its codes in the byte groups and leaves acc[] alone: zero, as the remainder's partial flush needs it)
     while (t + 7 <= T_end && t <= T_end - LAG) {
-#pragma unroll
-        for (int s8 = 0; s8 < 8; s8++, t++) step_tagged();
-        k += 8;
-        lin_flush<NW, kGroup>(acc, qA, qB, [](uint32_t w) { return w; }, bd.store(0, t - 8, t - 1), bd.store(1, t - 8, t - 1));
+        GACT_LIN_BLOCK8(step_tagged);
+        t += 8; k += 8;
+        lin_flush_groups<C2>(grp, odd, qA, qB, bd.store(0, t - 8, t - 1), bd.store(1, t - 8, t - 1));
         qA += QD * kWsRow;
         qB += QD * kWsRow;
     }
     while (t + 7 <= T_end) {
-#pragma unroll
-        for (int s8 = 0; s8 < 8; s8++, t++) step_tagged_r2();
-        k += 8;
-        lin_flush<NW, kGroup>(acc, qA, qB, [](uint32_t w) { return w; }, bd.store(0, t - 8, t - 1), bd.store(1, t - 8, t - 1));
+        GACT_LIN_BLOCK8(step_tagged_r2);
+        t += 8; k += 8;
+        lin_flush_groups<C2>(grp, odd, qA, qB, bd.store(0, t - 8, t - 1), bd.store(1, t - 8, t - 1));
         qA += QD * kWsRow;
         qB += QD * kWsRow;
     }
+#undef GACT_LIN_BLOCK8
     // (what is left are the last seven steps at most: region 2 alone, unless the pointer phase began inside them)
-    for (; t <= T_end - LAG; t++, k++) step_tagged();
-    for (; t <= T_end; t++, k++) step_tagged_r2();
+    for (; t <= T_end - LAG; t++, k++) step_tagged(LinPos<kLinTail>{});
+    for (; t <= T_end; t++, k++) step_tagged_r2(LinPos<kLinTail>{});
     if (k & 7) {
         const int sh = 2 * (8 - (k & 7));
         lin_flush<NW, kGroup>(acc, qA, qB, [sh](uint32_t w) { return ((w & 0xffffu) << sh & 0xffffu) | ((w >> 16) << sh << 16); },
                               bd.store(0, t - (k & 7), t - 1), bd.store(1, t - (k & 7), t - 1));
     }
     // H of the last column at the row of the last step, drift taken off
-    return tagged ? pk_ashr2(pk_sub(H2 | kc.c3, Z24)) : pk_sub(H2, Z2);
+    return tagged ? pk_ashr2(lin_sub(H2 | kc.c3, Z24)) : lin_sub(H2, Z2);
 }
 
 // ---------------------------------------------------------------------------
@@ -533,10 +648,10 @@ __device__ __forceinline__ uint32_t dp_pass_lin(const P16Consts &kc, const int g
             for (int c = 0; c < C; c++) U[c] = pk_max3f(U[c], Zr, G[c]);                       // :145-147 and the insertion, :149-154
         } else {
 #pragma unroll
-            for (int c = 0; c < C; c++) U[c] = pk_max(U[c], Zr);                               // :145-147
+            for (int c = 0; c < C; c++) U[c] = lin_max(U[c], Zr);                               // :145-147
             GACT_SB();
 #pragma unroll
-            for (int c = 0; c < C; c++) U[c] = pk_max(U[c], G[c]);                             // the insertion, :149-154
+            for (int c = 0; c < C; c++) U[c] = lin_max(U[c], G[c]);                             // the insertion, :149-154
         }
         GACT_SB();
     };
@@ -550,7 +665,7 @@ __device__ __forceinline__ uint32_t dp_pass_lin(const P16Consts &kc, const int g
         Hdiag = Hl0;
         uint32_t Hl = Hl0;
 #pragma unroll
-        for (int c = 0; c < C; c++) { G[c] = pk_max(U[c], Hl - gv); Hl = G[c]; }               // :151-160
+        for (int c = 0; c < C; c++) { G[c] = lin_max(U[c], Hl - gv); Hl = G[c]; }               // :151-160
         G_last = Hl;
         lutA = lut(w_next & 0xffu); lutB = lut(w_next >> 8);
     };
@@ -565,7 +680,7 @@ __device__ __forceinline__ uint32_t dp_pass_lin(const P16Consts &kc, const int g
             const uint32_t sidx = (uint32_t)(t - tB) & 7u, row0 = (uint32_t)(t - t_first);
             const uint32_t ka = row0 < (uint32_t)rows[0] ? sidx : ((uint32_t)kKeyBias & 0xffffu);
             const uint32_t kb = row0 < (uint32_t)rows[1] ? sidx : ((uint32_t)kKeyBias & 0xffffu);
-            key_c = pk_sub(ka | (kb << 16), Z8);
+            key_c = lin_sub(ka | (kb << 16), Z8);
         }
         const uint32_t Hl0 = shr1(G_last, Z4 - onev);       // j = 0 border: the zero level, tagged 2 like every G''
         uint32_t U[C];
@@ -576,10 +691,10 @@ __device__ __forceinline__ uint32_t dp_pass_lin(const P16Consts &kc, const int g
         for (int c = 0; c < C; c++) {
             const uint32_t Db = Hl - dtv;                                                       // G'' tagged 2 -> D'' tagged 1
             GACT_SB();
-            const uint32_t Hp = pk_max(U[c], Db);                                               // the low bits: the op (:162-164)
+            const uint32_t Hp = lin_max(U[c], Db);                                               // the low bits: the op (:162-164)
             if (c > 0) {
                 acc[c - 1] = pk_shl_add4(acc[c - 1], tprev);
-                if (AMAX) bk[c - 1] = pk_max(bk[c - 1], pk_mad_vvv(G[c - 1], kc.tag2, key_c)); // 2 G'' + (step & 7) - Z8
+                if (AMAX) bk[c - 1] = lin_max(bk[c - 1], pk_mad_vvv(G[c - 1], kc.tag2, key_c)); // 2 G'' + (step & 7) - Z8
             }
             GACT_SB();
             G[c] = andn_or(Hp, c3v, c2v);                                                       // low bits := 2
@@ -588,7 +703,7 @@ __device__ __forceinline__ uint32_t dp_pass_lin(const P16Consts &kc, const int g
             Hl = G[c];
         }
         acc[C - 1] = pk_shl_add4(acc[C - 1], tprev);
-        if (AMAX) bk[C - 1] = pk_max(bk[C - 1], pk_mad_vvv(G[C - 1], kc.tag2, key_c));
+        if (AMAX) bk[C - 1] = lin_max(bk[C - 1], pk_mad_vvv(G[C - 1], kc.tag2, key_c));
         G_last = Hl;
         lutA = lut4(w_next & 0xffu) + lut1v; lutB = lut4(w_next >> 8) + lut1v;
     };
@@ -611,9 +726,9 @@ __device__ __forceinline__ uint32_t dp_pass_lin(const P16Consts &kc, const int g
             const uint32_t v = pk_sign(x);
             x = pk_add(x, kc.one);
             const uint32_t key = pk_mad_m1(v, pk_add(bk[AMAX ? c : 0], kc.one));
-            const uint32_t keep = pk_sign(pk_sub(key, m));
+            const uint32_t keep = pk_sign(lin_sub(key, m));
             rel = pk_mad_m1(keep, rel);
-            m = pk_max(m, key);
+            m = lin_max(m, key);
             bk[AMAX ? c : 0] = 0xffffffffu;
         }
 #pragma unroll
@@ -676,7 +791,7 @@ __device__ __forceinline__ uint32_t dp_pass_lin(const P16Consts &kc, const int g
 #pragma unroll
     for (int c = 1; c < C; c++) { ga = (c == cqA) ? G[c] : ga; gb = (c == cqB) ? G[c] : gb; }
     const uint32_t pick = __builtin_amdgcn_perm(gb, ga, 0x07060100u);           // {tile B's half of gb, tile A's half of ga}
-    return tagged ? pk_ashr2(pk_sub(pick | kc.c3, Z4)) : pk_sub(pick, Z);
+    return tagged ? pk_ashr2(lin_sub(pick | kc.c3, Z4)) : lin_sub(pick, Z);
 }
 
 // The wide main launch of linear scorings: UniformLayout<10, 32>'s column map, the pass above, FMT 3 words
