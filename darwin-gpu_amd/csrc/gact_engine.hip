@@ -22,6 +22,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -264,6 +265,29 @@ struct Slot {
             p = nullptr; bytes = 0; ev0 = ev1 = nullptr;
         }
     } cover;
+    // gact_hip_pileup_add (gact_pileup.hpp): the events around this slot's adds; the counts are the engine's (Pileup)
+    hipEvent_t pile_ev0 = nullptr, pile_ev1 = nullptr;
+};
+
+// gact_hip_pileup_* (gact_pileup.hpp): the open window of GACT_SET_REF and its counts, one allocation of the engine's
+struct Pileup {
+    uint8_t *p = nullptr;                 // counts (32 per position) | consensus (1 per position) | read table | alignments per read | state
+    size_t bytes = 0;
+    bool open = false;
+    int32_t read_first = 0, n_reads = 0;
+    int64_t base = 0, positions = 0;      // the window's first base in the set's concatenation, its bases
+    size_t at_cons = 0, at_reads = 0, at_aln = 0, at_state = 0;       // where the parts of p begin
+    int64_t ref_epoch = -1;               // gact_hip_engine::ref_epoch at begin: the window describes that upload of GACT_SET_REF
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;      // around begin's and finish's own work
+    std::mutex mu;                        // the statistics: adds come from several threads
+    gact_pileup_stats stats{};
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        p = nullptr; bytes = 0; ev0 = ev1 = nullptr; open = false;
+    }
 };
 
 // device-side D-SOFT filter (dsoft_device.hpp)
@@ -460,6 +484,8 @@ struct gact_hip_engine {
     int64_t sets_epoch = 0;     // bumped by every upload / derive_revcomp: range checks of older sets are void
     DsoftState dsoft;
     std::mutex dsoft_mu;        // the filter's scratch is shared by all slots
+    int64_t ref_epoch = 0;      // bumped by every upload of GACT_SET_REF (an open pileup window describes one of them)
+    Pileup pileup;
 };
 
 namespace {
@@ -1418,6 +1444,8 @@ void gact_hip_destroy(gact_hip_engine *e)
         sl.summary.release();
         sl.select.release();
         sl.cover.release();
+        if (sl.pile_ev0) (void)hipEventDestroy(sl.pile_ev0);
+        if (sl.pile_ev1) (void)hipEventDestroy(sl.pile_ev1);
         if (sl.d_counter) (void)hipFree(sl.d_counter);
         if (sl.d_flags) (void)hipFree(sl.d_flags);
         if (sl.d_ws) (void)hipFree(sl.d_ws);
@@ -1456,6 +1484,7 @@ void gact_hip_destroy(gact_hip_engine *e)
     }
     e->cb.stats_pool.clear();
     for (auto &s : e->sets) s.release();
+    e->pileup.release();
     e->dsoft.release_index();
     e->dsoft.release_scratch();
     delete e;
@@ -1484,6 +1513,7 @@ int gact_hip_upload_seqs(gact_hip_engine *e, int which, const uint8_t *concat, c
     if (rc) return rc;
     e->sets_epoch++;
     if (which == GACT_SET_REF) {
+        e->ref_epoch++;
         // the filter's index (start bins, bin -> sequence map, positions) describes the set it was built from
         std::lock_guard<std::mutex> lk2(e->dsoft_mu);
         e->dsoft.built = false;
@@ -2123,6 +2153,62 @@ static int select_candidates(gact_hip_engine *e, int slot, int32_t n_sel, const 
     return 0;
 }
 
+// the path run's pop counter and events, made on the slot's first path run or pileup add
+static int path_bufs_init(Slot::PathBufs &pb, const char *who)
+{
+    if (!pb.d_counter && (hipMalloc((void **)&pb.d_counter, sizeof(int)) != hipSuccess || hipEventCreate(&pb.ev0) != hipSuccess ||
+                          hipEventCreate(&pb.ev1) != hipSuccess))
+        return fail(GACT_HIP_ENOMEM, "%s: device allocation failed", who);
+    return 0;
+}
+
+// where the chunk of a path run that starts at candidate `first` ends: as many candidates as the budget's column bytes hold,
+// at least one; bytes: their column bytes
+static int32_t path_chunk_end(const gact_hip_engine *e, const std::vector<int64_t> &cap, int32_t first, int32_t n_sel, int64_t &bytes)
+{
+    int32_t end = first;
+    bytes = 0;
+    while (end < n_sel && (end == first || bytes + cap[(size_t)end] <= e->path_budget)) bytes += cap[(size_t)end++];
+    return end;
+}
+
+// One chunk of a path run (gact_hip_candidates_paths, gact_hip_pileup_add): candidates [first, end) of the selection, as many
+// as the budget's column bytes hold (at least one), their tagged copies, column offsets and zeroed column counts on the
+// device, and path_kernel behind them on the slot's stream.  pb.d_counter is the caller's to have made.
+static int launch_path_chunk(gact_hip_engine *e, Slot &sl, const Selection &sn, int32_t first, int32_t n_sel, int same_file,
+                             const char *who, std::vector<int64_t> &col_off, int32_t &end, int64_t &bytes)
+{
+    Slot::PathBufs &pb = sl.path;
+    const std::vector<int64_t> &cap = sn.cap;
+    const int groups_per_block = (gact::kBlockThreads / 64) * gact::kGroupsPerWave;
+    end = path_chunk_end(e, cap, first, n_sel, bytes);
+    const int32_t n = end - first;
+    col_off.assign((size_t)n + 1, 0);
+    for (int32_t k = 0; k < n; k++) col_off[(size_t)k + 1] = col_off[(size_t)k] + cap[(size_t)(first + k)];
+    if (pb.cands.reserve((size_t)n) || pb.records.reserve((size_t)n) || pb.col_off.reserve((size_t)n + 1) ||
+        pb.op_off.reserve((size_t)n) || pb.n_cols.reserve(2 * (size_t)n) || pb.n_ops.reserve((size_t)n) ||
+        pb.cols.reserve((size_t)bytes + 64))
+        return fail(GACT_HIP_ENOMEM, "%s: device allocation failed (%d candidates, %lld column bytes)", who, n, (long long)bytes);
+    HIP_TRY(hipMemcpyAsync(pb.cands.p, sn.tagged.data() + first, (size_t)n * sizeof(gact_candidate), hipMemcpyHostToDevice, sl.stream));
+    HIP_TRY(hipMemcpyAsync(pb.col_off.p, col_off.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, sl.stream));
+    HIP_TRY(hipMemsetAsync(pb.n_cols.p, 0, 2 * (size_t)n * sizeof(int32_t), sl.stream));
+    HIP_TRY(hipMemsetAsync(pb.d_counter, 0, sizeof(int), sl.stream));
+    gact::ChainQueues q{};
+    q.pop_seed = pb.d_counter;
+    q.list_n = -1;
+    const gact::PathArgs pa{pb.cols.p, pb.col_off.p, pb.n_cols.p};
+    // (the slot's workspace is sized for grid_blocks blocks of the chain kernels)
+    const int blocks = std::max(1, std::min((n + groups_per_block - 1) / groups_per_block, e->grid_blocks));
+    if (e->C == 20)
+        hipLaunchKernelGGL((gact::path_kernel<20>), dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, sn.d_rs, sn.d_qf,
+                           sn.d_qr, pb.cands.p, n, gact::kCompInCand, same_file, pb.records.p, q, pa, sl.d_ws);
+    else
+        hipLaunchKernelGGL((gact::path_kernel<32>), dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, sn.d_rs, sn.d_qf,
+                           sn.d_qr, pb.cands.p, n, gact::kCompInCand, same_file, pb.records.p, q, pa, sl.d_ws);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // The path run (gact_path.hpp).  The host takes the selected candidates (its copy of an uploaded list, else the device
 // filter's list copied back), tags each with its strand (kCompInCand, as a merged run does), and cuts the selection into
 // chunks whose column buffers fit the budget; per chunk: path_kernel, the op count, the counts back, the scan on the host,
@@ -2144,50 +2230,20 @@ int gact_hip_candidates_paths(gact_hip_engine *e, int slot, int32_t n_sel, const
     if (n_sel == 0) return 0;                 // (nothing asked for: also on a slot without candidates, e.g. a feeder with no reads)
     Selection sn;
     if ((rc = select_candidates(e, slot, n_sel, sel, rc_from, "candidates_paths", sn))) return rc;
-    const std::vector<gact_candidate> &tagged = sn.tagged;
-    const std::vector<int64_t> &cap = sn.cap;
-    const gact::SeqSetDev &d_rs = sn.d_rs, &d_qf = sn.d_qf, &d_qr = sn.d_qr;
     Slot::PathBufs &pb = sl.path;
-    if (!pb.d_counter && (hipMalloc((void **)&pb.d_counter, sizeof(int)) != hipSuccess || hipEventCreate(&pb.ev0) != hipSuccess ||
-                          hipEventCreate(&pb.ev1) != hipSuccess))
-        return fail(GACT_HIP_ENOMEM, "candidates_paths: device allocation failed");
+    if ((rc = path_bufs_init(pb, "candidates_paths"))) return rc;
     pb.stats = gact_paths_stats{};
     pb.timed = false;
     HIP_TRY(hipEventRecord(pb.ev0, sl.stream));
-    const int groups_per_block = (gact::kBlockThreads / 64) * gact::kGroupsPerWave;
     int64_t total_ops = 0;
     bool room = ops != nullptr;
     std::vector<int64_t> col_off, op_off;
     std::vector<int32_t> n_cols, n_ops;
     for (int32_t first = 0; first < n_sel;) {
-        // ---- one chunk: as many candidates as the budget holds (at least one)
         int32_t end = first;
         int64_t bytes = 0;
-        while (end < n_sel && (end == first || bytes + cap[(size_t)end] <= e->path_budget)) bytes += cap[(size_t)end++];
+        if ((rc = launch_path_chunk(e, sl, sn, first, n_sel, same_file, "candidates_paths", col_off, end, bytes))) return rc;
         const int32_t n = end - first;
-        col_off.assign((size_t)n + 1, 0);
-        for (int32_t k = 0; k < n; k++) col_off[(size_t)k + 1] = col_off[(size_t)k] + cap[(size_t)(first + k)];
-        if (pb.cands.reserve((size_t)n) || pb.records.reserve((size_t)n) || pb.col_off.reserve((size_t)n + 1) ||
-            pb.op_off.reserve((size_t)n) || pb.n_cols.reserve(2 * (size_t)n) || pb.n_ops.reserve((size_t)n) ||
-            pb.cols.reserve((size_t)bytes + 64))
-            return fail(GACT_HIP_ENOMEM, "candidates_paths: device allocation failed (%d candidates, %lld column bytes)", n, (long long)bytes);
-        HIP_TRY(hipMemcpyAsync(pb.cands.p, tagged.data() + first, (size_t)n * sizeof(gact_candidate), hipMemcpyHostToDevice, sl.stream));
-        HIP_TRY(hipMemcpyAsync(pb.col_off.p, col_off.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, sl.stream));
-        HIP_TRY(hipMemsetAsync(pb.n_cols.p, 0, 2 * (size_t)n * sizeof(int32_t), sl.stream));
-        HIP_TRY(hipMemsetAsync(pb.d_counter, 0, sizeof(int), sl.stream));
-        gact::ChainQueues q{};
-        q.pop_seed = pb.d_counter;
-        q.list_n = -1;
-        const gact::PathArgs pa{pb.cols.p, pb.col_off.p, pb.n_cols.p};
-        // (the slot's workspace is sized for grid_blocks blocks of the chain kernels)
-        const int blocks = std::max(1, std::min((n + groups_per_block - 1) / groups_per_block, e->grid_blocks));
-        if (e->C == 20)
-            hipLaunchKernelGGL((gact::path_kernel<20>), dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, d_rs, d_qf, d_qr,
-                               pb.cands.p, n, gact::kCompInCand, same_file, pb.records.p, q, pa, sl.d_ws);
-        else
-            hipLaunchKernelGGL((gact::path_kernel<32>), dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, d_rs, d_qf, d_qr,
-                               pb.cands.p, n, gact::kCompInCand, same_file, pb.records.p, q, pa, sl.d_ws);
-        HIP_TRY(hipGetLastError());
         const int op_blocks = std::max(1, std::min((n + 3) / 4, 4096));
         hipLaunchKernelGGL(gact::path_ops_kernel<false>, dim3(op_blocks), dim3(256), 0, sl.stream, pb.cols.p, pb.col_off.p, pb.n_cols.p,
                            n, pb.n_ops.p, nullptr, nullptr);
@@ -2643,6 +2699,7 @@ int gact_hip_measure_valu_rate(gact_hip_engine *e, double *lane_ops_per_s)
 #include "gact_gather.hpp"       // gact_hip_comm_*: the RCCL gather of a sharded job
 #include "gact_select.hpp"       // gact_hip_select_overlaps: one overlap per class, behind every other kernel
 #include "gact_cover.hpp"        // gact_hip_read_coverage: per-read coverage of an overlap set, behind those
+#include "gact_pileup.hpp"       // gact_hip_pileup_*: per-base pileup and consensus from the alignments' columns
 
 #ifdef GACT_STAMPS
 // diagnostic build: per-wave (start, queues empty, end, iterations) of the last main launch

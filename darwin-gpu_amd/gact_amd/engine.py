@@ -14,7 +14,7 @@ _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.path.join(_PKG, "libgact_hip.so")
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in
            ("gact_engine.hip", "gact_kernels.hpp", "gact_device.hpp", "gact_chain.hpp", "gact_p16.hpp", "gact_p16s.hpp", "gact_lin.hpp",
-            "gact_aff.hpp", "gact_roles.hpp", "gact_coop.hpp", "gact_policy.hpp", "gact_big.hpp", "gact_gather.hpp", "gact_path.hpp", "gact_summary.hpp", "gact_select.hpp", "gact_cover.hpp",
+            "gact_aff.hpp", "gact_roles.hpp", "gact_coop.hpp", "gact_policy.hpp", "gact_big.hpp", "gact_gather.hpp", "gact_path.hpp", "gact_summary.hpp", "gact_select.hpp", "gact_cover.hpp", "gact_pileup.hpp",
             "dsoft_device.hpp", "dsoft_engine.hpp")] + \
           [os.path.join(_ROOT, "include", "gact_hip.h")]
 
@@ -37,6 +37,12 @@ assert SUMMARY_DTYPE.itemsize == 32
 COVER_DTYPE = np.dtype([(n, "<i4") for n in ("n_intervals", "max_depth", "covered", "well_covered", "span_begin", "span_end")] +
                        [("depth_sum", "<i8")])
 assert COVER_DTYPE.itemsize == 32
+# the kinds a position of a pileup counts (include/gact_hip.h GACT_PILEUP_*), and the per-read table of pileup_finish
+PILEUP_A, PILEUP_C, PILEUP_G, PILEUP_T, PILEUP_OTHER, PILEUP_DEL, PILEUP_INS, PILEUP_DEPTH = range(8)
+PILEUP_COL_DTYPE = np.dtype([("n", "<u4", (8,))])
+READ_PILEUP_DTYPE = np.dtype([(n, "<i4") for n in ("n_alignments", "max_depth", "called", "changed", "deleted", "ins_flagged")] +
+                             [("reserved", "<i4", (2,))])
+assert PILEUP_COL_DTYPE.itemsize == 32 and READ_PILEUP_DTYPE.itemsize == 32
 
 # alignment ops (include/gact_hip.h GACT_PATH_OP_*): BAM's CIGAR numbering; an op word is len << 4 | op
 OP_I, OP_D, OP_EQ, OP_X = 1, 2, 7, 8
@@ -118,6 +124,11 @@ _SELECT_MODES = {"exact": SELECT_EXACT, "pair": SELECT_PAIR}
 class CoverStats(C.Structure):
     _fields_ = [("device_ms", C.c_float), ("reads", C.c_int32), ("intervals", C.c_int64), ("positions", C.c_int64),
                 ("scratch_bytes", C.c_int64)]
+
+
+class PileupStats(C.Structure):
+    _fields_ = [("device_ms", C.c_float), ("adds", C.c_int32), ("chunks", C.c_int32), ("alignments", C.c_int64),
+                ("columns", C.c_int64), ("positions", C.c_int64), ("scratch_bytes", C.c_int64)]
 
 
 COVER_REF, COVER_QUERY, COVER_BOTH = 1, 2, 3
@@ -283,6 +294,15 @@ def load():
         L.gact_hip_last_cover_stats.restype = C.c_int
     except AttributeError:
         pass
+    try:
+        L.gact_hip_pileup_begin.argtypes = [vp, i32, i32]
+        L.gact_hip_pileup_add.argtypes = [vp, C.c_int, i32, vp, i32, C.c_int]
+        L.gact_hip_pileup_finish.argtypes = [vp, i32, vp, vp, vp]
+        L.gact_hip_last_pileup_stats.argtypes = [vp, C.POINTER(PileupStats)]
+        for name in ("pileup_begin", "pileup_add", "pileup_finish", "last_pileup_stats"):
+            getattr(L, "gact_hip_" + name).restype = C.c_int
+    except AttributeError:
+        pass
     try:                                    # (an older build loaded through GACT_HIP_LIB_PATH for an A/B run has none)
         L.gact_hip_comm_create.argtypes = [vp, i32, i32, C.c_char_p, i32, C.POINTER(vp)]
         L.gact_hip_comm_gather_lines.argtypes = [vp, C.c_int, i32, vp, vp, C.c_int64]
@@ -315,7 +335,8 @@ EXPORTS = ("gact_hip_create", "gact_hip_destroy", "gact_hip_last_error", "gact_h
            "gact_hip_comm_create", "gact_hip_comm_gather_lines", "gact_hip_comm_destroy", "gact_hip_options_describe", "gact_hip_plan_describe",
            "gact_hip_candidates_paths", "gact_hip_last_paths_stats", "gact_hip_candidates_summaries",
            "gact_hip_last_summaries_stats", "gact_hip_format_paf", "gact_hip_select_overlaps", "gact_hip_last_select_stats",
-           "gact_hip_read_coverage", "gact_hip_last_cover_stats")
+           "gact_hip_read_coverage", "gact_hip_last_cover_stats", "gact_hip_pileup_begin", "gact_hip_pileup_add",
+           "gact_hip_pileup_finish", "gact_hip_last_pileup_stats")
 
 
 def plan(count, flags=0, compute_units=256, tile_size=320, tile_overlap=120, scoring=(1, -1, -1, -1), threshold=35):
@@ -358,6 +379,8 @@ class Engine:
         self.h = C.c_void_p()
         self._registered = {}
         self._n_cands = {}                            # slot -> candidates it holds (select_overlaps' default n)
+        self._ref_offsets = np.zeros(1, dtype=np.int64)       # of SET_REF as uploaded (the pileup's window is made of its reads)
+        self._pileup = None                           # (n_reads, positions) of the open pileup window
         self._check(self.L.gact_hip_create(C.byref(self.p), C.byref(self.h)))
         self.tile_size = tile_size
         self.tile_overlap = tile_overlap
@@ -393,6 +416,8 @@ class Engine:
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         self._check(self.L.gact_hip_upload_seqs(self.h, which, concat.ctypes.data, offsets.ctypes.data,
                                                 len(offsets) - 1))
+        if which == SET_REF:
+            self._ref_offsets = offsets.copy()
 
     def derive_revcomp(self):
         """SET_QUERY_RC := reverse complement of SET_QUERY, on the device (darwin.cpp:110-147)"""
@@ -591,6 +616,49 @@ class Engine:
         st = CoverStats()
         self._check(self.L.gact_hip_last_cover_stats(self.h, slot, C.byref(st)))
         return {n: getattr(st, n) for n, _ in CoverStats._fields_}
+
+    def pileup_begin(self, read_first=0, n_reads=None):
+        """opens the pileup window: reads [read_first, read_first + n_reads) of SET_REF (n_reads None: to the set's end), counts
+        zeroed; a second call starts over, and one that is refused leaves no window open, an earlier one's neither
+        (include/gact_hip.h gact_hip_pileup_begin)"""
+        n_all = len(self._ref_offsets) - 1
+        if n_reads is None:
+            n_reads = max(n_all - int(read_first), 0)
+        self._pileup = None
+        self._check(self.L.gact_hip_pileup_begin(self.h, int(read_first), int(n_reads)))
+        offs = self._ref_offsets
+        self._pileup = (int(n_reads), int(offs[int(read_first) + int(n_reads)] - offs[int(read_first)]))
+
+    def pileup_add(self, sel=None, n=None, rc_from=0x7fffffff, same_file=True, slot=0):
+        """stacks the alignments of candidates `sel` of the slot's candidate array (sel None: the first n; index >= rc_from =>
+        reverse-complement strand: the selection of candidates_paths) on their target reads inside the window, on the device;
+        any number of calls, from several threads on different slots at once (gact_hip_pileup_add)"""
+        if sel is not None:
+            sel = np.ascontiguousarray(sel, dtype=np.int32)
+            n = len(sel)
+        self._check(self.L.gact_hip_pileup_add(self.h, slot, int(n or 0), sel.ctypes.data if sel is not None else None,
+                                               int(rc_from), int(same_file)))
+
+    def pileup_finish(self, min_depth=3, counts=True, consensus=True):
+        """-> (reads READ_PILEUP_DTYPE, counts uint32 [positions, 8] or None, consensus uint8 [positions] or None): the
+        window's positions read after read, a position's counts indexed by PILEUP_*; the counts stay, so more pileup_add
+        calls and another pileup_finish may follow (gact_hip_pileup_finish)"""
+        if self._pileup is None:                      # (the sizes of the three arrays are the window's)
+            raise GactHipError("gact_hip error -1: pileup_finish: no window is open (gact_hip_pileup_begin first)")
+        n_reads, n_pos = self._pileup
+        reads = np.zeros(n_reads, dtype=READ_PILEUP_DTYPE)
+        cnt = np.zeros((n_pos, 8), dtype=np.uint32) if counts else None
+        cons = np.zeros(n_pos, dtype=np.uint8) if consensus else None
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        self._check(self.L.gact_hip_pileup_finish(self.h, int(min_depth), ptr(cnt), ptr(cons), ptr(reads)))
+        return reads, cnt, cons
+
+    def last_pileup_stats(self):
+        """the pileup since pileup_begin: device ms of its adds and finishes (HIP events), adds, path-run chunks, alignments
+        counted, their columns, the window's positions, device bytes the window holds"""
+        st = PileupStats()
+        self._check(self.L.gact_hip_last_pileup_stats(self.h, C.byref(st)))
+        return {n: getattr(st, n) for n, _ in PileupStats._fields_}
 
     def register_output(self, out, slot=0):
         """page-locks a caller-owned record array that will be fetched into repeatedly (opt-in; it must outlive the

@@ -3,6 +3,7 @@
 //   darwin_hip <REF.fasta> <READS.fasta> CPU_THREADS [--params params.cfg]
 //              [--candidates FILE | --dump-candidates FILE [--dsoft-only]] [--device-dsoft]
 //              [--device D] [--shard R/W] [--recode] [--cigar] [--paf] [--unique exact|pair] [--coverage K]
+//              [--pileup K]
 //
 // Plays the part of reference darwin.cpp:451-646 for the GACT stage: owns the
 // globals gact.cpp reads, loads params.cfg and the two FASTA files, builds the
@@ -33,6 +34,11 @@
 // longest stretch that is covered K deep) and mean_depth, tab-separated.  Same file: both sides of every record over the
 // reads; different files: the ref side over the reference sequences.  With --paf the summaries go along, so the table is what
 // the .paf files' own columns give.  Every other output byte is as without the flag.
+// --pileup K (with --device-dsoft, not with --shard; K >= 1): the alignments of the records the feeders write (the emitted ones;
+// with --unique the selected ones) are stacked on their target sequences on the device -- gact_hip_pileup_begin over all of
+// them before the feeders start, one gact_hip_pileup_add per feeder behind its run, gact_hip_pileup_finish(K) after the join --
+// and darwin.cons.fa gets one record per reference sequence in id order: `>name called=<n> changed=<n> deleted=<n>
+// ins_flagged=<n>`, then the consensus bytes with every '-' left out, on one line.  Every other output byte is as without the flag.
 //
 // --device D: the GPU this process uses (the reference is single-device, cuda_host.cu:195).  --shard R/W: this
 // process is rank R of W -- it extends every W-th candidate (host filter) or the R-th contiguous range of reads
@@ -73,6 +79,7 @@ static bool want_cigar = false;                  // --cigar
 static bool want_paf = false;                    // --paf
 static int unique_mode = -1;                     // --unique: GACT_SELECT_EXACT / GACT_SELECT_PAIR, -1: every emitted record
 static int coverage_depth = 0;                   // --coverage K: min_depth of darwin.cover.tsv, 0: no table
+static int pileup_depth = 0;                     // --pileup K: min_depth of darwin.cons.fa, 0: no consensus
 // --coverage: the records every feeder wrote a line for, in its file's order, and with --paf their summaries
 static std::vector<std::vector<gact_overlap> > cover_records;
 static std::vector<std::vector<gact_path_summary> > cover_sums;
@@ -249,7 +256,7 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
     // room for every op at once: an alignment has no more ops than columns, and no more columns than the bases of its
     // record's two spans (its ops end at (ae, be) and start at (ab, bb) or inside those spans, include/gact_hip.h)
     size_t room = 1;
-    if (want_cigar || want_paf)
+    if (want_cigar || want_paf || pileup_depth)
         for (int32_t k = 0; k < n; k++)
             if (o[(size_t)k].emitted && keep[(size_t)k]) {
                 sel.push_back(k);
@@ -278,6 +285,9 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
               "gact_hip_candidates_summaries");
         fpaf.open(paf_name(cpu_id));
     }
+    // --pileup: the same records' alignments onto their target sequences, counted on the device (gact_hip_pileup_add)
+    if (pileup_depth)
+        check(gact_hip_pileup_add(e, s.slot, (int32_t)sel.size(), sel.data(), nf, same_file), "gact_hip_pileup_add");
     char line[1024];
     size_t next = 0;                              // (the emitted records in order: paths[next], sums[next] are this one's)
     for (int32_t at = 0; at < n; at++) {
@@ -347,6 +357,35 @@ static int write_coverage(gact_hip_engine *e)
         const gact_read_cover &c = cover[i];
         fprintf(f, "%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.3f\n", names[i][0].c_str(), lens[i], c.n_intervals, c.max_depth, c.covered,
                 c.well_covered, c.span_begin, c.span_end, lens[i] ? (double)c.depth_sum / lens[i] : 0.0);
+    }
+    fclose(f);
+    return 0;
+}
+
+// --pileup: the consensus of every reference sequence from the counts the feeders' adds left, then darwin.cons.fa
+static int write_consensus(gact_hip_engine *e)
+{
+    size_t positions = 0;
+    for (const std::string &r : reference_seqs) positions += r.size();
+    std::vector<uint8_t> cons(positions);
+    std::vector<gact_read_pileup> table(reference_seqs.size());
+    if (gact_hip_pileup_finish(e, pileup_depth, nullptr, cons.data(), table.data()) != 0) {
+        printf("\ngact_hip_pileup_finish failed: %s\n\n", gact_hip_last_error());
+        return 1;
+    }
+    FILE *f = fopen("darwin.cons.fa", "w");
+    if (!f) { fprintf(stderr, "--pileup: cannot write darwin.cons.fa\n"); return 1; }
+    size_t at = 0;
+    std::string seq;
+    for (size_t i = 0; i < reference_seqs.size(); i++) {
+        const gact_read_pileup &t = table[i];
+        fprintf(f, ">%s called=%d changed=%d deleted=%d ins_flagged=%d\n", reference_descrips[i][0].c_str(), t.called, t.changed,
+                t.deleted, t.ins_flagged);
+        seq.clear();
+        for (size_t k = 0; k < reference_seqs[i].size(); k++)
+            if (cons[at + k] != '-') seq += (char)cons[at + k];
+        at += reference_seqs[i].size();
+        fprintf(f, "%s\n", seq.c_str());
     }
     fclose(f);
     return 0;
@@ -517,7 +556,7 @@ int main(int argc, char *argv[])
     if (argc >= 3 && strcmp(argv[1], "--selftest") == 0) return selftest(argv[2]);
     if (argc < 4) {
         fprintf(stderr, "Usage: darwin_hip <REFERENCE>.fasta <READS>.fasta CPU_THREADS --candidates FILE "
-                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K]]\n");
+                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K]]\n");
         return 1;
     }
     std::string cand_path, dump_path, cfg_path = "params.cfg", gather_id;
@@ -543,6 +582,13 @@ int main(int argc, char *argv[])
             const long k = strtol(v, &end, 10);
             if (!*v || *end || k < 1 || k > 0x7fffffffL) { fprintf(stderr, "--coverage wants an integer >= 1, not '%s'\n", v); return 1; }
             coverage_depth = (int)k;
+        }
+        else if (!strcmp(argv[a], "--pileup")) {
+            const char *v = a + 1 < argc ? argv[++a] : "";
+            char *end = nullptr;
+            const long k = strtol(v, &end, 10);
+            if (!*v || *end || k < 1 || k > 0x7fffffffL) { fprintf(stderr, "--pileup wants an integer >= 1, not '%s'\n", v); return 1; }
+            pileup_depth = (int)k;
         }
         else if (!strcmp(argv[a], "--rccl-gather") && a + 1 < argc) gather_id = argv[++a];
         else if (!strcmp(argv[a], "--device") && a + 1 < argc) setenv("GACT_HIP_DEVICE", argv[++a], 1);   // read by GPU_init
@@ -574,6 +620,12 @@ int main(int argc, char *argv[])
         // the table is made from the records of one process's feeders: the host-filter mode keeps none (it writes through
         // GACT_Batch), and a rank of a sharded job holds part of every read's overlaps
         fprintf(stderr, "--coverage: only with --device-dsoft, and not with --shard\n");
+        return 1;
+    }
+    if (pileup_depth && (!device_dsoft || shard_given)) {
+        // the counts come from the alignments of one engine's candidate arrays, and a rank of a sharded job holds part of every
+        // sequence's overlaps: combining the ranks' counts is left to the caller
+        fprintf(stderr, "--pileup: only with --device-dsoft, and not with --shard\n");
         return 1;
     }
     std::map<std::string, double> cfg = parse_cfg(cfg_path);
@@ -632,6 +684,10 @@ int main(int argc, char *argv[])
         const bool dumping = !dump_path.empty() && dsoft_only;
         cover_records.resize((size_t)num_threads);
         cover_sums.resize((size_t)num_threads);
+        if (pileup_depth && !dumping && gact_hip_pileup_begin(e, 0, (int32_t)reference_seqs.size()) != 0) {
+            printf("\ngact_hip_pileup_begin failed: %s\n\n", gact_hip_last_error());
+            return 1;
+        }
         std::vector<std::thread> threads;
         t_stage = now();
         for (int i = 0; i < num_threads; i++) {
@@ -647,8 +703,9 @@ int main(int argc, char *argv[])
             printf("num_candidates: %zu\n", total);
         }
         const int cover_rc = coverage_depth && !dumping ? write_coverage(e) : 0;
+        const int cons_rc = pileup_depth && !dumping ? write_consensus(e) : 0;
         GPU_close(&s, num_threads);
-        return cover_rc;
+        return cover_rc ? cover_rc : cons_rc;
     }
 
     // per-thread candidate lists, contiguous read ranges like darwin.cpp:619-629

@@ -380,6 +380,77 @@ int gact_hip_read_coverage(gact_hip_engine *e, int slot, int32_t n, const gact_o
 typedef struct { float device_ms; int32_t reads; int64_t intervals, positions, scratch_bytes; } gact_cover_stats;
 int gact_hip_last_cover_stats(gact_hip_engine *e, int slot, gact_cover_stats *stats);
 
+/* Per-base pileup and consensus of the reads of GACT_SET_REF from the overlaps' alignments, counted on the device: every chosen
+ * candidate's alignment (the one gact_hip_candidates_paths returns as a CIGAR) is stacked on its target read, every position
+ * counts what the other reads say there, and the majority is the consensus.  The pileup belongs to the engine, not to a slot:
+ * a read's pileup needs the candidates of every batch of queries, so it accumulates over calls and over slots.
+ *   gact_hip_pileup_begin   opens a window, reads [read_first, read_first + n_reads) of GACT_SET_REF, and zeroes its counts (32
+ *                           bytes per position, one allocation of the engine's, grown on demand, released with the engine); a
+ *                           second begin starts over, and a begin that is refused leaves no window open, an earlier one's
+ *                           neither.  n_reads == 0 is allowed.  GACT_HIP_EINVAL: GACT_SET_REF not uploaded, a
+ *                           window outside it, tile_size > GACT_HIP_FAST_TILE (as gact_hip_candidates_paths, for its reason);
+ *                           GACT_HIP_ENOMEM: the allocation failed
+ *   gact_hip_pileup_add     sel, n_sel, rc_from, same_file: the selection of gact_hip_candidates_paths, with its conventions and
+ *                           refusals (sel == NULL: candidates [0, n_sel); n_sel == 0: nothing to do, also on a slot without
+ *                           candidates).  Candidates whose ref_id lies outside the window are dropped on the host; the rest run
+ *                           through the path run's chunks on the slot's stream (column buffers within GACT_HIP_PATH_BUDGET_MB),
+ *                           and in each chunk the pileup kernel consumes the columns behind the chain kernel.  No ops are made
+ *                           and nothing but 32 bytes of error state and counters comes back.  Synchronous on the slot's stream;
+ *                           any number of calls, also from several threads on different slots at once: the counts are integer
+ *                           atomic adds, so the result does not depend on order or interleaving.  A candidate whose record has
+ *                           emitted == 0, or that has no columns, adds nothing.  Without an open window, or after GACT_SET_REF
+ *                           was uploaded again: GACT_HIP_EINVAL.  GACT_HIP_ERANGE (none is expected: every index is checked on
+ *                           the device before it is used): an alignment of this add, or of an add running beside it on
+ *                           another slot, lay outside the window or outside its two reads; that alignment was left out, the
+ *                           add's other alignments are counted and the add is in the statistics, and the condition is reported
+ *                           once -- later adds answer for themselves.  A failure of the device or of an allocation part of the
+ *                           way leaves the earlier chunks' alignments counted: begin again.  The slot's records and its run, paths, summaries, select and
+ *                           cover statistics stay as they were
+ *   gact_hip_pileup_finish  makes the consensus and the per-read table for min_depth (>= 1) and copies back whichever of counts
+ *                           (the window's positions, read after read, no padding), consensus (one byte per position, same
+ *                           layout) and reads[n_reads] are not NULL.  The counts stay: finish may be called again (another
+ *                           min_depth) and be followed by more adds.  Not to be called while an add is running
+ * Column rules.  Every coordinate is in the record's strand, as ab .. be are: for comp == 1 the query bytes are
+ * GACT_SET_QUERY_RC's and nothing is complemented.  The alignment starts at target position ae - (ref-consuming columns) and
+ * query position be - (query-consuming columns): the spans gact_hip_format_paf prints, not ab / bb.  With target cursor r and
+ * query cursor q:
+ *   '=' / 'X'   n[kind of query byte q] += 1 (case folded; anything but acgtACGT is OTHER), n[DEPTH] += 1 at r; r++, q++
+ *   'D'         n[DEL] += 1, n[DEPTH] += 1 at r; r++
+ *   'I'         q++; the FIRST column of a run of 'I' adds 1 to n[INS] at min(r, len - 1): a run counts once whatever its length
+ *               (also across a tile boundary or the junction of the left and the right extension).  The inserted bases are not
+ *               kept: a caller who wants them takes the CIGAR
+ * Consensus byte of a position: its depth < min_depth: the read's own raw byte, unchanged.  Else the largest of A, C, G, T, DEL
+ * (OTHER never wins); ties go to the read's own base (case folded) if it is among the tied kinds, else in the order A, C, G, T,
+ * DEL; the byte is 'A' 'C' 'G' 'T' or '-'.  All five zero (every aligned query byte was OTHER): the read's own byte, which does
+ * not count as changed. */
+#define GACT_PILEUP_A 0      /* query base aligned here ('=' or 'X' column), case folded: a/A ... */
+#define GACT_PILEUP_C 1
+#define GACT_PILEUP_G 2
+#define GACT_PILEUP_T 3
+#define GACT_PILEUP_OTHER 4  /* ... any other query byte (N, ...) */
+#define GACT_PILEUP_DEL 5    /* a 'D' column: the alignment spans the position, no query base */
+#define GACT_PILEUP_INS 6    /* 'I' RUNS directly in front of this position */
+#define GACT_PILEUP_DEPTH 7  /* alignments whose columns consume this position = sum of 0..5 */
+typedef struct { uint32_t n[8]; } gact_pileup_col;          /* 32 bytes per position */
+typedef struct {
+    int32_t n_alignments;   /* alignments with at least one column, counted on this read */
+    int32_t max_depth;
+    int32_t called;         /* positions with depth >= min_depth */
+    int32_t changed;        /* called positions whose consensus byte is a base other than the read's own (case folded) */
+    int32_t deleted;        /* called positions whose consensus is '-' */
+    int32_t ins_flagged;    /* called positions with 2 * n[INS] > n[DEPTH] */
+    int32_t reserved[2];
+} gact_read_pileup;         /* 32 bytes */
+int gact_hip_pileup_begin (gact_hip_engine *e, int32_t read_first, int32_t n_reads);
+int gact_hip_pileup_add   (gact_hip_engine *e, int slot, int32_t n_sel, const int32_t *sel, int32_t rc_from, int same_file);
+int gact_hip_pileup_finish(gact_hip_engine *e, int32_t min_depth, gact_pileup_col *counts, uint8_t *consensus,
+                           gact_read_pileup *reads);
+/* The pileup since the last gact_hip_pileup_begin: HIP-event time of its adds and finishes together (each on its own stream,
+ * copies and kernels), the adds, the path-run chunks they made, the alignments counted (inside the window, emitted, with at
+ * least one column), their columns, the window's positions, and the device memory the window holds. */
+typedef struct { float device_ms; int32_t adds, chunks; int64_t alignments, columns, positions, scratch_bytes; } gact_pileup_stats;
+int gact_hip_last_pileup_stats(gact_hip_engine *e, gact_pileup_stats *stats);
+
 /* ------------------------------------------------------------------------
  * D-SOFT seed filter on the device (the stage in front of the path; optional:
  * the reference's host filter keeps working against the calls above).
