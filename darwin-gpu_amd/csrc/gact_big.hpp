@@ -209,7 +209,7 @@ __global__ __launch_bounds__(kBlockThreads) void big_tiles_kernel(
 
 // ---------------------------------------------------------------------------
 // gact_hip_candidates_run* for big tiles: one wave per candidate, the whole chain (the consumption of a tile is
-// extend_kernel's, gact_kernels.hpp, statement by statement)
+// chain_kernel's, gact_chain_kernel.hpp, statement by statement)
 template <int CB>
 __global__ __launch_bounds__(kBlockThreads) void big_extend_kernel(
     KParams kp, SeqSetDev refs, SeqSetDev qfwd, SeqSetDev qrc, const gact_candidate *__restrict__ cands, int first_cand, int n,

@@ -518,7 +518,7 @@ struct PathCursor {
 // storing them -- columns and runs (= CIGAR ops) of each kind.  Runs are counted where they start: a column whose op
 // differs from the op of the column emitted before it.  `prev` carries that op from tile to tile of a phase (0: there is
 // no column yet); `first` keeps the first op the left phase emitted -- that phase emits right to left, so it is the column
-// next to the junction, and the right phase starts with it as its `prev` (summary_kernel).
+// next to the junction, and the right phase starts with it as its `prev` (CountSink).
 struct PathCount {
     int prev, first;              // GACT_PATH_OP_*, 0 = none
     int n_eq, n_x, n_i, n_d;      // columns

@@ -31,6 +31,7 @@
 
 #include "gact_hip.h"
 #include "gact_kernels.hpp"
+#include "gact_chain_kernel.hpp"
 #include "gact_p16.hpp"
 #include "gact_p16s.hpp"
 #include "gact_lin.hpp"
@@ -940,8 +941,8 @@ int launch_extend(gact_hip_engine *e, Slot &sl, int first, int n, int rc_from, i
             case S::P16Raw: GACT_LAUNCH_SEED((gact::seed_p16_kernel<C, true>)); break;
             case S::P16: GACT_LAUNCH_SEED((gact::seed_p16_kernel<C, false>)); break;
             case S::Int32:
-                hipLaunchKernelGGL((gact::extend_kernel<C>), g, b256, 0, stream, kp, d_rs, d_qf, d_qr, sl.cands.p, first, n, rc_from, same_file,
-                                   sl.overlaps.p, q, e->p16 ? 1 : 0, ws);
+                hipLaunchKernelGGL((gact::chain_kernel<C, gact::SeedSink>), g, b256, 0, stream, kp, d_rs, d_qf, d_qr, sl.cands.p, n, rc_from,
+                                   same_file, sl.overlaps.p, q, gact::SeedSink{first, e->p16 ? 1 : 0}, ws);
                 break;
             default: break;
             }
@@ -1105,7 +1106,7 @@ int launch_extend(gact_hip_engine *e, Slot &sl, int first, int n, int rc_from, i
 template <int C> int occupancy_blocks(int *out)
 {
     int a = 0, b = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, gact::extend_kernel<C>, gact::kBlockThreads, 0));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, gact::chain_kernel<C, gact::SeedSink>, gact::kBlockThreads, 0));
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, gact::align_tiles_kernel<C>, gact::kBlockThreads, 0));
     int m = std::min(a, b);
     for (int v = 0; v < 14; v++) {
@@ -2172,15 +2173,35 @@ static int32_t path_chunk_end(const gact_hip_engine *e, const std::vector<int64_
     return end;
 }
 
+// One launch of chain_kernel for a second pass over a selection (the path run's chunks, the summary run): candidates
+// d_cands[0, n), tagged with their strands, popped through *d_counter (zeroed by the caller) into the sink.
+extern "C++" {                  // (a template: not in this file's extern "C")
+template <class Sink>
+static int launch_chain_kernel(gact_hip_engine *e, Slot &sl, const Selection &sn, const gact_candidate *d_cands, int n, int same_file,
+                               gact_overlap *d_records, int *d_counter, Sink sink)
+{
+    gact::ChainQueues q{};
+    q.pop_seed = d_counter;
+    q.list_n = -1;
+    const int groups_per_block = (gact::kBlockThreads / 64) * gact::kGroupsPerWave;
+    // (the slot's workspace is sized for grid_blocks blocks of the chain kernels)
+    const int blocks = std::max(1, std::min((n + groups_per_block - 1) / groups_per_block, e->grid_blocks));
+    auto k = e->C == 20 ? gact::chain_kernel<20, Sink> : gact::chain_kernel<32, Sink>;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, sn.d_rs, sn.d_qf, sn.d_qr, d_cands, n,
+                       gact::kCompInCand, same_file, d_records, q, sink, sl.d_ws);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+}
+
 // One chunk of a path run (gact_hip_candidates_paths, gact_hip_pileup_add): candidates [first, end) of the selection, as many
 // as the budget's column bytes hold (at least one), their tagged copies, column offsets and zeroed column counts on the
-// device, and path_kernel behind them on the slot's stream.  pb.d_counter is the caller's to have made.
+// device, and chain_kernel with a ColumnSink behind them on the slot's stream.  pb.d_counter is the caller's to have made.
 static int launch_path_chunk(gact_hip_engine *e, Slot &sl, const Selection &sn, int32_t first, int32_t n_sel, int same_file,
                              const char *who, std::vector<int64_t> &col_off, int32_t &end, int64_t &bytes)
 {
     Slot::PathBufs &pb = sl.path;
     const std::vector<int64_t> &cap = sn.cap;
-    const int groups_per_block = (gact::kBlockThreads / 64) * gact::kGroupsPerWave;
     end = path_chunk_end(e, cap, first, n_sel, bytes);
     const int32_t n = end - first;
     col_off.assign((size_t)n + 1, 0);
@@ -2193,25 +2214,13 @@ static int launch_path_chunk(gact_hip_engine *e, Slot &sl, const Selection &sn, 
     HIP_TRY(hipMemcpyAsync(pb.col_off.p, col_off.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(hipMemsetAsync(pb.n_cols.p, 0, 2 * (size_t)n * sizeof(int32_t), sl.stream));
     HIP_TRY(hipMemsetAsync(pb.d_counter, 0, sizeof(int), sl.stream));
-    gact::ChainQueues q{};
-    q.pop_seed = pb.d_counter;
-    q.list_n = -1;
-    const gact::PathArgs pa{pb.cols.p, pb.col_off.p, pb.n_cols.p};
-    // (the slot's workspace is sized for grid_blocks blocks of the chain kernels)
-    const int blocks = std::max(1, std::min((n + groups_per_block - 1) / groups_per_block, e->grid_blocks));
-    if (e->C == 20)
-        hipLaunchKernelGGL((gact::path_kernel<20>), dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, sn.d_rs, sn.d_qf,
-                           sn.d_qr, pb.cands.p, n, gact::kCompInCand, same_file, pb.records.p, q, pa, sl.d_ws);
-    else
-        hipLaunchKernelGGL((gact::path_kernel<32>), dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, sn.d_rs, sn.d_qf,
-                           sn.d_qr, pb.cands.p, n, gact::kCompInCand, same_file, pb.records.p, q, pa, sl.d_ws);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_chain_kernel(e, sl, sn, pb.cands.p, n, same_file, pb.records.p, pb.d_counter,
+                               gact::ColumnSink{{pb.cols.p, pb.col_off.p, pb.n_cols.p}});
 }
 
 // The path run (gact_path.hpp).  The host takes the selected candidates (its copy of an uploaded list, else the device
 // filter's list copied back), tags each with its strand (kCompInCand, as a merged run does), and cuts the selection into
-// chunks whose column buffers fit the budget; per chunk: path_kernel, the op count, the counts back, the scan on the host,
+// chunks whose column buffers fit the budget; per chunk: the chain kernel, the op count, the counts back, the scan on the host,
 // the op write, the ops back.
 int gact_hip_candidates_paths(gact_hip_engine *e, int slot, int32_t n_sel, const int32_t *sel, int32_t rc_from,
                               int same_file, gact_overlap *records, gact_path *paths,
@@ -2304,7 +2313,7 @@ int gact_hip_last_paths_stats(gact_hip_engine *e, int slot, gact_paths_stats *st
     return 0;
 }
 
-// The summary run (gact_summary.hpp): the same selection, one summary_kernel launch over all of it, records and summaries back.
+// The summary run (gact_summary.hpp): the same selection, one chain_kernel launch (CountSink) over all of it, records and summaries back.
 int gact_hip_candidates_summaries(gact_hip_engine *e, int slot, int32_t n_sel, const int32_t *sel, int32_t rc_from,
                                   int same_file, gact_overlap *records, gact_path_summary *sums)
 {
@@ -2346,19 +2355,7 @@ int gact_hip_candidates_summaries(gact_hip_engine *e, int slot, int32_t n_sel, c
     HIP_TRY(hipMemcpyAsync(d_cands, sn.tagged.data(), n * sizeof(gact_candidate), hipMemcpyHostToDevice, sl.stream));
     // (a chain with no tile over the threshold never walks: its summary stays zero; the counter starts at zero)
     HIP_TRY(hipMemsetAsync(d_sums, 0, n * sizeof(gact_path_summary) + 16, sl.stream));
-    gact::ChainQueues q{};
-    q.pop_seed = d_counter;
-    q.list_n = -1;
-    const int groups_per_block = (gact::kBlockThreads / 64) * gact::kGroupsPerWave;
-    // (the slot's workspace is sized for grid_blocks blocks of the chain kernels)
-    const int blocks = std::max(1, std::min((n_sel + groups_per_block - 1) / groups_per_block, e->grid_blocks));
-    if (e->C == 20)
-        hipLaunchKernelGGL((gact::summary_kernel<20>), dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, sn.d_rs, sn.d_qf,
-                           sn.d_qr, d_cands, n_sel, gact::kCompInCand, same_file, d_records, q, d_sums, sl.d_ws);
-    else
-        hipLaunchKernelGGL((gact::summary_kernel<32>), dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, sn.d_rs, sn.d_qf,
-                           sn.d_qr, d_cands, n_sel, gact::kCompInCand, same_file, d_records, q, d_sums, sl.d_ws);
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch_chain_kernel(e, sl, sn, d_cands, n_sel, same_file, d_records, d_counter, gact::CountSink{d_sums}))) return rc;
     HIP_TRY(hipMemcpyAsync(records, d_records, n * sizeof(gact_overlap), hipMemcpyDeviceToHost, sl.stream));
     HIP_TRY(hipMemcpyAsync(sums, d_sums, n * sizeof(gact_path_summary), hipMemcpyDeviceToHost, sl.stream));
     HIP_TRY(hipEventRecord(sb.ev1, sl.stream));

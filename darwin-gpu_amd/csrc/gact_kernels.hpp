@@ -1,9 +1,9 @@
-// gact_kernels.hpp -- the two __global__ entry points built on gact_device.hpp.
+// gact_kernels.hpp -- the __global__ entry points built on gact_device.hpp.
 //
 //   align_tiles_kernel      one AlignWithBT per group per iteration
 //                           (stands under Align_Batch_GPU, cuda_host.cu:23-190)
-//   extend_kernel           persistent: every group owns one candidate and
-//                           walks its whole tile chain (GACT, gact.cpp:48-228 /
+//   SeedSink                the int32 run of chain_kernel (gact_chain_kernel.hpp), persistent: every group owns one
+//                           candidate and walks its whole tile chain (GACT, gact.cpp:48-228 /
 //                           GACT_Batch, gact.cpp:231-560) without leaving the GPU
 #pragma once
 
@@ -128,114 +128,53 @@ __global__ __launch_bounds__(kBlockThreads, 3) void align_tiles_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Persistent chain kernel (int32 scores).  Per-group state mirrors the locals of
-// GACT() (gact_chain.hpp); every lane of the group carries an identical copy,
-// only the traceback runs on one lane and its results are broadcast.
+// What chain_kernel (gact_chain_kernel.hpp) hands to its sink's walk for walk_chain: workspace and walker scratch, the
+// start cell (R, Q) with its lane, column-in-lane and stored step, the LDS bytes of DP row 1 / column 1.
+struct TileWalk {
+    const uint32_t *ws;
+    uint32_t *scratch;
+    int R, Q, l0, c0, k0;
+    const uint8_t *rrow, *qrow;
+};
+
+// The int32 run's sink of chain_kernel, also the int32 seed launch's.
 //
 // seed_mode: walk every candidate only until its first tile has been consumed
 // (first_tile == false) or the chain is over, then hand the chain state to the
 // main launch (ChainQueues): the seed launch of the packed main kernel where the
 // packed arg-max keys do not fit (seed_p16_kernel otherwise).
-template <int C>
-__global__ __launch_bounds__(kBlockThreads, 3) void extend_kernel(
-    KParams kp, SeqSetDev refs, SeqSetDev qfwd, SeqSetDev qrc,
-    const gact_candidate *__restrict__ cands, int first_cand, int n,
-    int rc_from, int same_file,
-    gact_overlap *__restrict__ out, ChainQueues cq, int seed_mode,
-    uint32_t *__restrict__ ws_all)
-{
-    using G = Geometry<C>;
-    __shared__ uint8_t lds[(kBlockThreads / 64) * kGroupsPerWave * G::kGroupLds];
-    __shared__ __attribute__((aligned(16))) uint32_t tb_lds[(kBlockThreads / 64) * kGroupsPerWave][kTbScratchWords];
+struct SeedSink {
+    int first_cand, seed_mode;
 
-    const WaveCtx w = wave_ctx();
-    const int wave_in_block = threadIdx.x >> 6;
-    uint8_t *ref_lds_g = lds + (wave_in_block * kGroupsPerWave + w.g) * G::kGroupLds;
-    uint8_t *q_lds_g = ref_lds_g + G::kRefLds;
-    const uint8_t *ref_lds_lane = ref_lds_g + (kGroup - 1 - w.gl);
-    uint32_t *ws = ws_all + (size_t)w.slot * kp.ws_words;
-    const bool raw = refs.use_raw | qfwd.use_raw | qrc.use_raw;
-
-    ChainState s;
-    s.comp = 0; s.cand = -1; s.phase = 2;
-    bool exhausted = false;
-    __builtin_amdgcn_s_setprio(3);
-
-    for (;;) {
-        // ---- pick the next tile of this group, finishing / fetching candidates on the way
-        TilePick pk;
-        pk.have = false; pk.R = 0; pk.Q = 0; pk.reverse = false; pk.rp0 = 0; pk.qp0 = 0;
-        for (int guard = 0; guard < 3 && !pk.have; guard++) {
-            if (s.phase == 2) {
-                if (exhausted) break;
-                if (!seed_pop(s, cq, w.gl == 0, [](int v) { return __shfl(v, 0, kGroup); }, cands, first_cand, n, rc_from, refs, qfwd,
-                              qrc)) { exhausted = true; break; }
-            }
-            pk = chain_pick(s, kp, same_file, out, w.gl == 0);
-            if (!pk.have && seed_mode && w.gl == 0)
-                atomicAdd(cq.seed_cells, (unsigned long long)s.cells);     // finished inside the seed launch
-        }
-        if (!__any(pk.have)) {
-            // nobody in this wave has a tile: either all exhausted, or some group
-            // still has transitions pending (guard ran out) -- loop again for those
-            if (__all(exhausted && s.phase == 2)) break;
-            continue;
-        }
-        GroupTile gt{pk.R, pk.Q, pk.have ? s.first_tile : 0, 0};
-
-        const bool active = gt.R > 0 && gt.Q > 0;
-        const WavePlan wp = align_starts(last_step<C>(gt.R, gt.Q),
-                                         first_pointer_step<C>(gt.R, gt.Q, kp.early, gt.first), active, gt.shift);
-        uint32_t qb[C];
-        load_tile<C>(refs, s.comp ? qrc : qfwd, raw, pk.rp0, pk.qp0, gt.R, gt.Q, pk.reverse, w.gl, ref_lds_g,
-                     q_lds_g, qb, gt.shift);
-        wave_sync();
-        const bool any_first = __any(gt.first != 0);
-
-        PassOut po;
-        __builtin_amdgcn_s_setprio(0);          // throughput work; the serial sections around it run at priority 3
-        if (any_first) dp_pass<C, true>(kp, w.gl, ref_lds_lane, qb, gt, wp.T_end, wp.tB, ws, po);
-        else           dp_pass<C, false>(kp, w.gl, ref_lds_lane, qb, gt, wp.T_end, wp.tB, ws, po);
-        __builtin_amdgcn_s_setprio(3);
-        po.tB -= gt.shift;      // the traceback indexes steps in the tile's own (undelayed) time
-
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // see align_tiles_kernel
-
-        // ---- consume the tile exactly as gact.cpp:95-133 / :158-194 do
-        if (pk.have) {
-            s.n_tiles++;
-            s.cells += (int64_t)gt.R * gt.Q;
-            int i0 = gt.R, j0 = gt.Q;
-            bool stop = false;
-            if (s.first_tile) {
-                i0 = po.bi; j0 = po.bj;
-                stop = chain_first_tile(s, kp, gt.R, gt.Q, po.best, po.bi, po.bj);
-            }
-            int ref_steps = 0, query_steps = 0, nst = 0;
-            ScoreWalk wk;
-            wk.load(s);
-            if (!stop && w.gl == 0) {
-                const int l0 = (j0 - 1) / C;
-                walk_chain<C, 0>(ws, tb_lds[wave_in_block * kGroupsPerWave + w.g], i0, j0, l0, (j0 - 1) - l0 * C,
-                                 i0 + l0 - po.tB, kp.early, ref_lds_g + kGroup + gt.shift, 1, q_lds_g, s.phase, kp,
-                                 wk, ref_steps, query_steps, nst);
-            }
-            chain_advance(s, stop, wk, ref_steps, query_steps, nst, 0);
-            if (seed_mode && !s.first_tile) {
-                // first tile done: the rest of the chain belongs to the main launch
-                if (w.gl == 0) {
-                    cq.states[s.cand] = s;
-                    const int b = chain_bucket(s, kp);
-                    const int slot = atomicAdd(&cq.bucket_count[b], 1);
-                    cq.live[(size_t)b * cq.live_stride + slot] = s.cand;
-                    atomicAdd(cq.seed_cells, (unsigned long long)s.cells);
-                }
-                s.phase = 2;
-            }
-        }
-        wave_sync();
+    __device__ __forceinline__ int first() const { return first_cand; }
+    __device__ __forceinline__ void begin() const {}
+    __device__ __forceinline__ void picked(const ChainState &s, const ChainQueues &cq, bool have, bool leader) const
+    {
+        if (!have && seed_mode && leader)
+            atomicAdd(cq.seed_cells, (unsigned long long)s.cells);     // finished inside the seed launch
     }
-}
+    template <int C>
+    __device__ __forceinline__ void walk(const TileWalk &t, const ChainState &s, const KParams &kp, ScoreWalk &wk,
+                                         int &ref_steps, int &query_steps, int &nst) const
+    {
+        walk_chain<C, 0>(t.ws, t.scratch, t.R, t.Q, t.l0, t.c0, t.k0, kp.early, t.rrow, 1, t.qrow, s.phase, kp, wk,
+                         ref_steps, query_steps, nst);
+    }
+    __device__ __forceinline__ void advanced(ChainState &s, const ChainQueues &cq, const KParams &kp, bool leader) const
+    {
+        if (seed_mode && !s.first_tile) {
+            // first tile done: the rest of the chain belongs to the main launch
+            if (leader) {
+                cq.states[s.cand] = s;
+                const int b = chain_bucket(s, kp);
+                const int slot = atomicAdd(&cq.bucket_count[b], 1);
+                cq.live[(size_t)b * cq.live_stride + slot] = s.cand;
+                atomicAdd(cq.seed_cells, (unsigned long long)s.cells);
+            }
+            s.phase = 2;
+        }
+    }
+};
 
 // ---------------------------------------------------------------------------
 // 2-bit packer: 16 bases -> one word; flags[0] |= 1 when a byte is not A/C/G/T

@@ -1116,7 +1116,7 @@ __device__ __forceinline__ void dp_pass_aff_seed(const P16Consts &kc, const int 
 // ---------------------------------------------------------------------------
 // Packed seed launch: the first tile(s) of every candidate (arg-max, pointers of the
 // whole tile), two candidates per group, then the chain is handed to the main launch
-// (ChainQueues) exactly as the int32 seed launch does (extend_kernel, seed_mode).
+// (ChainQueues) exactly as the int32 seed launch does (SeedSink, seed_mode).
 // Needs p16_argmax_ok on top of p16_scoring_ok.  LIN: linear gap scoring on 2-bit sets (gact_lin.hpp).
 // MODE: 0 round 1's affine pass (any scoring that fits int16, raw bytes or 2-bit), 1 the linear-gap pass, 2 / 3 the drifted
 // affine pass (gact_aff.hpp; 3: mismatch < gap_extend) -- 1..3 on 2-bit sets only

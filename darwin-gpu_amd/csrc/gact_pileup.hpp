@@ -6,7 +6,7 @@
 // writes every selected candidate's alignment columns into device buffers (gact_path.hpp) right beside the read bytes they
 // refer to, so the counting is done there; the rules are stated in include/gact_hip.h.
 //
-//   pileup_kernel            behind path_kernel in every chunk of an add, one wave per candidate, 64 columns per step (the shape
+//   pileup_kernel            behind chain_kernel in every chunk of an add, one wave per candidate, 64 columns per step (the shape
 //                            of path_ops_kernel).  A first pass counts the ref-consuming and the query-consuming columns (two
 //                            ballots per step): the alignment starts at (ae - ref columns, be - query columns).  The second pass
 //                            gives each lane its target position r and query position q from the same two ballots under the lane
@@ -275,7 +275,7 @@ static int pileup_window(gact_hip_engine *e, const char *who)
 }
 
 // The selection of gact_hip_candidates_paths, less the candidates outside the window, through the path run's chunks:
-// path_kernel into the slot's column buffers, pileup_kernel behind it, the next chunk behind that on the same stream.
+// chain_kernel (ColumnSink) into the slot's column buffers, pileup_kernel behind it, the next chunk behind that on the same stream.
 int gact_hip_pileup_add(gact_hip_engine *e, int slot, int32_t n_sel, const int32_t *sel, int32_t rc_from, int same_file)
 {
     int rc = check_slot(e, slot);

@@ -1,7 +1,7 @@
 """GPU suite that holds the path run (gact_hip_candidates_paths) to the chain model at every configuration and edge: the
 CIGAR string, n_columns, n_ops and the record of every compared candidate equal tests/path_model.py's on the oracle's
 AlignWithBT, the records equal the normal run's byte for byte, and check_path holds with the model's left_aligned.  A
-sample of both strands of ecoli10x_small at both scorings and three tile geometries (path_kernel<20> and <32>), raw-byte
+sample of both strands of ecoli10x_small at both scorings and three tile geometries (chain_kernel<20, ColumnSink> and <32, ...>), raw-byte
 reads, the crafted candidates of tests/path_cases.py, one block walking everything, what a slot keeps between runs, and
 the device filter's own list.  No tolerance anywhere: integers, bytes and strings are equal or the test fails."""
 import numpy as np

@@ -2,7 +2,7 @@
 gact_hip_candidates_paths gives, field by field, and what the chain model gives (tests/path_model.py on the oracle's
 AlignWithBT); its records equal the normal run's byte for byte.  The crafted candidates plus the additions of
 tests/summary_cases.py (tests/test_summaries_model.py asserts which edges of the counting walk they reach), a shuffled
-sample of both strands at three tile geometries (summary_kernel<20> and <32>), raw-byte reads, one block walking everything,
+sample of both strands at three tile geometries (chain_kernel<20, CountSink> and <32, ...>), raw-byte reads, one block walking everything,
 independence from the path budget, what a slot keeps, the refusals, and the driver's --paf.  No tolerance anywhere."""
 import json
 import os
