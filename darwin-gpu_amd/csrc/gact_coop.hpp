@@ -205,7 +205,7 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
     uint32_t *const lin_lut = LinLutLds<L::kLutWords>::get();      // the pass's table of look-up words (gact_lin.hpp 8.)
     for (int n = threadIdx.x; n < kCoopJobs; n += kBlockThreads) jstate[n] = 0;
     if (threadIdx.x == 0) walk_lock = 0;
-    lin_lut_fill(lin_lut, kc, (int)threadIdx.x);
+    lin_lut_fill_for_pass<L>(lin_lut, kc, (int)threadIdx.x);
     __syncthreads();
 
     const int wave_in_block = threadIdx.x >> 6;

@@ -438,6 +438,7 @@ struct gact_hip_engine {
     bool split = false;         // ... in its split (two-region) layout: tile <= 320 and early <= 208
     bool tagged = false;        // the packed main launch runs its pointer phase on tagged scores (any layout)
     bool lin = false;           // linear gaps (open == extend == mismatch): the drifted pass of gact_lin.hpp on 2-bit sets
+    bool lin_row = false;       // ... and its split launches on the row-drifted pass: the scoring fails lin_col_drift_ok (gact_lin.hpp 12.)
     bool aff = false;           // any other scoring that fits: the drifted affine pass of gact_aff.hpp (split main launch, 2-bit sets)
     bool aff_seed = true;       // ... and its first-tile form in the seed launch (GACT_HIP_NO_AFF_SEED: round 1's packed seed pass)
     int wide = 0;               // wide (32 lanes per tile pair) main launch: 0 auto (few chains), 1 always, -1 never
@@ -889,13 +890,24 @@ int launch_extend(gact_hip_engine *e, Slot &sl, int first, int n, int rc_from, i
         }
         using gact::extend_p16_kernel;
         using RolesL = gact::SplitLayoutLin<7, 13>;
+        using RowL = gact::SplitLayoutLinRow<7, 13>;     // the same launches on the row-drifted pass (gact_lin.hpp 12.)
+        using RowTeamL = gact::SplitLayoutLinRowTeam<7, 13>;
+        const bool lin_row = e->lin_row;
         // a main launch of the plan's kernel: the same arguments whatever the kernel
         auto launch_main = [&](pol::MainK k, bool two_sets, int blocks, hipStream_t stream, const gact::ChainQueues &q, uint32_t *ws) -> int {
             using M = pol::MainK;
             const dim3 g((unsigned)blocks), b256(gact::kBlockThreads), brole(gact::kRoleThreads);
 #define GACT_LAUNCH_MAIN(KERNEL, BLOCK) hipLaunchKernelGGL(KERNEL, g, BLOCK, 0, stream, kp, e->kc, d_rs, d_qf, d_qr, same_file, sl.overlaps.p, q, ws)
             if constexpr (C == 20) {
-                switch (k) {
+                if (lin_row) switch (k) {
+                case M::RolesLin: if (two_sets) GACT_LAUNCH_MAIN((gact::extend_roles_kernel<RowL, true>), brole); else GACT_LAUNCH_MAIN((gact::extend_roles_kernel<RowL, false>), brole); break;
+                case M::CoopLin: if (two_sets) GACT_LAUNCH_MAIN((gact::extend_coop_kernel<RowL, true>), b256); else GACT_LAUNCH_MAIN((gact::extend_coop_kernel<RowL, false>), b256); break;
+                case M::SplitLin: if (two_sets) GACT_LAUNCH_MAIN((extend_p16_kernel<RowL, false, true>), b256); else GACT_LAUNCH_MAIN((extend_p16_kernel<RowL, false>), b256); break;
+                case M::SplitLinTeam: GACT_LAUNCH_MAIN((extend_p16_kernel<RowTeamL, false>), b256); break;
+                default: break;
+                }
+                const bool row_done = lin_row && (k == M::RolesLin || k == M::CoopLin || k == M::SplitLin || k == M::SplitLinTeam);
+                if (!row_done) switch (k) {
                 case M::RolesLin: if (two_sets) GACT_LAUNCH_MAIN((gact::extend_roles_kernel<RolesL, true>), brole); else GACT_LAUNCH_MAIN((gact::extend_roles_kernel<RolesL, false>), brole); break;
                 case M::CoopLin: if (two_sets) GACT_LAUNCH_MAIN((gact::extend_coop_kernel<RolesL, true>), b256); else GACT_LAUNCH_MAIN((gact::extend_coop_kernel<RolesL, false>), b256); break;
                 case M::SplitLin: if (two_sets) GACT_LAUNCH_MAIN((extend_p16_kernel<gact::SplitLayoutLin<7, 13>, false, true>), b256); else GACT_LAUNCH_MAIN((extend_p16_kernel<gact::SplitLayoutLin<7, 13>, false>), b256); break;
@@ -1137,10 +1149,15 @@ int lin_occupancy_blocks(int *out)
     int a = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, gact::extend_p16_kernel<gact::SplitLayoutLin<7, 13>, false>,
                                                          gact::kBlockThreads, 0));
-    int b = a;
+    int b = a, c = a, d = a;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, gact::extend_p16_kernel<gact::SplitLayoutLinTeam<7, 13>, false>,
                                                          gact::kBlockThreads, 0));
-    *out = std::max(1, std::min(a, b));
+    // (the same launches on the row-drifted pass, gact_lin.hpp 12.: one grid serves whichever pass the scoring takes)
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c, gact::extend_p16_kernel<gact::SplitLayoutLinRow<7, 13>, false>,
+                                                         gact::kBlockThreads, 0));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d, gact::extend_p16_kernel<gact::SplitLayoutLinRowTeam<7, 13>, false>,
+                                                         gact::kBlockThreads, 0));
+    *out = std::max(1, std::min(std::min(a, b), std::min(c, d)));
     return 0;
 }
 
@@ -1238,6 +1255,7 @@ static bool derive_kernel_flags(gact_hip_engine *e)
                 opt_env("no_tagged") == nullptr;
     e->lin = e->tagged && gact::p16_lin_ok(p->tile_size, p->match, p->mismatch, p->gap_open, p->gap_extend) &&
              opt_env("no_lin") == nullptr;
+    e->lin_row = e->lin && !gact::lin_col_drift_ok(p->match, p->gap_extend);
     e->aff = e->tagged && e->split && !e->lin && gact::p16_aff_ok(p->tile_size, p->match, p->mismatch, p->gap_open, p->gap_extend) &&
              opt_env("no_aff") == nullptr;
     e->aff_seed = opt_env("no_aff_seed") == nullptr;
@@ -1372,13 +1390,16 @@ int gact_hip_create(const gact_hip_params *p, gact_hip_engine **out)
     e->role_grid_blocks = 0;
     if (e->lin && e->split && e->C == 20) {
         using RL = gact::SplitLayoutLin<7, 13>;
-        int rb = 0, rb2 = 0;
+        using RowL = gact::SplitLayoutLinRow<7, 13>;
+        int rb = 0, rb2 = 0, rb3 = 0, rb4 = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&rb, gact::extend_roles_kernel<RL, false>, gact::kRoleThreads, 0) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&rb2, gact::extend_roles_kernel<RL, true>, gact::kRoleThreads, 0) != hipSuccess) {
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&rb2, gact::extend_roles_kernel<RL, true>, gact::kRoleThreads, 0) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&rb3, gact::extend_roles_kernel<RowL, false>, gact::kRoleThreads, 0) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&rb4, gact::extend_roles_kernel<RowL, true>, gact::kRoleThreads, 0) != hipSuccess) {
             delete e;
             return fail(GACT_HIP_EDEVICE, "hipOccupancyMaxActiveBlocksPerMultiprocessor failed");
         }
-        e->role_grid_blocks = std::max(1, std::min(rb, rb2)) * e->prop.multiProcessorCount;
+        e->role_grid_blocks = std::max(1, std::min(std::min(rb, rb2), std::min(rb3, rb4))) * e->prop.multiProcessorCount;
         if (const char *v = opt_env("role_blocks")) e->role_grid_blocks = std::max(1, std::min(atoi(v), e->role_grid_blocks));
     }
     e->roles = e->roles && e->role_grid_blocks > 0;
@@ -2446,7 +2467,7 @@ int gact_hip_last_run_stats(gact_hip_engine *e, int slot, gact_hip_run_stats *st
         st->packed16 = rec->two_phase ? (rec->wide ? 3 : e->split ? 2 : 1) : 0;
         st->seed_packed16 = (rec->two_phase && e->seed16) ? 1 : 0;
         st->tagged_pointers = (rec->two_phase && e->tagged) ? 1 : 0;
-        st->linear_gap = (rec->two_phase && rec->lin) ? 1 : (rec->two_phase && rec->aff) ? 2 : 0;
+        st->linear_gap = (rec->two_phase && rec->lin) ? ((e->lin_row && !rec->wide) ? 3 : 1) : (rec->two_phase && rec->aff) ? 2 : 0;
         st->raw_candidates = rec->routed_raw;
         if (rec->two_phase) {
             HIP_TRY(hipEventElapsedTime(&st->seed_ms, rec->ev0, rec->ev_mid));
@@ -2477,7 +2498,7 @@ int gact_hip_last_run_stats(gact_hip_engine *e, int slot, gact_hip_run_stats *st
     st->packed16 = sl.two_phase ? (sl.wide ? 3 : e->split ? 2 : 1) : 0;
     st->seed_packed16 = (sl.two_phase && e->seed16) ? 1 : 0;
     st->tagged_pointers = (sl.two_phase && e->tagged) ? 1 : 0;
-    st->linear_gap = (sl.two_phase && sl.lin) ? 1 : (sl.two_phase && sl.aff) ? 2 : 0;
+    st->linear_gap = (sl.two_phase && sl.lin) ? ((e->lin_row && !sl.wide) ? 3 : 1) : (sl.two_phase && sl.aff) ? 2 : 0;
     st->raw_candidates = sl.routed_raw;
     if (sl.two_phase) {
         HIP_TRY(hipEventElapsedTime(&st->seed_ms, sl.ev0, sl.ev_mid));
@@ -2538,20 +2559,25 @@ int gact_hip_prepare(gact_hip_engine *e, int32_t expected_candidates)
             for (hipStream_t st : {sl.stream, sl.aux_stream}) {
                 hipLaunchKernelGGL((gact::seed_p16_kernel<20, false, 1>), dim3(1), dim3(gact::kBlockThreads), 0, st, e->kp, e->kc, d, d, d,
                                    sl.cands.p, 0, 0, 0, 0, sl.overlaps.p, q, sl.d_ws);
-                hipLaunchKernelGGL((gact::extend_p16_kernel<gact::SplitLayoutLin<7, 13>, false>), dim3(1), dim3(gact::kBlockThreads), 0, st, e->kp,
-                                   e->kc, d, d, d, 0, sl.overlaps.p, q, sl.d_ws);
-                hipLaunchKernelGGL((gact::extend_p16_kernel<gact::SplitLayoutLin<7, 13>, false, true>), dim3(1), dim3(gact::kBlockThreads), 0, st,
-                                   e->kp, e->kc, d, d, d, 0, sl.overlaps.p, q2, sl.d_ws);
-                hipLaunchKernelGGL((gact::extend_coop_kernel<gact::SplitLayoutLin<7, 13>, false>), dim3(1), dim3(gact::kBlockThreads), 0, st,
-                                   e->kp, e->kc, d, d, d, 0, sl.overlaps.p, q, sl.d_ws);
-                hipLaunchKernelGGL((gact::extend_coop_kernel<gact::SplitLayoutLin<7, 13>, true>), dim3(1), dim3(gact::kBlockThreads), 0, st,
-                                   e->kp, e->kc, d, d, d, 0, sl.overlaps.p, q2, sl.d_ws);
-                if (e->role_grid_blocks > 0) {
-                    hipLaunchKernelGGL((gact::extend_roles_kernel<gact::SplitLayoutLin<7, 13>, false>), dim3(1), dim3(gact::kRoleThreads), 0, st,
-                                       e->kp, e->kc, d, d, d, 0, sl.overlaps.p, q, sl.d_ws);
-                    hipLaunchKernelGGL((gact::extend_roles_kernel<gact::SplitLayoutLin<7, 13>, true>), dim3(1), dim3(gact::kRoleThreads), 0, st,
+                // the kernels of the pass this engine's scoring takes (gact_lin.hpp 12.)
+                auto warm = [&](auto layout) {
+                    using WL = decltype(layout);
+                    hipLaunchKernelGGL((gact::extend_p16_kernel<WL, false>), dim3(1), dim3(gact::kBlockThreads), 0, st, e->kp,
+                                       e->kc, d, d, d, 0, sl.overlaps.p, q, sl.d_ws);
+                    hipLaunchKernelGGL((gact::extend_p16_kernel<WL, false, true>), dim3(1), dim3(gact::kBlockThreads), 0, st,
                                        e->kp, e->kc, d, d, d, 0, sl.overlaps.p, q2, sl.d_ws);
-                }
+                    hipLaunchKernelGGL((gact::extend_coop_kernel<WL, false>), dim3(1), dim3(gact::kBlockThreads), 0, st,
+                                       e->kp, e->kc, d, d, d, 0, sl.overlaps.p, q, sl.d_ws);
+                    hipLaunchKernelGGL((gact::extend_coop_kernel<WL, true>), dim3(1), dim3(gact::kBlockThreads), 0, st,
+                                       e->kp, e->kc, d, d, d, 0, sl.overlaps.p, q2, sl.d_ws);
+                    if (e->role_grid_blocks > 0) {
+                        hipLaunchKernelGGL((gact::extend_roles_kernel<WL, false>), dim3(1), dim3(gact::kRoleThreads), 0, st,
+                                           e->kp, e->kc, d, d, d, 0, sl.overlaps.p, q, sl.d_ws);
+                        hipLaunchKernelGGL((gact::extend_roles_kernel<WL, true>), dim3(1), dim3(gact::kRoleThreads), 0, st,
+                                           e->kp, e->kc, d, d, d, 0, sl.overlaps.p, q2, sl.d_ws);
+                    }
+                };
+                if (e->lin_row) warm(gact::SplitLayoutLinRow<7, 13>{}); else warm(gact::SplitLayoutLin<7, 13>{});
                 HIP_TRY(hipGetLastError());
             }
             HIP_TRY(hipStreamSynchronize(sl.stream));

@@ -10,13 +10,33 @@
 //    The same for D.  So one value per cell is carried,
 //      H[i][j] = max(M, 0, H[i-1][j] + g, H[i][j-1] + g),        M = H[i-1][j-1] + sub,
 //    and every H, every op and every arg-max is the reference's.
-// 2. Row drift.  Every value of DP row i is kept as X + beta_i with beta_i = -i * g (it grows by |g| per row):
-//    H[i-1][j] + g is then H'_up as it stands, the zero level is Z = beta_i, and M' = H'_diag + (sub - g) where
-//    sub - g is 0 for a mismatch (mismatch == g) and match - g otherwise: the non-negative byte the look-up word of
-//    dp_pass_p16 already holds.  Per cell pair: perm, add | max Z, max H'_up | sub, max = 6 instructions, one
-//    register of state per column slot.  The drift is tied to the step, not to the tile's row number (rows in
-//    front of row 1 are virtual and behave like row 0, gact_device.hpp), so two tiles with different start delays
-//    share it.
+// 2. Drifted frames.  A value is kept as X + (a frame that grows by |g| per row), so that H[i-1][j] + g is the upper
+//    neighbour as it stands.  The frame is tied to the step, not to the tile's row number (rows in front of row 1 are
+//    virtual and behave like row 0, gact_device.hpp), so two tiles with different start delays share it.
+//    a. Row drift (the uniform pass, dp_pass_lin: seed and wide launches).  Every value of DP row i is X + beta_i with
+//       beta_i = -i * g: the zero level is Z = beta_i, one register per lane moved by one v_add per step, and
+//       M' = H'_diag + (sub - g) where sub - g is 0 for a mismatch (mismatch == g) and match - g otherwise: the
+//       non-negative byte the look-up word of dp_pass_p16 already holds.  H_left + g costs a subtraction per column slot
+//       on the serial chain.  Per cell pair: perm, add | max3 (Z, H'_up) | sub, max = 5 instructions (5. below).
+//    b. Column drift (the split pass, dp_pass_lin_split_col, round 9; dp_pass_lin_split keeps the row drift for the
+//       scorings of 12. below).  The cell a lane computes at step t in column slot c
+//       is kept as X + Zw(t + c), Zw(k) = lin_base + k |g|: the frame grows along the columns of a lane too, so
+//       H_left + g is the left neighbour of the same lane AS IT STANDS -- the subtraction is gone, the serial chain of
+//       an untagged slot is one v_pk_max_i16 -- and the diagonal, two gaps below, gets its 2|g| from the look-up word
+//       (lin_lut_fill_col, gact_p16.hpp: |g| for a mismatch, match + 2|g| for a match).  The frame depends on the step
+//       and the slot only, not on the lane, the tile or the row: the zero level of (t, c) is ONE number for the wave.
+//       A window of them, W[k] = Zw(t - 1 + k) for k = 0 .. C2 + 1, serves region 1 (slot c: W[c + 1]), region 2 (the
+//       same) and the j = 0 border (W[0]: one gap below slot 0's level); the pointer phase keeps T[c] = 4 Zw(t + c) + 3
+//       for region 2.  They live in SGPRs, move by one s_add_u32 each per step (both half-words at once: every value is
+//       positive and far from a carry) and enter the cell as the scalar operand of the v_pk_maximum3_f16 that is there
+//       anyway.  A value that crosses a lane changes frames by a constant, folded into the DPP hand-over (11. below):
+//       (C1 - 1)|g| between lanes of region 1 and from lane 15's region 1 into lane 0's region 2 (scaled by four with
+//       the tag in the addend of the v_pk_mad_u16 of the pointer phase), (C2 - 1)|g| between lanes of region 2.  Slot
+//       0's diagonal is last step's hand-over value as before.  A pad row's words and a pad column's constant stay 0:
+//       both only ever lower a value that the zero level clamps.  Per cell pair: perm, add | max3 | max = 4
+//       instructions, 8 where pointers are made (the subtraction there is also the re-tag 2 -> 1 and became - 1).
+//       tests/test_lin_col_drift_model.py runs this at lane level against the plain recurrence and holds the value range
+//       and the byte rule (12.) over every scoring p16_lin_ok admits at every tile the layout runs.
 // 3. Op-only pointers.  Inside the traceback window the scores are times four and the two low bits say where a value
 //    came from -- M 3, H_up 2, H_left 1: the numbering of align.h:23, and the tie order of align.cpp:162-164 is the
 //    order of the tags:
@@ -34,7 +54,9 @@
 //    v_perm_b32, v_mad_*, DPP moves and anything with an SGPR operand every 3.2-3.4.  So the frame is shifted up
 //    (lin_base) until every value is a positive int16: the packed additions then cannot carry or borrow across the
 //    half-words and run as plain 32-bit v_add_u32 / v_sub_u32, the re-taggings are a subtraction each, and the
-//    constants sit in VGPRs.
+//    constants of fast-class instructions sit in VGPRs (vconst).  An instruction that is in the slow class anyway takes
+//    a wave-uniform operand out of an SGPR for nothing: the zero levels of the column-drifted split pass (2b.) are operands of its
+//    v_pk_maximum3_f16 and are kept and moved by the scalar unit, off the VALU and out of the VGPR file.
 #pragma once
 
 #include "gact_p16s.hpp"
@@ -82,14 +104,30 @@ __host__ inline bool p16_lin_ok(int tile, int match, int mismatch, int open, int
 #ifndef GACT_LIN_BUILTINS
 #define GACT_LIN_BUILTINS 0
 #endif
+// 12. Which split pass runs.  The column-drifted pass's look-up byte of the pointer phase is 4 (match + 2|g|) + 1 and must
+//     fit 255: match + 2|g| <= 63, where p16_lin_ok admits match + |g| <= 63.  At tile 320 every admitted scoring fits;
+//     SplitLayoutLin<7, 13> also runs smaller tiles, and at tile 64 (62, -1, -1, -1) is admitted and does not.  The guard is
+//     not narrowed and the plan does not change: the launch takes the same kernel on the row-drifted pass
+//     (SplitLayoutLinRow, dp_pass_lin_split) for a scoring that fails lin_col_drift_ok, the column-drifted one otherwise.
+//     The value range needs no rule of its own: the frame adds at most (C2 - 1)|g| to the row drift and lin_base, inside
+//     what p16_lin_ok allows at every tile (tests/test_lin_col_drift_model.py).
+//     Two things in how the column-drifted pass is written came from measuring it.  It takes the builtin
+//     forms of v_pk_max_i16 and v_bitop3_b32 (kLinSplitBuiltins): with the subtraction gone an untagged slot's chain is
+//     maximum after maximum, and after an inline-asm one the hazard recogniser puts an s_nop 0 in front of each; the other
+//     passes keep 10.'s switch, so the seed and wide kernels are as they were.  And in the pointer phase its zero levels move
+//     by an s_add_u32 the compiler cannot see through: written in C++ the compiler keeps every level as a loop-invariant base
+//     plus a running offset, twice the scalar registers, with lane-spill reads inside the pointer phase's block loops.  On
+//     plain scores the C++ form is the better one (opaque, the single step behind the two-step loop becomes a loop of its own).
+__host__ inline bool lin_col_drift_ok(int match, int ext) { return match - 2 * ext <= 63; }
+constexpr bool kLinSplitBuiltins = true;
 typedef short LinS2 __attribute__((ext_vector_type(2)));
+template <bool BUILTIN = GACT_LIN_BUILTINS>
 __device__ __forceinline__ uint32_t lin_max(uint32_t a, uint32_t b)        // pk_max (v_pk_max_i16)
 {
-#if GACT_LIN_BUILTINS
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(LinS2, a), __builtin_bit_cast(LinS2, b)));
-#else
-    return pk_max(a, b);
-#endif
+    if constexpr (BUILTIN)
+        return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(LinS2, a), __builtin_bit_cast(LinS2, b)));
+    else
+        return pk_max(a, b);
 }
 __device__ __forceinline__ uint32_t lin_sub(uint32_t a, uint32_t b)        // pk_sub (v_pk_sub_i16)
 {
@@ -112,16 +150,64 @@ __device__ __forceinline__ uint32_t pk_max3f(uint32_t a, uint32_t b, uint32_t c)
     asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
+// the same with the middle operand out of an SGPR (the instruction is in the slow class as it is: the scalar operand is free)
+__device__ __forceinline__ uint32_t pk_max3f_s(uint32_t a, uint32_t s_b, uint32_t c)
+{
+    uint32_t r;
+    asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(s_b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_max_sgpr(uint32_t a, uint32_t s_b)
+{
+    uint32_t r;
+    asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "s"(s_b));
+    return r;
+}
+// 11. Hand-overs of the column-drifted split pass (2b. above): a lane takes its left neighbour's last slot less a constant
+//     of the frame, the subtraction riding on the DPP move (v_sub_u32_dpp: a lane without a source keeps what the register
+//     held).  A DPP operand written by the VALU needs two wait states, and the compiler does not look into an asm
+//     statement: every statement keeps them itself, with the instructions that do not read across lanes where it can.
+#define GACT_DPP_SHR1 " row_shr:1 row_mask:0xf bank_mask:0xf"
+#define GACT_DPP_ROR1 " row_ror:1 row_mask:0xf bank_mask:0xf"
+// lane n: h[n - 1] - k, lane 0 of a row: s_old
+__device__ __forceinline__ uint32_t lin_hand_shr1(uint32_t h, uint32_t v_k, uint32_t s_old)
+{
+    uint32_t r;
+    asm("v_mov_b32 %0, %3\n\ts_nop 0\n\tv_sub_u32_dpp %0, %1, %2" GACT_DPP_SHR1 : "=&v"(r) : "v"(h), "v"(v_k), "s"(s_old));
+    return r;
+}
+// lane n: h2[n - 1] - k2, lane 0 of a row: h1[15] - k1
+__device__ __forceinline__ uint32_t lin_hand_ror1_shr1(uint32_t h1, uint32_t v_k1, uint32_t h2, uint32_t v_k2)
+{
+    uint32_t r;
+    asm("s_nop 1\n\tv_sub_u32_dpp %0, %1, %2" GACT_DPP_ROR1 "\n\tv_sub_u32_dpp %0, %3, %4" GACT_DPP_SHR1
+        : "=&v"(r) : "v"(h1), "v"(v_k1), "v"(h2), "v"(v_k2));
+    return r;
+}
+// what lane 0 of a row takes in the pointer phase: 4 h1[15] + c (scaled, frame constant and tag in c), in every lane
+__device__ __forceinline__ uint32_t lin_hand_scaled_ror1(uint32_t h1, uint32_t v_c)
+{
+    uint32_t r;
+    asm("v_pk_mad_u16 %0, %1, 4, %2 op_sel_hi:[1,0,1]\n\ts_nop 1\n\tv_mov_b32_dpp %0, %0" GACT_DPP_ROR1 : "=&v"(r) : "v"(h1), "v"(v_c));
+    return r;
+}
+// lane n: h2[n - 1] - k2, lane 0 of a row: keeps first
+__device__ __forceinline__ uint32_t lin_hand_shr1_over(uint32_t first, uint32_t h2, uint32_t v_k2)
+{
+    asm("s_nop 1\n\tv_sub_u32_dpp %0, %1, %2" GACT_DPP_SHR1 : "+v"(first) : "v"(h2), "v"(v_k2));
+    return first;
+}
 // (a & ~b) | c in one fast-class instruction (v_bitop3_b32, gfx950; truth table over a = 0xF0, b = 0xCC, c = 0xAA)
+template <bool BUILTIN = GACT_LIN_BUILTINS>
 __device__ __forceinline__ uint32_t andn_or(uint32_t a, uint32_t b, uint32_t c)
 {
-#if GACT_LIN_BUILTINS
-    return __builtin_amdgcn_bitop3_b32(a, b, c, 0xba);
-#else
-    uint32_t r;
-    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xba" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-#endif
+    if constexpr (BUILTIN)
+        return __builtin_amdgcn_bitop3_b32(a, b, c, 0xba);
+    else {
+        uint32_t r;
+        asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xba" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+        return r;
+    }
 }
 __device__ __forceinline__ uint32_t pk_ashr2(uint32_t a)
 {
@@ -558,6 +644,343 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
 }
 
 // ---------------------------------------------------------------------------
+// Split layout in the column-drifted frame (2b. above; which of the two runs: 12.): the same pass, same arguments.  Returns, in lane 15 of every group, H[R][Q] of both tiles
+// (packed, plain scores) -- valid when every tile's last row is the wave's last step (shift = T_end - Tend).
+template <int C1, int C2>
+__device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, const int gl,
+                                                      const uint16_t *__restrict__ ref16,
+                                                      const uint32_t (&qb)[C1 + C2],
+                                                      const int T_end, const int tB,
+                                                      uint32_t *__restrict__ wsA, uint32_t *__restrict__ wsB,
+                                                      const int band, const bool fullA, const bool fullB,
+                                                      const uint32_t *lut_lds)
+{
+    constexpr int CT = C1 + C2;
+    constexpr int NW = LinWords<C2>::kWords, QD = LinWords<C2>::kUint4;
+    constexpr int LAG = kGroup;
+    const int g = (int)(int16_t)(kc.ext & 0xffffu);
+    const uint32_t gs = kc.next, g4s = kc.next4;                       // |g|, 4|g|: what the windows move by per step
+    const uint32_t k1v = vconst((uint32_t)(C1 - 1) * kc.next),         // hand-over between lanes of region 1: (C1 - 1)|g|
+                   k2v = vconst((uint32_t)(C2 - 1) * kc.next);         // ... of region 2
+    // the pointer phase's constants are made where it begins (enter_tagged): k2v's register is free by then
+    uint32_t c3v = 0, onev = 0, c2v = 0,
+             k24v = 0,                                                 // hand-over between lanes of region 2 on tagged scores
+             k12v = 0;   // region 1 into region 2, scaled: 4 (H - (C1 - 1)|g|) + 2
+    const uint32_t psel = sconst_here(kLinPairSel);
+    // the zero levels (2b. above).  During step t W[k] = Zw(t - 1 + k): W[0] the j = 0 border, W[c + 1] slot c of either
+    // region; in the pointer phase T[c] = 4 Zw(t + c) + 3 is region 2's.  Wave-uniform: SGPRs, moved by the scalar unit
+    constexpr int NWIN = C2 + 1;
+    uint32_t W[NWIN], T[C2];
+#pragma unroll
+    for (int k = 0; k < NWIN; k++) W[k] = pk2(lin_base(g) + (k - 1) * (-g));      // before step 1: Zw(k - 1)
+#pragma unroll
+    for (int c = 0; c < C2; c++) T[c] = 0;
+    // (an opaque addition in the pointer phase, a plain one on plain scores: 12. above)
+    auto bump = [](uint32_t &z, const uint32_t by) { asm("s_add_u32 %0, %0, %1" : "+s"(z) : "s"(by) : "scc"); };
+    auto advance = [&](const int nW, const bool tagged_too) {
+#pragma unroll
+        for (int k = 0; k < NWIN; k++) if (k < nW) { if (tagged_too) bump(W[k], gs); else W[k] += gs; }
+        if (tagged_too) {
+#pragma unroll
+            for (int c = 0; c < C2; c++) bump(T[c], g4s);
+        }
+    };
+    uint32_t G[CT];                         // H of the previous row (drifted)
+    uint32_t acc[2 * NW];                   // op codes of the last (up to) seven steps, one column each: the steps behind the last whole block
+    uint32_t grp[2 * (C2 / 2)], odd = 0;    // op codes of a whole block, two columns each (9. above); nothing reads them before the
+                                            // block's first step has written them
+#pragma unroll
+    for (int c = 0; c < CT; c++) G[c] = W[(c < C1 ? c : c - C1) + 1];             // row 0: H = 0, in the frame of "step 0"
+#pragma unroll
+    for (int c = 0; c < 2 * NW; c++) acc[c] = 0;
+    // last slot of each region as the neighbour lane will see it; on the j = 0 border it is the zero level
+    uint32_t H1 = W[C1], H2 = W[C2];
+    uint32_t Hdiag1 = W[0], Hdiag2 = W[0];          // last step's hand-over value: one gap below the zero level of slot 0 then
+
+    // Look-up words (LinLut above): a row's byte in the ref stream IS the byte offset of its word in the table, so a row
+    // costs two LDS reads per tile and no VALU instruction.  rp: this lane's stream bytes of region 2's row at the step
+    // to come (tile A, tile B); region 1's are LAG entries further on.  Before step t: rb1 / rb1b = row t of region 1,
+    // rb2 / rb2b = row t - LAG of region 2.
+    typedef __attribute__((address_space(3))) const uint8_t LdsByte;
+    typedef __attribute__((address_space(3))) const uint32_t LdsWord;
+    LdsByte *const lut_plain = (LdsByte *)lut_lds, *const lut_tagged = (LdsByte *)(lut_lds + 1);
+    auto row = [](LdsByte *table, uint32_t stream_byte) { return *(LdsWord *)(table + stream_byte); };
+    LdsByte *rp = (LdsByte *)(ref16 + (1 - LAG));
+    uint32_t rb1 = row(lut_plain, rp[2 * LAG]), rb1b = row(lut_plain, rp[2 * LAG + 1]);
+    uint32_t rb2 = row(lut_plain, rp[0]), rb2b = row(lut_plain, rp[1]);
+    rp += 2;
+
+    // Instruction order.  With three waves on a SIMD a v_add / v_sub / v_and / v_or issues in 1.9 cycles when it does
+    // not wait for the instruction in front of it, in 3.0 when it does (issue_rate_probe.json, dependent streams).
+    // So the step is written in stages -- one kind of instruction for all column slots, then the next kind -- and the
+    // two regions' column chains (H_left -> D -> H, two dependent instructions per slot) run side by side; the
+    // scheduling barriers keep the compiler from folding the stages back into per-slot sequences.
+#define GACT_SB() __builtin_amdgcn_sched_barrier(0)
+    // the next step's rows: the stream bytes are asked for when the step begins, their look-up words once the v_perm stage
+    // has read the current ones (the bytes have had that stage's time to arrive, the words have the rest of the step)
+    uint32_t sb1 = 0, sb1b = 0, sb2 = 0, sb2b = 0;
+    auto ask_bytes = [&](const bool r1, const bool r2) {
+        if (r2) { sb2 = rp[0]; sb2b = rp[1]; }
+        if (r1) { sb1 = rp[2 * LAG]; sb1b = rp[2 * LAG + 1]; }
+        rp += 2;
+    };
+    auto ask_rows = [&](const bool r1, const bool r2, const bool tag2) {
+        if (r1) { rb1 = row(lut_plain, sb1); rb1b = row(lut_plain, sb1b); }
+        if (r2) { rb2 = row(tag2 ? lut_tagged : lut_plain, sb2); rb2b = row(tag2 ? lut_tagged : lut_plain, sb2b); }
+    };
+    auto upper_all = [&](uint32_t (&U)[CT], const bool tag2) {
+        uint32_t P[CT];
+#pragma unroll
+        for (int c = 0; c < CT; c++) P[c] = __builtin_amdgcn_perm(c < C1 ? rb1b : rb2b, c < C1 ? rb1 : rb2, qb[c]);
+        GACT_SB();
+#pragma unroll
+        for (int c = 0; c < CT; c++) U[c] = (c == 0 ? Hdiag1 : c == C1 ? Hdiag2 : G[c - 1]) + P[c];   // align.cpp:134-144
+        // (pointer phase: region 2's G is kept tagged 2, so it IS H_up'' as it stands; the look-up words of that phase
+        //  carry a +1, so M'' = G_diag'' + 4 (sub - g) + 1 comes out tagged 3 with no instruction of its own)
+        ask_rows(true, true, tag2);
+        GACT_SB();
+        if (GACT_LIN_MAX3) {
+#pragma unroll
+            for (int c = 0; c < CT; c++)                                         // :145-147 and the insertion, :149-154
+                U[c] = pk_max3f_s(U[c], c < C1 ? W[c + 1] : tag2 ? T[c - C1] : W[c - C1 + 1], G[c]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < CT; c++) U[c] = pk_max_sgpr(U[c], c < C1 ? W[c + 1] : tag2 ? T[c - C1] : W[c - C1 + 1]);     // :145-147
+            GACT_SB();
+#pragma unroll
+            for (int c = 0; c < CT; c++) U[c] = lin_max<kLinSplitBuiltins>(U[c], G[c]);              // the insertion, :149-154
+        }
+        GACT_SB();
+    };
+
+    auto step = [&]() {
+        ask_bytes(true, true);
+        advance(NWIN, false);
+        // lane 0 of region 1 sits on the j = 0 border: one gap below its zero level
+        const uint32_t Hl1 = lin_hand_shr1(H1, k1v, W[0]);
+        // lane 0 of region 2 continues lane 15's region 1 (one step ago = same row)
+        const uint32_t Hl2 = lin_hand_ror1_shr1(H1, k1v, H2, k2v);
+        uint32_t U[CT];
+        upper_all(U, false);
+        Hdiag1 = Hl1; Hdiag2 = Hl2;
+        uint32_t Ha = Hl1, Hb = Hl2;
+        static_assert(C2 >= C1, "region 2 is the longer chain");
+#pragma unroll
+        for (int c = 0; c < C1; c++) {                                           // :151-160: H_left + g is H_left as it stands
+            G[c] = lin_max<kLinSplitBuiltins>(U[c], Ha); G[C1 + c] = lin_max<kLinSplitBuiltins>(U[C1 + c], Hb);
+            GACT_SB();
+            Ha = G[c]; Hb = G[C1 + c];
+        }
+#pragma unroll
+        for (int c = 2 * C1; c < CT; c++) { G[c] = lin_max<kLinSplitBuiltins>(U[c], Hb); Hb = G[c]; }
+        H1 = Ha; H2 = Hb;
+    };
+    // a step in which region 2 is in front of its row 1 in every lane (see 7. below): region 1 alone, region 2's zero level
+    auto step_r1 = [&]() {
+        ask_bytes(true, false);
+        advance(C1 + 1, false);
+        const uint32_t Hl1 = lin_hand_shr1(H1, k1v, W[0]);
+        uint32_t P[C1], U[C1];
+#pragma unroll
+        for (int c = 0; c < C1; c++) P[c] = __builtin_amdgcn_perm(rb1b, rb1, qb[c]);
+        GACT_SB();
+#pragma unroll
+        for (int c = 0; c < C1; c++) U[c] = (c == 0 ? Hdiag1 : G[c - 1]) + P[c];
+        ask_rows(true, false, false);
+        GACT_SB();
+#pragma unroll
+        for (int c = 0; c < C1; c++) U[c] = GACT_LIN_MAX3 ? pk_max3f_s(U[c], W[c + 1], G[c]) : lin_max<kLinSplitBuiltins>(pk_max_sgpr(U[c], W[c + 1]), G[c]);
+        GACT_SB();
+        Hdiag1 = Hl1;
+        uint32_t Ha = Hl1;
+#pragma unroll
+        for (int c = 0; c < C1; c++) { G[c] = lin_max<kLinSplitBuiltins>(U[c], Ha); Ha = G[c]; }
+        H1 = Ha;
+    };
+
+    // ---- pointer phase: region 2 on tagged scores; G = 4H + 2 there: H_up'' without an instruction, the diagonal gets
+    //      its tag 3 from the look-up word (+1), the left neighbour its tag 1 from the gap subtraction (4|g| + 1), and
+    //      "low bits := 2" is one fast-class v_bitop3_b32
+    // filing the codes.  A step of the remainder (kLinTail): slot c's code goes into acc[c], a v_and_b32 beside the v_bitop3 and a
+    // v_pk_mad_u16 beside the next slot's maximum.  Step S of a whole block: the pair's v_perm_b32 stands where the odd column's
+    // v_and_b32 stood, its v_and_b32 beside the next slot's subtraction, its v_pk_mad_u16 (none at S = 0 and S = 4) beside
+    // that slot's maximum; Hq: the even column's H'' until its partner's exists
+    static_assert(C2 >= 3 && (C2 & 1), "the last pair is filed while the unpaired slot is computed");
+    auto file_group = [&](const int S, const int c, const uint32_t x) {
+        uint32_t &r = grp[c - 2 + (S >> 2)];
+        r = (S & 3) ? pk_shl_add4(r, x) : x;
+    };
+    auto step_tagged = [&](auto pos) {
+        constexpr int S = decltype(pos)::value;
+        constexpr bool blk = S != kLinTail;
+        ask_bytes(true, true);
+        advance(C1 + 1, true);
+        const uint32_t Hl1 = lin_hand_shr1(H1, k1v, W[0]);
+        // lane 15's region-1 column enters region 2 scaled and tagged 2
+        const uint32_t Hl2 = lin_hand_shr1_over(lin_hand_scaled_ror1(H1, k12v), H2, k24v);
+        uint32_t U[CT];
+        upper_all(U, true);
+        Hdiag1 = Hl1; Hdiag2 = Hl2;
+        uint32_t Ha = Hl1, Hb = Hl2;
+        uint32_t tprev = 0, Hq = 0, x = 0;
+#pragma unroll
+        for (int c = 0; c < C2; c++) {
+            const bool both = c < C1;
+            const bool filed = blk && c >= 2 && !(c & 1);                        // the pair (c - 2, c - 1) is filed in this slot
+            const uint32_t Db = Hb - onev;                                       // G'' tagged 2 -> D'' tagged 1
+            if (filed) x &= kLinPairMask;
+            GACT_SB();
+            const uint32_t Hp = lin_max<kLinSplitBuiltins>(U[C1 + c], Db);                           // the low bits: the op (:162-164)
+            if (both) { G[c] = lin_max<kLinSplitBuiltins>(U[c], Ha); Ha = G[c]; }
+            if (!blk && c > 0) acc[c - 1] = pk_shl_add4(acc[c - 1], tprev);
+            if (filed) file_group(S, c, x);
+            GACT_SB();
+            G[C1 + c] = andn_or<kLinSplitBuiltins>(Hp, c3v, c2v);                                   // low bits := 2
+            if (!blk || c == C2 - 1) tprev = Hp & c3v;
+            else if (c & 1) x = __builtin_amdgcn_perm(Hp, Hq, psel);
+            else Hq = Hp;
+            GACT_SB();
+            Hb = G[C1 + c];
+        }
+        if (!blk) acc[C2 - 1] = pk_shl_add4(acc[C2 - 1], tprev);
+        else odd = S ? pk_shl_add4(odd, tprev) : tprev;
+        H1 = Ha; H2 = Hb;
+    };
+    // a step of the pointer phase in which region 1 is past its last row in every lane (see 7. below): region 2 alone; H1
+    // stays what lane 15 left at step T_end - LAG
+    auto step_tagged_r2 = [&](auto pos) {
+        constexpr int S = decltype(pos)::value;
+        constexpr bool blk = S != kLinTail;
+        ask_bytes(false, true);
+        advance(0, true);
+        const uint32_t Hl2 = lin_hand_shr1_over(lin_hand_scaled_ror1(H1, k12v), H2, k24v);
+        uint32_t P[C2], U[C2];
+#pragma unroll
+        for (int c = 0; c < C2; c++) P[c] = __builtin_amdgcn_perm(rb2b, rb2, qb[C1 + c]);
+        GACT_SB();
+#pragma unroll
+        for (int c = 0; c < C2; c++) U[c] = (c == 0 ? Hdiag2 : G[C1 + c - 1]) + P[c];
+        ask_rows(false, true, true);
+        GACT_SB();
+#pragma unroll
+        for (int c = 0; c < C2; c++) U[c] = GACT_LIN_MAX3 ? pk_max3f_s(U[c], T[c], G[C1 + c]) : lin_max<kLinSplitBuiltins>(pk_max_sgpr(U[c], T[c]), G[C1 + c]);
+        GACT_SB();
+        Hdiag2 = Hl2;
+        uint32_t Hb = Hl2;
+        uint32_t tprev = 0, Hq = 0, x = 0;
+#pragma unroll
+        for (int c = 0; c < C2; c++) {
+            const bool filed = blk && c >= 2 && !(c & 1);
+            const uint32_t Db = Hb - onev;
+            if (filed) x &= kLinPairMask;
+            GACT_SB();
+            const uint32_t Hp = lin_max<kLinSplitBuiltins>(U[c], Db);
+            if (!blk && c > 0) acc[c - 1] = pk_shl_add4(acc[c - 1], tprev);
+            if (filed) file_group(S, c, x);
+            GACT_SB();
+            G[C1 + c] = andn_or<kLinSplitBuiltins>(Hp, c3v, c2v);
+            if (!blk || c == C2 - 1) tprev = Hp & c3v;
+            else if (c & 1) x = __builtin_amdgcn_perm(Hp, Hq, psel);
+            else Hq = Hp;
+            GACT_SB();
+            Hb = G[C1 + c];
+        }
+        if (!blk) acc[C2 - 1] = pk_shl_add4(acc[C2 - 1], tprev);
+        else odd = S ? pk_shl_add4(odd, tprev) : tprev;
+        H2 = Hb;
+    };
+    // the eight steps of a whole block, each with its place
+#define GACT_LIN_BLOCK8(f) do { f(LinPos<0>{}); f(LinPos<1>{}); f(LinPos<2>{}); f(LinPos<3>{}); \
+                                f(LinPos<4>{}); f(LinPos<5>{}); f(LinPos<6>{}); f(LinPos<7>{}); } while (0)
+#undef GACT_SB
+    auto enter_tagged = [&]() {
+        c3v = vconst(kc.c3); onev = vconst(kc.one); c2v = vconst(kc.tag2);
+        k24v = vconst((uint32_t)(C2 - 1) * kc.next4);
+        k12v = vconst(pk2(2 + 4 * (C1 - 1) * g));
+#pragma unroll
+        for (int c = C1; c < CT; c++) G[c] = pk_mad4v(G[c], c2v);
+        H2 = pk_mad4v(H2, c2v);
+        Hdiag2 = pk_mad4v(Hdiag2, c2v);
+#pragma unroll
+        for (int c = 0; c < C2; c++) T[c] = (W[c + 1] << 2) + kc.c3;   // the zero levels stay tagged 3 (H == 0 reads as MATCH, see 3.)
+        // the row already fetched, from the pointer phase's table: bonus times four, + 1
+        rb2 = row(lut_tagged, rp[-2]); rb2b = row(lut_tagged, rp[-1]);
+    };
+
+    int t = 1;
+    // 7. Region 2 runs LAG steps behind region 1 and every tile ends on the wave's last step: for the first LAG steps region 2
+    //    is in front of its row 1 in EVERY lane (its values are the zero level, whatever the reads hold), for the last LAG
+    //    steps region 1 is past its last row in every lane (nothing reads what it would compute: lane 0 of region 2 takes
+    //    lane 15's H of step T_end - LAG at step T_end - LAG + 1 and rows past R after that).  Those steps run without the
+    //    idle region's column slots: 16 x 65 + up to 16 x 37 of a pass's ~53 k instructions.
+    for (const int tP = imin(LAG, imin(tB - 1, T_end)); t <= tP; t++) step_r1();
+    if (t > 1) {
+        // region 2 starts at its zero level: what its slots "computed" at step t - 1, in that step's frame
+#pragma unroll
+        for (int k = C1 + 1; k < NWIN; k++) W[k] = W[k - 1] + gs;
+#pragma unroll
+        for (int c = C1; c < CT; c++) G[c] = W[c - C1 + 1];
+        H2 = W[C2]; Hdiag2 = W[0];
+        rb2 = row(lut_plain, rp[-2]); rb2b = row(lut_plain, rp[-1]);
+    }
+    // (two steps per trip: the hand-over of the diagonal's registers from step to step is then a renaming)
+    const int tU = imin(tB - 1, T_end);
+    for (; t + 1 <= tU; t += 2) { step(); step(); }
+    if (t <= tU) { step(); t++; }
+    const bool tagged = t <= T_end;
+    if (tagged) enter_tagged();
+    uint4 *qA = reinterpret_cast<uint4 *>(wsA) + gl;
+    uint4 *qB = reinterpret_cast<uint4 *>(wsB) + gl;
+    // region 2 is right-aligned: lane gl's columns are 13 (15 - gl) .. 13 (15 - gl) + 12 away from column Q in EVERY tile
+    // (quantum: lanes store in aligned groups of 1, 4 or 8 -- whole 64- or 128-byte pieces of a workspace row -- so that the
+    //  walker's loads never meet a partly written cache line; both ends of a lane's range grow with the lane)
+    LinBand bd;
+    {
+        const int q1 = (band >> 16) - 1, b = band & 0xffff;
+        const int u_lo = kGroup - 1 - (gl & ~q1), u_hi = kGroup - 1 - (gl | q1);
+        LinBand lo_, hi_;
+        lin_band_range(lo_, 0, T_end, u_lo, C2 * u_lo, C2 * u_lo + C2 - 1, b, fullA);
+        lin_band_range(hi_, 0, T_end, u_hi, C2 * u_hi, C2 * u_hi + C2 - 1, b, fullA);
+        bd.lo[0] = bd.lo[1] = lo_.lo[0]; bd.hi[0] = bd.hi[1] = hi_.hi[0];
+        bd.full[0] = fullA | (b <= 0); bd.full[1] = fullB | (b <= 0);
+    }
+    // whole blocks of eight steps, each followed by its flush (an `if ((k & 7) == 7)` inside one loop is
+    // if-converted by the compiler: the re-pairing v_perm of the flush would then run at every step)
+    int k = 0;
+    // (two loops one behind the other, not one loop with a branch inside: the two kinds of step keep their registers
+    //  differently, and a loop that holds both moves ~90 registers per block to reconcile them)
+    // (the eight steps are straight-line code: the stream offsets are immediates, the diagonal's registers are renamed)
+    // (a whole block keeps its codes in the byte groups and leaves acc[] alone: zero, as the remainder's partial flush needs it)
+    while (t + 7 <= T_end && t <= T_end - LAG) {
+        GACT_LIN_BLOCK8(step_tagged);
+        t += 8; k += 8;
+        lin_flush_groups<C2>(grp, odd, qA, qB, bd.store(0, t - 8, t - 1), bd.store(1, t - 8, t - 1));
+        qA += QD * kWsRow;
+        qB += QD * kWsRow;
+    }
+    while (t + 7 <= T_end) {
+        GACT_LIN_BLOCK8(step_tagged_r2);
+        t += 8; k += 8;
+        lin_flush_groups<C2>(grp, odd, qA, qB, bd.store(0, t - 8, t - 1), bd.store(1, t - 8, t - 1));
+        qA += QD * kWsRow;
+        qB += QD * kWsRow;
+    }
+#undef GACT_LIN_BLOCK8
+    // (what is left are the last seven steps at most: region 2 alone, unless the pointer phase began inside them)
+    for (; t <= T_end - LAG; t++, k++) step_tagged(LinPos<kLinTail>{});
+    for (; t <= T_end; t++, k++) step_tagged_r2(LinPos<kLinTail>{});
+    if (k & 7) {
+        const int sh = 2 * (8 - (k & 7));
+        lin_flush<NW, kGroup>(acc, qA, qB, [sh](uint32_t w) { return ((w & 0xffffu) << sh & 0xffffu) | ((w >> 16) << sh << 16); },
+                              bd.store(0, t - (k & 7), t - 1), bd.store(1, t - (k & 7), t - 1));
+    }
+    // H of the last column at the row of the last step, drift taken off
+    return tagged ? pk_ashr2(lin_sub(H2 | kc.c3, T[C2 - 1])) : lin_sub(H2, W[C2]);
+}
+#undef GACT_DPP_SHR1
+#undef GACT_DPP_ROR1
+
+// ---------------------------------------------------------------------------
 // Uniform layout (lane gl owns columns gl*C .. gl*C + C-1; 16 or 32 lanes per tile pair), every slot tagged in the
 // pointer phase.  Two users: the wide main launch (LANES = 32, few long chains) and, with AMAX, the seed launch
 // (first tiles: pointers from step 1 on, arg-max of align.cpp:173-177 as in dp_pass_p16 -- the key 8H + (step & 7)
@@ -827,7 +1250,8 @@ template <int C1, int C2> struct SplitLayoutLin : SplitLayout<C1, C2, true> {
     static constexpr int kWalkFmt = 3, kWalkQuads = LinWords<C2>::kUint4;
     static constexpr int kWalkSpan = GACT_WALK_SPAN;
     static constexpr bool kEndAligned = true;       // every tile's last row on the wave's last step
-    static constexpr int kLutWords = kLinLutWords;  // the kernel keeps lin_lut_fill's table and hands it over in PairTile::lut
+    static constexpr int kLutWords = kLinLutWords;  // the kernel keeps the pass's table and hands it over in PairTile::lut
+    static constexpr bool kColDrift = true;         // the column-drifted pass and lin_lut_fill_col's words (2b., 12.)
     using Base = SplitLayout<C1, C2, true>;
     template <bool RAW>
     __device__ static void load(const SeqSetDev &rs, const SeqSetDev &qf, const SeqSetDev &qr,
@@ -842,10 +1266,27 @@ template <int C1, int C2> struct SplitLayoutLin : SplitLayout<C1, C2, true> {
                                     int T_end, int tB, uint32_t *wsA, uint32_t *wsB, const PairTile &pt)
     {
         static_assert(!RAW, "the linear-gap pass reads 2-bit sets");
-        return dp_pass_lin_split<C1, C2>(kc, gl, ref16, qb, T_end, tB, wsA, wsB, pt.band, pt.full[0], pt.full[1], pt.lut);
+        return dp_pass_lin_split_col<C1, C2>(kc, gl, ref16, qb, T_end, tB, wsA, wsB, pt.band, pt.full[0], pt.full[1], pt.lut);
     }
     // lane and half-word of pass()'s return value that hold H[R][Q] of slot h
     __device__ static int fin_lane(int Q) { (void)Q; return kGroup - 1; }
+};
+
+// The same launch on the row-drifted pass, for the linear scorings whose pointer byte does not fit the column-drifted frame
+// (lin_col_drift_ok, 12. above).  A kernel symbol of its own: the names with SplitLayoutLin stay the column-drifted pass's.
+template <int C1, int C2> struct SplitLayoutLinRow : SplitLayoutLin<C1, C2> {
+    static constexpr bool kColDrift = false;
+    template <bool RAW>
+    __device__ static uint32_t pass(const P16Consts &kc, int gl, const uint16_t *ref16, const uint32_t (&qb)[C1 + C2],
+                                    int T_end, int tB, uint32_t *wsA, uint32_t *wsB, const PairTile &pt)
+    {
+        static_assert(!RAW, "the linear-gap pass reads 2-bit sets");
+        return dp_pass_lin_split<C1, C2>(kc, gl, ref16, qb, T_end, tB, wsA, wsB, pt.band, pt.full[0], pt.full[1], pt.lut);
+    }
+};
+
+template <int C1, int C2> struct SplitLayoutLinRowTeam : SplitLayoutLinRow<C1, C2> {      // (with the look-ahead walker, as below)
+    static constexpr bool kTeamWalk = true;
 };
 
 // The same launch with the look-ahead walker (teams of eight lanes, gact_chain.hpp).  Alone on the machine the team makes

@@ -546,6 +546,25 @@ __device__ __forceinline__ void lin_lut_fill(uint32_t *lut, const P16Consts &kc,
         lut[tid] = (b < kLinPadRow ? base >> b : 0u) + ((tid & 1) ? 0x01010101u : 0u);
     }
 }
+// The table of the column-drifted split pass (gact_lin.hpp 2b.): the diagonal lies two gaps below the cell's frame, so a real
+// row's bytes gain |g| on plain scores (|g| for a mismatch, match + 2|g| for a match) and 4|g| in the pointer phase; the pad
+// row's words stay 0 and 0x01010101 (a pad only ever lowers a value that the zero level clamps)
+__device__ __forceinline__ void lin_lut_fill_col(uint32_t *lut, const P16Consts &kc, const int tid)
+{
+    if (tid < kLinLutWords) {
+        const uint32_t b = 8u * ((uint32_t)tid >> 1), base = (tid & 1) ? kc.dsub4 : kc.dsub;
+        const uint32_t gap = (((tid & 1) ? kc.next4 : kc.next) & 0xffu) * 0x01010101u;
+        lut[tid] = (b < kLinPadRow ? (base >> b) + gap : 0u) + ((tid & 1) ? 0x01010101u : 0u);
+    }
+}
+// the fill that goes with the layout's pass (L::kColDrift, gact_lin.hpp 12.)
+template <class L, class = void> struct lin_col_drift { static constexpr bool value = false; };
+template <class L> struct lin_col_drift<L, std::void_t<decltype(L::kColDrift)>> { static constexpr bool value = L::kColDrift; };
+template <class L>
+__device__ __forceinline__ void lin_lut_fill_for_pass(uint32_t *lut, const P16Consts &kc, const int tid)
+{
+    if constexpr (lin_col_drift<L>::value) lin_lut_fill_col(lut, kc, tid); else lin_lut_fill(lut, kc, tid);
+}
 // the block's table: a __shared__ array of its own for every kernel that asks (N = 0: the layout has no such pass)
 template <int N> struct LinLutLds {
     __device__ __forceinline__ static uint32_t *get() { __shared__ __attribute__((aligned(8))) uint32_t words[N]; return words; }
@@ -847,7 +866,7 @@ __global__ __launch_bounds__(kBlockThreads, L::kBlocksPerCu) void extend_p16_ker
     // the split linear-gap pass's table of look-up words (gact_lin.hpp 8.)
     uint32_t *const lin_lut = LinLutLds<lin_lut_words<L>::value>::get();
     if constexpr (lin_lut_words<L>::value > 0) {
-        lin_lut_fill(lin_lut, kc, (int)threadIdx.x);
+        lin_lut_fill_for_pass<L>(lin_lut, kc, (int)threadIdx.x);
         __syncthreads();
     }
     // a wave owns 8 tile workspaces' worth of kp.ws_words, and its tiles' words are interleaved in it: row =

@@ -240,7 +240,7 @@ __global__ __launch_bounds__(kRoleThreads, 3) void extend_roles_kernel(
     }
     if (threadIdx.x == 0) dp_finished = 0;
     uint32_t *const lin_lut = LinLutLds<L::kLutWords>::get();      // the pass's table of look-up words (gact_lin.hpp 8.)
-    lin_lut_fill(lin_lut, kc, (int)threadIdx.x);
+    lin_lut_fill_for_pass<L>(lin_lut, kc, (int)threadIdx.x);
     __syncthreads();
 
     const int wave_in_block = threadIdx.x >> 6;
