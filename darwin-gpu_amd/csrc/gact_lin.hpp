@@ -28,7 +28,7 @@
 //       A window of them, W[k] = Zw(t - 1 + k) for k = 0 .. C2 + 1, serves region 1 (slot c: W[c + 1]), region 2 (the
 //       same) and the j = 0 border (W[0]: one gap below slot 0's level); the pointer phase keeps T[c] = 4 Zw(t + c) + 3
 //       for region 2.  They live in SGPRs, move by one s_add_u32 each per step (both half-words at once: every value is
-//       positive and far from a carry) and enter the cell as the scalar operand of the v_pk_maximum3_f16 that is there
+//       positive and far from a carry; inside whole blocks of steps they do not move at all, 13. below) and enter the cell as the scalar operand of the v_pk_maximum3_f16 that is there
 //       anyway.  A value that crosses a lane changes frames by a constant, folded into the DPP hand-over (11. below):
 //       (C1 - 1)|g| between lanes of region 1 and from lane 15's region 1 into lane 0's region 2 (scaled by four with
 //       the tag in the addend of the v_pk_mad_u16 of the pointer phase), (C2 - 1)|g| between lanes of region 2.  Slot
@@ -643,6 +643,52 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
     return tagged ? pk_ashr2(lin_sub(H2 | kc.c3, Z24)) : lin_sub(H2, Z2);
 }
 
+// 13. Sliding the zero levels (round 10; GACT_LIN_SLIDE=0 builds the per-step additions of 2b.).  The zero level of step t
+//     and slot c is Zw(t + c): from one step to the next the window does not change its contents, it moves up by one entry.
+//     Inside a block of kLinBlock steps whose places are compile-time facts (LinPos) the pass therefore keeps a STRIP of
+//     levels that covers the whole block, strip[j] = Zw(t0 - 1 + j) with t0 the block's first step (4 Zw(t0 + j) + 3 for
+//     the pointer phase's region 2), and step S reads strip[S + k] where the per-step form reads W[k] / T[k]: a renaming,
+//     no instruction.  The strip moves once per block, by kLinBlock |g| per entry (lin_strip_slide: opaque s_add_u32, several
+//     to an asm statement -- the hazard recogniser puts an s_nop behind a statement, not behind an instruction).
+//     The per-step form (the remainders, step_r1) keeps W[k] = Zw(t - 2 + k) BEFORE step t and adds |g| when the step begins;
+//     the strip holds the levels DURING the block's first step.  lin_strip_enter takes the first N entries from the one form
+//     to the other and builds the entries above them; lin_strip_leave takes them back (the strip has moved behind the last
+//     block, so its first N entries are then the levels during the step to come).  A handful of scalar instructions per
+//     phase and pass.  tests/test_lin_level_window.py drives exactly these helpers through the pass's loop structure.
+#ifndef GACT_LIN_SLIDE
+#define GACT_LIN_SLIDE 1
+#endif
+constexpr int kLinBlock = 8;
+// entries of a strip that serves a window of n levels through a block
+__host__ __device__ constexpr int lin_strip_len(int n, int steps = kLinBlock) { return GACT_LIN_SLIDE ? n + steps - 1 : n; }
+// the entry step S of a block reads for window entry k (a remainder step, or the per-step build: the window itself)
+__host__ __device__ constexpr int lin_strip_at(int S, int k) { return GACT_LIN_SLIDE && S != kLinTail ? S + k : k; }
+template <int N, int STEPS = kLinBlock, int LEN>
+__host__ __device__ __forceinline__ void lin_strip_enter(uint32_t (&s)[LEN], const uint32_t by)
+{
+    static_assert(lin_strip_len(N, STEPS) <= LEN, "the strip fits its registers");
+#pragma unroll
+    for (int k = 0; k < N; k++) s[k] += by;
+#pragma unroll
+    for (int k = N; k < lin_strip_len(N, STEPS); k++) s[k] = s[k - 1] + by;
+}
+template <int N, int LEN>
+__host__ __device__ __forceinline__ void lin_strip_leave(uint32_t (&s)[LEN], const uint32_t by)
+{
+#pragma unroll
+    for (int k = 0; k < N; k++) s[k] -= by;
+}
+// behind a block: every entry up by kLinBlock steps' worth (by_block); add4 / add1: four additions, one
+template <int N, int STEPS = kLinBlock, int LEN, class Add4, class Add1>
+__host__ __device__ __forceinline__ void lin_strip_slide(uint32_t (&s)[LEN], const uint32_t by_block, Add4 add4, Add1 add1)
+{
+    constexpr int M = lin_strip_len(N, STEPS);
+#pragma unroll
+    for (int j = 0; j + 4 <= M; j += 4) add4(s[j], s[j + 1], s[j + 2], s[j + 3], by_block);
+#pragma unroll
+    for (int j = M & ~3; j < M; j++) add1(s[j], by_block);
+}
+
 // ---------------------------------------------------------------------------
 // Split layout in the column-drifted frame (2b. above; which of the two runs: 12.): the same pass, same arguments.  Returns, in lane 15 of every group, H[R][Q] of both tiles
 // (packed, plain scores) -- valid when every tile's last row is the wave's last step (shift = T_end - Tend).
@@ -670,11 +716,14 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
     // the zero levels (2b. above).  During step t W[k] = Zw(t - 1 + k): W[0] the j = 0 border, W[c + 1] slot c of either
     // region; in the pointer phase T[c] = 4 Zw(t + c) + 3 is region 2's.  Wave-uniform: SGPRs, moved by the scalar unit
     constexpr int NWIN = C2 + 1;
-    uint32_t W[NWIN], T[C2];
+    // (GACT_LIN_SLIDE: strips, 13. above -- the window is their first NWIN / C1 + 1 / C2 entries between the block loops)
+    uint32_t W[lin_strip_len(NWIN)], T[lin_strip_len(C2)];
 #pragma unroll
     for (int k = 0; k < NWIN; k++) W[k] = pk2(lin_base(g) + (k - 1) * (-g));      // before step 1: Zw(k - 1)
 #pragma unroll
-    for (int c = 0; c < C2; c++) T[c] = 0;
+    for (int c = 0; c < lin_strip_len(C2); c++) T[c] = 0;
+#pragma unroll
+    for (int k = NWIN; k < lin_strip_len(NWIN); k++) W[k] = 0;
     // (an opaque addition in the pointer phase, a plain one on plain scores: 12. above)
     auto bump = [](uint32_t &z, const uint32_t by) { asm("s_add_u32 %0, %0, %1" : "+s"(z) : "s"(by) : "scc"); };
     auto advance = [&](const int nW, const bool tagged_too) {
@@ -684,6 +733,10 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
 #pragma unroll
             for (int c = 0; c < C2; c++) bump(T[c], g4s);
         }
+    };
+    auto bump4 = [](uint32_t &z0, uint32_t &z1, uint32_t &z2, uint32_t &z3, const uint32_t by) {
+        asm("s_add_u32 %0, %0, %4\n\ts_add_u32 %1, %1, %4\n\ts_add_u32 %2, %2, %4\n\ts_add_u32 %3, %3, %4"
+            : "+s"(z0), "+s"(z1), "+s"(z2), "+s"(z3) : "s"(by) : "scc");
     };
     uint32_t G[CT];                         // H of the previous row (drifted)
     uint32_t acc[2 * NW];                   // op codes of the last (up to) seven steps, one column each: the steps behind the last whole block
@@ -728,7 +781,8 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
         if (r1) { rb1 = row(lut_plain, sb1); rb1b = row(lut_plain, sb1b); }
         if (r2) { rb2 = row(tag2 ? lut_tagged : lut_plain, sb2); rb2b = row(tag2 ? lut_tagged : lut_plain, sb2b); }
     };
-    auto upper_all = [&](uint32_t (&U)[CT], const bool tag2) {
+    // o: the step's place in a block's strips (lin_strip_at), 0 for a step of the per-step form
+    auto upper_all = [&](uint32_t (&U)[CT], const bool tag2, const int o) {
         uint32_t P[CT];
 #pragma unroll
         for (int c = 0; c < CT; c++) P[c] = __builtin_amdgcn_perm(c < C1 ? rb1b : rb2b, c < C1 ? rb1 : rb2, qb[c]);
@@ -742,10 +796,10 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
         if (GACT_LIN_MAX3) {
 #pragma unroll
             for (int c = 0; c < CT; c++)                                         // :145-147 and the insertion, :149-154
-                U[c] = pk_max3f_s(U[c], c < C1 ? W[c + 1] : tag2 ? T[c - C1] : W[c - C1 + 1], G[c]);
+                U[c] = pk_max3f_s(U[c], c < C1 ? W[o + c + 1] : tag2 ? T[o + c - C1] : W[o + c - C1 + 1], G[c]);
         } else {
 #pragma unroll
-            for (int c = 0; c < CT; c++) U[c] = pk_max_sgpr(U[c], c < C1 ? W[c + 1] : tag2 ? T[c - C1] : W[c - C1 + 1]);     // :145-147
+            for (int c = 0; c < CT; c++) U[c] = pk_max_sgpr(U[c], c < C1 ? W[o + c + 1] : tag2 ? T[o + c - C1] : W[o + c - C1 + 1]);     // :145-147
             GACT_SB();
 #pragma unroll
             for (int c = 0; c < CT; c++) U[c] = lin_max<kLinSplitBuiltins>(U[c], G[c]);              // the insertion, :149-154
@@ -753,15 +807,16 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
         GACT_SB();
     };
 
-    auto step = [&]() {
+    auto step = [&](auto pos) {
+        constexpr int S = decltype(pos)::value, o = lin_strip_at(S, 0);
         ask_bytes(true, true);
-        advance(NWIN, false);
+        if (!GACT_LIN_SLIDE || S == kLinTail) advance(NWIN, false);
         // lane 0 of region 1 sits on the j = 0 border: one gap below its zero level
-        const uint32_t Hl1 = lin_hand_shr1(H1, k1v, W[0]);
+        const uint32_t Hl1 = lin_hand_shr1(H1, k1v, W[o]);
         // lane 0 of region 2 continues lane 15's region 1 (one step ago = same row)
         const uint32_t Hl2 = lin_hand_ror1_shr1(H1, k1v, H2, k2v);
         uint32_t U[CT];
-        upper_all(U, false);
+        upper_all(U, false, o);
         Hdiag1 = Hl1; Hdiag2 = Hl2;
         uint32_t Ha = Hl1, Hb = Hl2;
         static_assert(C2 >= C1, "region 2 is the longer chain");
@@ -813,13 +868,14 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
     auto step_tagged = [&](auto pos) {
         constexpr int S = decltype(pos)::value;
         constexpr bool blk = S != kLinTail;
+        constexpr int o = lin_strip_at(S, 0);
         ask_bytes(true, true);
-        advance(C1 + 1, true);
-        const uint32_t Hl1 = lin_hand_shr1(H1, k1v, W[0]);
+        if (!GACT_LIN_SLIDE || !blk) advance(C1 + 1, true);
+        const uint32_t Hl1 = lin_hand_shr1(H1, k1v, W[o]);
         // lane 15's region-1 column enters region 2 scaled and tagged 2
         const uint32_t Hl2 = lin_hand_shr1_over(lin_hand_scaled_ror1(H1, k12v), H2, k24v);
         uint32_t U[CT];
-        upper_all(U, true);
+        upper_all(U, true, o);
         Hdiag1 = Hl1; Hdiag2 = Hl2;
         uint32_t Ha = Hl1, Hb = Hl2;
         uint32_t tprev = 0, Hq = 0, x = 0;
@@ -851,8 +907,9 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
     auto step_tagged_r2 = [&](auto pos) {
         constexpr int S = decltype(pos)::value;
         constexpr bool blk = S != kLinTail;
+        constexpr int o = lin_strip_at(S, 0);
         ask_bytes(false, true);
-        advance(0, true);
+        if (!GACT_LIN_SLIDE || !blk) advance(0, true);
         const uint32_t Hl2 = lin_hand_shr1_over(lin_hand_scaled_ror1(H1, k12v), H2, k24v);
         uint32_t P[C2], U[C2];
 #pragma unroll
@@ -863,7 +920,7 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
         ask_rows(false, true, true);
         GACT_SB();
 #pragma unroll
-        for (int c = 0; c < C2; c++) U[c] = GACT_LIN_MAX3 ? pk_max3f_s(U[c], T[c], G[C1 + c]) : lin_max<kLinSplitBuiltins>(pk_max_sgpr(U[c], T[c]), G[C1 + c]);
+        for (int c = 0; c < C2; c++) U[c] = GACT_LIN_MAX3 ? pk_max3f_s(U[c], T[o + c], G[C1 + c]) : lin_max<kLinSplitBuiltins>(pk_max_sgpr(U[c], T[o + c]), G[C1 + c]);
         GACT_SB();
         Hdiag2 = Hl2;
         uint32_t Hb = Hl2;
@@ -925,8 +982,18 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
     }
     // (two steps per trip: the hand-over of the diagonal's registers from step to step is then a renaming)
     const int tU = imin(tB - 1, T_end);
-    for (; t + 1 <= tU; t += 2) { step(); step(); }
-    if (t <= tU) { step(); t++; }
+#if GACT_LIN_SLIDE
+    // (13. above: eight steps per trip on a strip of NWIN + 7 levels; the steps left over in the two-step form below --
+    //  as a single-step loop they cost the cooperative kernel two more spilled VGPRs)
+    lin_strip_enter<NWIN>(W, gs);
+    for (; t + kLinBlock - 1 <= tU; t += kLinBlock) {
+        GACT_LIN_BLOCK8(step);
+        lin_strip_slide<NWIN>(W, gs * kLinBlock, bump4, bump);
+    }
+    lin_strip_leave<NWIN>(W, gs);
+#endif
+    for (; t + 1 <= tU; t += 2) { step(LinPos<kLinTail>{}); step(LinPos<kLinTail>{}); }
+    if (t <= tU) { step(LinPos<kLinTail>{}); t++; }
     const bool tagged = t <= T_end;
     if (tagged) enter_tagged();
     uint4 *qA = reinterpret_cast<uint4 *>(wsA) + gl;
@@ -947,6 +1014,10 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
     // whole blocks of eight steps, each followed by its flush (an `if ((k & 7) == 7)` inside one loop is
     // if-converted by the compiler: the re-pairing v_perm of the flush would then run at every step)
     int k = 0;
+#if GACT_LIN_SLIDE
+    // (13. above: region 1's and the border's C1 + 1 levels and region 2's C2 scaled ones become strips for the whole blocks)
+    if (tagged) { lin_strip_enter<C1 + 1>(W, gs); lin_strip_enter<C2>(T, g4s); }
+#endif
     // (two loops one behind the other, not one loop with a branch inside: the two kinds of step keep their registers
     //  differently, and a loop that holds both moves ~90 registers per block to reconcile them)
     // (the eight steps are straight-line code: the stream offsets are immediates, the diagonal's registers are renamed)
@@ -954,6 +1025,10 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
     while (t + 7 <= T_end && t <= T_end - LAG) {
         GACT_LIN_BLOCK8(step_tagged);
         t += 8; k += 8;
+#if GACT_LIN_SLIDE
+        lin_strip_slide<C1 + 1>(W, gs * kLinBlock, bump4, bump);
+        lin_strip_slide<C2>(T, g4s * kLinBlock, bump4, bump);
+#endif
         lin_flush_groups<C2>(grp, odd, qA, qB, bd.store(0, t - 8, t - 1), bd.store(1, t - 8, t - 1));
         qA += QD * kWsRow;
         qB += QD * kWsRow;
@@ -961,11 +1036,17 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
     while (t + 7 <= T_end) {
         GACT_LIN_BLOCK8(step_tagged_r2);
         t += 8; k += 8;
+#if GACT_LIN_SLIDE
+        lin_strip_slide<C2>(T, g4s * kLinBlock, bump4, bump);
+#endif
         lin_flush_groups<C2>(grp, odd, qA, qB, bd.store(0, t - 8, t - 1), bd.store(1, t - 8, t - 1));
         qA += QD * kWsRow;
         qB += QD * kWsRow;
     }
 #undef GACT_LIN_BLOCK8
+#if GACT_LIN_SLIDE
+    if (tagged) { lin_strip_leave<C1 + 1>(W, gs); lin_strip_leave<C2>(T, g4s); }
+#endif
     // (what is left are the last seven steps at most: region 2 alone, unless the pointer phase began inside them)
     for (; t <= T_end - LAG; t++, k++) step_tagged(LinPos<kLinTail>{});
     for (; t <= T_end; t++, k++) step_tagged_r2(LinPos<kLinTail>{});

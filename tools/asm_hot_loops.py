@@ -10,7 +10,9 @@ tells the split pass's two-region steps (7 + 13 slots) from its one-region steps
 per slot: 5 on plain scores in the row-drifted frame, 4 in the column-drifted frame of the split pass (gact_lin.hpp 2.: its
 hand-overs are v_sub_u32_dpp, which is how a loop of that frame is told), 8 where pointers are made, 10 with the seed
 launch's arg-max key.  Beside s_nop the scalar additions per step (the split pass moves its zero levels on the scalar unit)
-and the lane-spill instructions (v_readlane_b32 / v_writelane_b32) inside the loop."""
+and the lane-spill instructions (v_readlane_b32 / v_writelane_b32) inside the loop.  "all": every instruction per step, whatever
+unit issues it -- a wave issues in order, so each takes a place in its stream.  The s_nop are reported in two parts: those that
+stand directly behind a scalar addition ("nop<add": the hazard recogniser puts one behind an inline-asm statement) and the rest."""
 import re
 import sys
 from collections import Counter
@@ -42,9 +44,11 @@ def describe(name, lines, meta):
     print("  vgprs %s  vgpr spills %s  sgpr spills %s  scratch %s B  LDS %s B  code %d lines" % (
         meta.get("vgpr_count", "?"), meta.get("vgpr_spill_count", "?"), meta.get("sgpr_spill_count", "?"),
         meta.get("private_segment_fixed_size", "?"), meta.get("group_segment_fixed_size", "?"), sum(1 for l in lines if is_inst(l))))
-    print("  %-24s %6s %6s %11s %9s %5s %4s %6s %6s %8s %10s" % ("loop", "steps", "VALU", "VALU/step", "recurr.", "rest", "LDS", "s_nop", "s_add", "scratch", "lane spill"))
+    print("  %-24s %6s %8s %6s %11s %9s %5s %4s %6s %7s %6s %8s %10s" % ("loop", "steps", "all/step", "VALU", "VALU/step", "recurr.", "rest", "LDS", "s_nop", "nop<add", "s_add", "scratch", "lane spill"))
     for a, b, label in loops_of(lines):
-        c = Counter(l.split()[0] for l in lines[a:b + 1] if is_inst(l))
+        insts = [l.split()[0] for l in lines[a:b + 1] if is_inst(l)]
+        c = Counter(insts)
+        nop_add = sum(1 for p, q in zip(insts, insts[1:]) if q == "s_nop" and p.startswith("s_add"))
         n_max3 = c.get("v_pk_maximum3_f16", 0)
         if n_max3 == 0:
             continue
@@ -58,9 +62,9 @@ def describe(name, lines, meta):
                 col_drift = c.get("v_sub_u32_dpp", 0) > 0
                 kind, steps, rec = kname, n_max3 // per, plain * (4 if col_drift else 5) + ptr * (10 if amax else 8)
                 break
-        print("  %-24s %6d %6d %11.1f %9d %5.1f %4.1f %6.1f %6.1f %8d %10d" % (
-            kind + " " + label, steps, valu, valu / steps, rec, valu / steps - rec,
-            sum(v for n, v in c.items() if n.startswith("ds_")) / steps, c.get("s_nop", 0) / steps,
+        print("  %-24s %6d %8.1f %6d %11.1f %9d %5.1f %4.1f %6.1f %7.1f %6.1f %8d %10d" % (
+            kind + " " + label, steps, len(insts) / steps, valu, valu / steps, rec, valu / steps - rec,
+            sum(v for n, v in c.items() if n.startswith("ds_")) / steps, (c.get("s_nop", 0) - nop_add) / steps, nop_add / steps,
             sum(v for n, v in c.items() if n.startswith("s_add")) / steps,
             sum(v for n, v in c.items() if n.startswith("scratch_")),
             c.get("v_readlane_b32", 0) + c.get("v_writelane_b32", 0)))
