@@ -266,6 +266,21 @@ struct Slot {
             p = nullptr; bytes = 0; ev0 = ev1 = nullptr;
         }
     } cover;
+    // gact_hip_overlap_graph (gact_graph.hpp): one allocation, grown to what the largest call so far needed
+    struct GraphBufs {
+        uint8_t *p = nullptr;                          // host records | sel | sums | lens | clip | read table, degrees, counters | table | proposals | arcs
+        size_t bytes = 0;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;       // around the whole call (gact_hip_last_graph_stats)
+        gact_graph_stats stats{};
+        bool timed = false;
+        void release()
+        {
+            if (p) (void)hipFree(p);
+            if (ev0) (void)hipEventDestroy(ev0);
+            if (ev1) (void)hipEventDestroy(ev1);
+            p = nullptr; bytes = 0; ev0 = ev1 = nullptr;
+        }
+    } graph;
     // gact_hip_pileup_add (gact_pileup.hpp): the events around this slot's adds; the counts are the engine's (Pileup)
     hipEvent_t pile_ev0 = nullptr, pile_ev1 = nullptr;
 };
@@ -1466,6 +1481,7 @@ void gact_hip_destroy(gact_hip_engine *e)
         sl.summary.release();
         sl.select.release();
         sl.cover.release();
+        sl.graph.release();
         if (sl.pile_ev0) (void)hipEventDestroy(sl.pile_ev0);
         if (sl.pile_ev1) (void)hipEventDestroy(sl.pile_ev1);
         if (sl.d_counter) (void)hipFree(sl.d_counter);
@@ -2722,6 +2738,7 @@ int gact_hip_measure_valu_rate(gact_hip_engine *e, double *lane_ops_per_s)
 #include "gact_gather.hpp"       // gact_hip_comm_*: the RCCL gather of a sharded job
 #include "gact_select.hpp"       // gact_hip_select_overlaps: one overlap per class, behind every other kernel
 #include "gact_cover.hpp"        // gact_hip_read_coverage: per-read coverage of an overlap set, behind those
+#include "gact_graph.hpp"        // gact_hip_overlap_graph: containment, dovetail arcs and their transitive flags, behind those
 #include "gact_pileup.hpp"       // gact_hip_pileup_*: per-base pileup and consensus from the alignments' columns
 
 #ifdef GACT_STAMPS

@@ -14,7 +14,7 @@ _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.path.join(_PKG, "libgact_hip.so")
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in
            ("gact_engine.hip", "gact_kernels.hpp", "gact_device.hpp", "gact_chain.hpp", "gact_p16.hpp", "gact_p16s.hpp", "gact_lin.hpp",
-            "gact_aff.hpp", "gact_roles.hpp", "gact_coop.hpp", "gact_policy.hpp", "gact_big.hpp", "gact_gather.hpp", "gact_chain_kernel.hpp", "gact_path.hpp", "gact_summary.hpp", "gact_select.hpp", "gact_cover.hpp", "gact_pileup.hpp",
+            "gact_aff.hpp", "gact_roles.hpp", "gact_coop.hpp", "gact_policy.hpp", "gact_big.hpp", "gact_gather.hpp", "gact_chain_kernel.hpp", "gact_path.hpp", "gact_summary.hpp", "gact_select.hpp", "gact_cover.hpp", "gact_graph.hpp", "gact_pileup.hpp",
             "dsoft_device.hpp", "dsoft_engine.hpp")] + \
           [os.path.join(_ROOT, "include", "gact_hip.h")]
 
@@ -37,6 +37,13 @@ assert SUMMARY_DTYPE.itemsize == 32
 COVER_DTYPE = np.dtype([(n, "<i4") for n in ("n_intervals", "max_depth", "covered", "well_covered", "span_begin", "span_end")] +
                        [("depth_sum", "<i8")])
 assert COVER_DTYPE.itemsize == 32
+# the overlap graph (include/gact_hip.h gact_hip_overlap_graph): an arc u -> v of the bidirected graph, and the per-read table
+GRAPH_ARC_DTYPE = np.dtype([(n, "<i4") for n in ("u", "v", "len", "ov_u", "ov_v", "record", "score", "flags")])
+GRAPH_READ_DTYPE = np.dtype([(n, "<i4") for n in ("n_hits", "n_internal", "n_contains", "contained_by")] +
+                            [("deg", "<i4", (2,)), ("kept", "<i4", (2,))])
+assert GRAPH_ARC_DTYPE.itemsize == 32 and GRAPH_READ_DTYPE.itemsize == 32
+GRAPH_NONE, GRAPH_SELF, GRAPH_DROPPED, GRAPH_INTERNAL, GRAPH_QUERY_CONTAINED, GRAPH_TARGET_CONTAINED, GRAPH_SHORT, \
+    GRAPH_DOVETAIL = range(8)
 # the kinds a position of a pileup counts (include/gact_hip.h GACT_PILEUP_*), and the per-read table of pileup_finish
 PILEUP_A, PILEUP_C, PILEUP_G, PILEUP_T, PILEUP_OTHER, PILEUP_DEL, PILEUP_INS, PILEUP_DEPTH = range(8)
 PILEUP_COL_DTYPE = np.dtype([("n", "<u4", (8,))])
@@ -124,6 +131,20 @@ _SELECT_MODES = {"exact": SELECT_EXACT, "pair": SELECT_PAIR}
 class CoverStats(C.Structure):
     _fields_ = [("device_ms", C.c_float), ("reads", C.c_int32), ("intervals", C.c_int64), ("positions", C.c_int64),
                 ("scratch_bytes", C.c_int64)]
+
+
+class GraphParams(C.Structure):
+    """the defaults are GACT_GRAPH_DEFAULT_*"""
+    _fields_ = [(n, C.c_int32) for n in ("max_hang", "int_permille", "min_ovlp", "fuzz")]
+
+    def __init__(self, max_hang=1000, int_permille=800, min_ovlp=1000, fuzz=1000):
+        super().__init__(max_hang, int_permille, min_ovlp, fuzz)
+
+
+class GraphStats(C.Structure):
+    _fields_ = [("device_ms", C.c_float), ("reads", C.c_int32), ("contained", C.c_int32), ("by_class", C.c_int64 * 8),
+                ("proposed", C.c_int64), ("arcs", C.c_int64), ("transitive", C.c_int64), ("kept", C.c_int64),
+                ("table_slots", C.c_int64), ("scratch_bytes", C.c_int64)]
 
 
 class PileupStats(C.Structure):
@@ -295,6 +316,14 @@ def load():
     except AttributeError:
         pass
     try:
+        L.gact_hip_overlap_graph.argtypes = [vp, C.c_int, i32, vp, i32, vp, vp, i32, vp, vp, C.POINTER(GraphParams), vp, vp, vp,
+                                             C.c_int64, C.POINTER(C.c_int64)]
+        L.gact_hip_overlap_graph.restype = C.c_int
+        L.gact_hip_last_graph_stats.argtypes = [vp, C.c_int, C.POINTER(GraphStats)]
+        L.gact_hip_last_graph_stats.restype = C.c_int
+    except AttributeError:
+        pass
+    try:
         L.gact_hip_pileup_begin.argtypes = [vp, i32, i32]
         L.gact_hip_pileup_add.argtypes = [vp, C.c_int, i32, vp, i32, C.c_int]
         L.gact_hip_pileup_finish.argtypes = [vp, i32, vp, vp, vp]
@@ -335,7 +364,8 @@ EXPORTS = ("gact_hip_create", "gact_hip_destroy", "gact_hip_last_error", "gact_h
            "gact_hip_comm_create", "gact_hip_comm_gather_lines", "gact_hip_comm_destroy", "gact_hip_options_describe", "gact_hip_plan_describe",
            "gact_hip_candidates_paths", "gact_hip_last_paths_stats", "gact_hip_candidates_summaries",
            "gact_hip_last_summaries_stats", "gact_hip_format_paf", "gact_hip_select_overlaps", "gact_hip_last_select_stats",
-           "gact_hip_read_coverage", "gact_hip_last_cover_stats", "gact_hip_pileup_begin", "gact_hip_pileup_add",
+           "gact_hip_read_coverage", "gact_hip_last_cover_stats", "gact_hip_overlap_graph", "gact_hip_last_graph_stats",
+           "gact_hip_pileup_begin", "gact_hip_pileup_add",
            "gact_hip_pileup_finish", "gact_hip_last_pileup_stats")
 
 
@@ -616,6 +646,57 @@ class Engine:
         st = CoverStats()
         self._check(self.L.gact_hip_last_cover_stats(self.h, slot, C.byref(st)))
         return {n: getattr(st, n) for n, _ in CoverStats._fields_}
+
+    def overlap_graph(self, read_lens, n=None, records=None, sel=None, sums=None, clip=None, params=None, classes=False, slot=0):
+        """the overlap graph of an overlap set, made on the device: (reads, arcs) -- one GRAPH_READ_DTYPE record per read of
+        `read_lens` (hits, internal hits, reads it contains, the record that contains it or -1, out-degrees of its two vertices,
+        all arcs and kept ones) and the GRAPH_ARC_DTYPE arcs ascending by (u, len, v), vertex 2 i = read i, 2 i + 1 its reverse
+        complement, kept iff flags == 0 -- or (reads, arcs, classes) with one GRAPH_* class byte per chosen record.  records, n,
+        sel and sums as in read_coverage.  clip: None, or (n_reads, 2) int32 [begin, end) of every read, read_coverage's
+        span_begin / span_end.  params: None, a GraphParams, or a dict of max_hang, int_permille, min_ovlp, fuzz
+        (include/gact_hip.h gact_hip_overlap_graph)"""
+        read_lens = np.ascontiguousarray(read_lens, dtype=np.int32)
+        if records is not None:
+            records = np.ascontiguousarray(records, dtype=OVERLAP_DTYPE)
+            n = len(records) if n is None else n
+            assert n <= len(records)
+        elif n is None:
+            n = self._n_cands.get(slot, 0)
+        n = int(n)
+        if sel is not None:
+            sel = np.ascontiguousarray(sel, dtype=np.int32)
+        n_chosen = len(sel) if sel is not None else max(n, 0)
+        if sums is not None:
+            sums = np.ascontiguousarray(sums, dtype=SUMMARY_DTYPE)
+            assert len(sums) == n_chosen
+        if clip is not None:
+            clip = np.ascontiguousarray(clip, dtype=np.int32).reshape(-1)
+            assert len(clip) == 2 * len(read_lens)
+        if isinstance(params, dict):
+            params = GraphParams(**params)
+        reads = np.zeros(len(read_lens), dtype=GRAPH_READ_DTYPE)
+        cls = np.zeros(n_chosen, dtype=np.uint8) if classes else None
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        n_arcs = C.c_int64()
+        cap = n_chosen                              # (room for 2 * n_chosen always suffices; most sets need less than half)
+        for attempt in range(2):
+            arcs = np.zeros(cap, dtype=GRAPH_ARC_DTYPE)
+            rc = self.L.gact_hip_overlap_graph(self.h, slot, n, ptr(records), len(sel) if sel is not None else 0, ptr(sel), ptr(sums),
+                                               len(read_lens), ptr(read_lens), ptr(clip), C.byref(params) if params is not None else None,
+                                               ptr(reads), ptr(cls), ptr(arcs), cap, C.byref(n_arcs))
+            if rc == 0 or attempt or n_arcs.value <= cap:
+                break
+            cap = n_arcs.value                      # (EINVAL with *n_arcs filled: once more with room for them)
+        self._check(rc)
+        arcs = arcs[:n_arcs.value].copy()
+        return (reads, arcs, cls) if classes else (reads, arcs)
+
+    def last_graph_stats(self, slot=0):
+        """the slot's last overlap graph: device ms (HIP events around the whole call), reads, contained reads, chosen records
+        per class (a list of 8), arcs proposed, arcs, transitive arcs, kept arcs, table slots, device bytes the call holds"""
+        st = GraphStats()
+        self._check(self.L.gact_hip_last_graph_stats(self.h, slot, C.byref(st)))
+        return {n: (list(getattr(st, n)) if n == "by_class" else getattr(st, n)) for n, _ in GraphStats._fields_}
 
     def pileup_begin(self, read_first=0, n_reads=None):
         """opens the pileup window: reads [read_first, read_first + n_reads) of SET_REF (n_reads None: to the set's end), counts

@@ -3,7 +3,7 @@
 //   darwin_hip <REF.fasta> <READS.fasta> CPU_THREADS [--params params.cfg]
 //              [--candidates FILE | --dump-candidates FILE [--dsoft-only]] [--device-dsoft]
 //              [--device D] [--shard R/W] [--recode] [--cigar] [--paf] [--unique exact|pair] [--coverage K]
-//              [--pileup K]
+//              [--pileup K] [--gfa]
 //
 // Plays the part of reference darwin.cpp:451-646 for the GACT stage: owns the
 // globals gact.cpp reads, loads params.cfg and the two FASTA files, builds the
@@ -39,6 +39,12 @@
 // them before the feeders start, one gact_hip_pileup_add per feeder behind its run, gact_hip_pileup_finish(K) after the join --
 // and darwin.cons.fa gets one record per reference sequence in id order: `>name called=<n> changed=<n> deleted=<n>
 // ins_flagged=<n>`, then the consensus bytes with every '-' left out, on one line.  Every other output byte is as without the flag.
+// --gfa (with --device-dsoft and one input file used for both sides, not with --shard): after the feeders have finished, the
+// records they wrote (the emitted ones; with --unique the selected ones; with --paf together with their summaries) go through
+// one gact_hip_overlap_graph call with the default parameters -- with --coverage K clipped to that table's spans, else against
+// whole reads -- and darwin.gfa gets `H VN:Z:1.0`, one `S <name> <clipped bases> LN:i:<n>` line per read that is not contained
+// and has a non-empty clip, in id order, and one `L <u name> <+|-> <v name> <+|-> <min(ov_u, ov_v)>M L1:i:<len>` line per kept
+// arc, in the arc list's order.  Every other output byte is as without the flag.
 //
 // --device D: the GPU this process uses (the reference is single-device, cuda_host.cu:195).  --shard R/W: this
 // process is rank R of W -- it extends every W-th candidate (host filter) or the R-th contiguous range of reads
@@ -80,7 +86,8 @@ static bool want_paf = false;                    // --paf
 static int unique_mode = -1;                     // --unique: GACT_SELECT_EXACT / GACT_SELECT_PAIR, -1: every emitted record
 static int coverage_depth = 0;                   // --coverage K: min_depth of darwin.cover.tsv, 0: no table
 static int pileup_depth = 0;                     // --pileup K: min_depth of darwin.cons.fa, 0: no consensus
-// --coverage: the records every feeder wrote a line for, in its file's order, and with --paf their summaries
+static bool want_gfa = false;                    // --gfa: darwin.gfa, the overlap graph of the records written
+// --coverage, --gfa: the records every feeder wrote a line for, in its file's order, and with --paf their summaries
 static std::vector<std::vector<gact_overlap> > cover_records;
 static std::vector<std::vector<gact_path_summary> > cover_sums;
 std::vector<long long int> reference_lengths, reads_lengths;
@@ -293,7 +300,7 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
     for (int32_t at = 0; at < n; at++) {
         const gact_overlap &r = o[(size_t)at];
         if (!r.emitted || !keep[(size_t)at]) continue;
-        if (coverage_depth) {
+        if (coverage_depth || want_gfa) {
             cover_records[(size_t)cpu_id].push_back(r);
             if (want_paf) cover_sums[(size_t)cpu_id].push_back(sums[next]);
         }
@@ -335,8 +342,8 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
     print_stage("Time GACT calling", t1, now());                 // darwin.cpp:441
 }
 
-// --coverage: one call over the records all feeders kept, on slot 0, then darwin.cover.tsv
-static int write_coverage(gact_hip_engine *e)
+// --coverage: one call over the records all feeders kept, on slot 0, then darwin.cover.tsv; the spans go to `spans` for --gfa
+static int write_coverage(gact_hip_engine *e, std::vector<int32_t> *spans)
 {
     std::vector<gact_overlap> rec;
     std::vector<gact_path_summary> sums;
@@ -351,12 +358,48 @@ static int write_coverage(gact_hip_engine *e)
                                           same_file ? GACT_COVER_BOTH : GACT_COVER_REF, coverage_depth, (int32_t)lens.size(),
                                           lens.data(), cover.data(), nullptr);
     if (rc != 0) { printf("\ngact_hip_read_coverage failed: %s\n\n", gact_hip_last_error()); return 1; }
+    if (spans)
+        for (const gact_read_cover &c : cover) { spans->push_back(c.span_begin); spans->push_back(c.span_end); }
     FILE *f = fopen("darwin.cover.tsv", "w");
     if (!f) { fprintf(stderr, "--coverage: cannot write darwin.cover.tsv\n"); return 1; }
     for (size_t i = 0; i < cover.size(); i++) {
         const gact_read_cover &c = cover[i];
         fprintf(f, "%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.3f\n", names[i][0].c_str(), lens[i], c.n_intervals, c.max_depth, c.covered,
                 c.well_covered, c.span_begin, c.span_end, lens[i] ? (double)c.depth_sum / lens[i] : 0.0);
+    }
+    fclose(f);
+    return 0;
+}
+
+// --gfa: one call over the records all feeders kept, on slot 0, then darwin.gfa.  clip: the spans of --coverage, or empty
+static int write_gfa(gact_hip_engine *e, const std::vector<int32_t> &clip)
+{
+    std::vector<gact_overlap> rec;
+    std::vector<gact_path_summary> sums;
+    for (const auto &v : cover_records) rec.insert(rec.end(), v.begin(), v.end());
+    for (const auto &v : cover_sums) sums.insert(sums.end(), v.begin(), v.end());
+    std::vector<int32_t> lens(reads_seqs.size());
+    for (size_t i = 0; i < reads_seqs.size(); i++) lens[i] = (int32_t)reads_seqs[i].size();
+    std::vector<gact_graph_read> reads(lens.size());
+    std::vector<gact_graph_arc> arcs(2 * rec.size() + 1);            // (twice the chosen count always suffices)
+    int64_t n_arcs = 0;
+    const int rc = gact_hip_overlap_graph(e, 0, (int32_t)rec.size(), rec.data(), 0, nullptr, want_paf ? sums.data() : nullptr,
+                                          (int32_t)lens.size(), lens.data(), clip.empty() ? nullptr : clip.data(), nullptr,
+                                          reads.data(), nullptr, arcs.data(), (int64_t)arcs.size(), &n_arcs);
+    if (rc != 0) { printf("\ngact_hip_overlap_graph failed: %s\n\n", gact_hip_last_error()); return 1; }
+    FILE *f = fopen("darwin.gfa", "w");
+    if (!f) { fprintf(stderr, "--gfa: cannot write darwin.gfa\n"); return 1; }
+    fprintf(f, "H\tVN:Z:1.0\n");
+    for (size_t i = 0; i < reads.size(); i++) {
+        const int32_t b = clip.empty() ? 0 : clip[2 * i], end = clip.empty() ? lens[i] : clip[2 * i + 1];
+        if (reads[i].contained_by >= 0 || end <= b) continue;
+        fprintf(f, "S\t%s\t%.*s\tLN:i:%d\n", reads_descrips[i][0].c_str(), (int)(end - b), reads_seqs[i].c_str() + b, (int)(end - b));
+    }
+    for (int64_t k = 0; k < n_arcs; k++) {
+        const gact_graph_arc &a = arcs[(size_t)k];
+        if (a.flags) continue;
+        fprintf(f, "L\t%s\t%c\t%s\t%c\t%dM\tL1:i:%d\n", reads_descrips[(size_t)(a.u >> 1)][0].c_str(), a.u & 1 ? '-' : '+',
+                reads_descrips[(size_t)(a.v >> 1)][0].c_str(), a.v & 1 ? '-' : '+', std::min(a.ov_u, a.ov_v), a.len);
     }
     fclose(f);
     return 0;
@@ -556,7 +599,7 @@ int main(int argc, char *argv[])
     if (argc >= 3 && strcmp(argv[1], "--selftest") == 0) return selftest(argv[2]);
     if (argc < 4) {
         fprintf(stderr, "Usage: darwin_hip <REFERENCE>.fasta <READS>.fasta CPU_THREADS --candidates FILE "
-                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K]]\n");
+                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K] [--gfa]]\n");
         return 1;
     }
     std::string cand_path, dump_path, cfg_path = "params.cfg", gather_id;
@@ -590,6 +633,7 @@ int main(int argc, char *argv[])
             if (!*v || *end || k < 1 || k > 0x7fffffffL) { fprintf(stderr, "--pileup wants an integer >= 1, not '%s'\n", v); return 1; }
             pileup_depth = (int)k;
         }
+        else if (!strcmp(argv[a], "--gfa")) want_gfa = true;
         else if (!strcmp(argv[a], "--rccl-gather") && a + 1 < argc) gather_id = argv[++a];
         else if (!strcmp(argv[a], "--device") && a + 1 < argc) setenv("GACT_HIP_DEVICE", argv[++a], 1);   // read by GPU_init
         else if (!strcmp(argv[a], "--shard") && a + 1 < argc) {
@@ -626,6 +670,12 @@ int main(int argc, char *argv[])
         // the counts come from the alignments of one engine's candidate arrays, and a rank of a sharded job holds part of every
         // sequence's overlaps: combining the ranks' counts is left to the caller
         fprintf(stderr, "--pileup: only with --device-dsoft, and not with --shard\n");
+        return 1;
+    }
+    if (want_gfa && (!device_dsoft || shard_given || strcmp(argv[1], argv[2]) != 0)) {
+        // the graph is over one read set, from the records of one process's feeders: the host-filter mode keeps none, a rank of a
+        // sharded job holds part of every read's overlaps, and with two files ref and query ids name different sequences
+        fprintf(stderr, "--gfa: only with --device-dsoft and one input file used for both sides, and not with --shard\n");
         return 1;
     }
     std::map<std::string, double> cfg = parse_cfg(cfg_path);
@@ -702,10 +752,12 @@ int main(int argc, char *argv[])
             for (auto &v : dumps) { out.write((const char *)v.data(), (std::streamsize)(v.size() * sizeof(Cand))); total += v.size(); }
             printf("num_candidates: %zu\n", total);
         }
-        const int cover_rc = coverage_depth && !dumping ? write_coverage(e) : 0;
+        std::vector<int32_t> spans;
+        const int cover_rc = coverage_depth && !dumping ? write_coverage(e, want_gfa ? &spans : nullptr) : 0;
+        const int gfa_rc = want_gfa && !dumping && !cover_rc ? write_gfa(e, spans) : 0;
         const int cons_rc = pileup_depth && !dumping ? write_consensus(e) : 0;
         GPU_close(&s, num_threads);
-        return cover_rc ? cover_rc : cons_rc;
+        return cover_rc ? cover_rc : gfa_rc ? gfa_rc : cons_rc;
     }
 
     // per-thread candidate lists, contiguous read ranges like darwin.cpp:619-629

@@ -324,7 +324,8 @@ int gact_hip_last_select_stats(gact_hip_engine *e, int slot, gact_select_stats *
 /* ---- per-read coverage: how deep every read is covered by an overlap set, and where it is covered min_depth deep ----
  * What a consumer of the overlaps (miniasm, racon) computes first: the depth along every read, and the stretch of it that is
  * covered at least min_depth deep -- the rest is adapter or chimera and gets clipped; for reads against contigs, the depth the
- * reads give each contig.  A read-level statistic: containment and transitive reduction stay with the assembler.  The records
+ * reads give each contig.  A read-level statistic: containment and transitive reduction are gact_hip_overlap_graph's, below,
+ * which takes span_begin / span_end of this table as its clip.  The records
  * are on the device when a run ends, and so are the indices of gact_hip_select_overlaps and the summaries of
  * gact_hip_candidates_summaries; this entry sweeps them there (csrc/gact_cover.hpp).
  *   records          as in gact_hip_select_overlaps: NULL = records [0, n) of the slot's device-resident array as its last run
@@ -379,6 +380,99 @@ int gact_hip_read_coverage(gact_hip_engine *e, int slot, int32_t n, const gact_o
  * device memory the call holds for itself. */
 typedef struct { float device_ms; int32_t reads; int64_t intervals, positions, scratch_bytes; } gact_cover_stats;
 int gact_hip_last_cover_stats(gact_hip_engine *e, int slot, gact_cover_stats *stats);
+
+/* ---- overlap graph: containment, bidirected dovetail arcs and their transitive flags, made on the device ----
+ * The step between an all-vs-all overlap set and an assembler's layout stage (miniasm's): every overlap is classified against the
+ * clipped reads, contained reads are marked, every dovetail overlap between two reads that are not contained becomes an arc and
+ * its complement, and the arcs a triangle explains are flagged (csrc/gact_graph.hpp).  All integer, order-free.
+ * Inputs.
+ *   records, n, sel, n_sel, sums   exactly as gact_hip_read_coverage takes them: records == NULL is the slot's device array; a
+ *                    record counts when it is emitted and named by sel (sel == NULL: every record of [0, n)); with sums the
+ *                    begins are ab' = ae - (n_eq + n_x + del_bases), bb' = be - (n_eq + n_x + ins_bases), else ab' = ab, bb' = bb.
+ *                    Ref and query ids name the same read set
+ *   read_lens        the n_reads lengths
+ *   clip             NULL: every read whole; else clip[2 i], clip[2 i + 1] = [cb, ce) of read i, 0 <= cb <= ce <= len: the caller
+ *                    passes cover[i].span_begin / span_end of gact_hip_read_coverage
+ *   params           NULL: GACT_GRAPH_DEFAULT_*.  max_hang, int_permille, min_ovlp, fuzz, all >= 0, int_permille <= 1000.  The
+ *                    defaults are parameters chosen after miniasm's usual values, not measurements
+ * Vertices.  2 i is read i as stored, 2 i + 1 its reverse complement.  The complement of vertex x is x ^ 1, the complement of arc
+ * u -> v is v^1 -> u^1.
+ * Class of a counted record (t = ref_id, q = query_id, rev = comp != 0); the first rule that applies wins; 64-bit arithmetic:
+ *   1 GACT_GRAPH_SELF     t == q
+ *   2 clip.  The query's clip is taken in the frame of its strand: (cbq, ceq) becomes (len_q - ceq, len_q - cbq) when rev.  Then
+ *     ts = max(ab', cb_t), te = min(ae, ce_t), qs = max(bb', cbq), qe = min(be, ceq): each end is clamped on its own, the other
+ *     read's end is not moved with it.  GACT_GRAPH_DROPPED when te <= ts or qe <= qs (so every record of a read whose clip is
+ *     empty).  Then all four are rebased to the clips' begins; tl, ql are the clipped lengths
+ *   3 ext5 = min(qs, ts), ext3 = min(ql - qe, tl - te), sq = qe - qs, st = te - ts.  GACT_GRAPH_INTERNAL when ext5 > max_hang or
+ *     ext3 > max_hang or 1000 sq < int_permille (sq + ext5 + ext3)
+ *   4 q_in = qs <= ts && ql - qe <= tl - te; t_in = qs >= ts && ql - qe >= tl - te.  GACT_GRAPH_QUERY_CONTAINED /
+ *     GACT_GRAPH_TARGET_CONTAINED; both true: the contained read is the one with the shorter clipped length, on a tie the one with
+ *     the higher read id
+ *   5 GACT_GRAPH_SHORT    sq + ext5 + ext3 < min_ovlp or st + ext5 + ext3 < min_ovlp
+ *   6 GACT_GRAPH_DOVETAIL the record proposes two arcs, with ov_q = sq + ext5 + ext3 and ov_t = st + ext5 + ext3:
+ *       qs > ts     (2 q + rev) -> (2 t), len = qs - ts, ov_u = ov_q, ov_v = ov_t, and its complement
+ *                   (2 t + 1) -> (2 q + 1 - rev), len = (tl - te) - (ql - qe), ov_u = ov_t, ov_v = ov_q
+ *       otherwise   (2 t) -> (2 q + rev), len = ts - qs, ov_u = ov_t, ov_v = ov_q, and its complement
+ *                   (2 q + 1 - rev) -> (2 t + 1), len = (ql - qe) - (tl - te), ov_u = ov_q, ov_v = ov_t
+ *     Every len is >= 1 by construction (a record with qs == ts, or with equal 3' rests, is a containment).
+ * A chosen record that is not counted has class GACT_GRAPH_NONE.
+ * Contained reads.  Read i is contained iff some counted record's class names it as the contained read; contained_by is the
+ * lowest such record index, else -1.  Two records that disagree -- (a, b) says a is inside b, (b, a) says the reverse -- remove
+ * both reads: known, and not repaired.
+ * Arcs.  The proposals of the DOVETAIL records whose two reads are both not contained.  One arc per (u, v): among the proposals
+ * for a key the one of the record with the higher score wins, then the lower record index (then the earlier place in sel, which
+ * matters only when sel names a record twice).  A record proposes an arc and its complement together, and two records that share
+ * one key share the other, so the same record wins both keys: the set is closed under complement, with the same `record`.
+ * Output ascending by (u, len, v).
+ * Transitive flags.  Bit 0 of an arc u -> x: some w exists with arcs u -> w and w -> x in the set and len(u->w) + len(w->x) <=
+ * len(u->x) + fuzz.  Bit 1: bit 0 of the complement arc x^1 -> u^1.  An arc is kept iff flags == 0.  A statement about
+ * triangles, independent of any processing order: not Myers' in-play walk, and no promise of connectivity.
+ * Result.
+ *   reads[i]    n_hits: the counted records that name the read on either side, SELF and DROPPED ones left out; n_internal: those
+ *               of class INTERNAL; n_contains: the records in which this read is the container; contained_by; deg[s] / kept[s]:
+ *               the arcs out of vertex 2 i + s, all of them and those with flags == 0
+ *   classes     NULL, or one byte per chosen record (sel[k]; record k when sel == NULL)
+ *   arcs, *n_arcs   arcs_cap too small (or arcs == NULL): GACT_HIP_EINVAL with reads, classes and *n_arcs filled -- call again
+ *               with room for *n_arcs, as with gact_hip_select_overlaps; twice the chosen count always suffices
+ * Synchronous on the slot's stream; the slot's records and every other statistic stay as they were.  Every output is the same on
+ * every call and every slot.  n == 0 (or no chosen record) returns 0 with zeros, contained_by = -1 and *n_arcs = 0; n_reads == 0
+ * returns 0 with *n_arcs = 0.
+ * Refused with GACT_HIP_EINVAL: n < 0 or n > 2^28, n_reads < 0 or > 2^30, n_sel < 0 with sel, NULL read_lens, reads or n_arcs, a
+ * negative length, a clip outside 0 <= cb <= ce <= len, a parameter < 0 or int_permille > 1000, records == NULL on a slot without
+ * records or with n beyond them, an index in sel outside [0, n).  Refused with GACT_HIP_ERANGE: a counted record whose ref_id or
+ * query_id is outside [0, n_reads).  On a refusal reads, classes and arcs are untouched.
+ * Device memory of its own, one allocation per slot, grown on demand and released with the engine: about 140 bytes per chosen
+ * record, 4 bytes per slot of the arc table (a power of two >= four times the chosen count), 64 bytes per read (8 more with a clip); 56 per host
+ * record, 4 per sel entry, 32 per summary.  Known limit: a vertex of out-degree d costs about d^2 look-ups, made by one wave --
+ * right for reads after containment, slow for a repeat hub. */
+#define GACT_GRAPH_NONE             0   /* not counted: not emitted */
+#define GACT_GRAPH_SELF             1
+#define GACT_GRAPH_DROPPED          2
+#define GACT_GRAPH_INTERNAL         3
+#define GACT_GRAPH_QUERY_CONTAINED  4
+#define GACT_GRAPH_TARGET_CONTAINED 5
+#define GACT_GRAPH_SHORT            6
+#define GACT_GRAPH_DOVETAIL         7
+#define GACT_GRAPH_DEFAULT_MAX_HANG     1000
+#define GACT_GRAPH_DEFAULT_INT_PERMILLE 800
+#define GACT_GRAPH_DEFAULT_MIN_OVLP     1000
+#define GACT_GRAPH_DEFAULT_FUZZ         1000
+typedef struct { int32_t max_hang, int_permille, min_ovlp, fuzz; } gact_graph_params;
+typedef struct { int32_t u, v, len, ov_u, ov_v, record, score, flags; } gact_graph_arc;      /* 32 bytes */
+typedef struct { int32_t n_hits, n_internal, n_contains, contained_by, deg[2], kept[2]; } gact_graph_read;  /* 32 bytes */
+int gact_hip_overlap_graph(gact_hip_engine *e, int slot, int32_t n, const gact_overlap *records,
+                           int32_t n_sel, const int32_t *sel, const gact_path_summary *sums,
+                           int32_t n_reads, const int32_t *read_lens, const int32_t *clip,
+                           const gact_graph_params *params /* NULL: the defaults */,
+                           gact_graph_read *reads, uint8_t *classes /* NULL or one per chosen record */,
+                           gact_graph_arc *arcs, int64_t arcs_cap, int64_t *n_arcs);
+/* What the slot's last gact_hip_overlap_graph call that got as far as the device did: HIP events on the slot's stream around the
+ * whole call (copies and kernels), the reads and how many of them are contained, the chosen records per class, the arcs
+ * proposed, the arcs of the set, those with flags != 0 and with flags == 0, the slots of the arc table, and the device memory
+ * the call holds for itself. */
+typedef struct { float device_ms; int32_t reads, contained; int64_t by_class[8], proposed, arcs, transitive, kept,
+                 table_slots, scratch_bytes; } gact_graph_stats;
+int gact_hip_last_graph_stats(gact_hip_engine *e, int slot, gact_graph_stats *stats);
 
 /* Per-base pileup and consensus of the reads of GACT_SET_REF from the overlaps' alignments, counted on the device: every chosen
  * candidate's alignment (the one gact_hip_candidates_paths returns as a CIGAR) is stacked on its target read, every position
