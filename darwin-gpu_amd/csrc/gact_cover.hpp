@@ -177,17 +177,11 @@ int gact_hip_read_coverage(gact_hip_engine *e, int slot, int32_t n, const gact_o
     }
     off[(size_t)n_reads] = positions + n_reads;
     Slot &sl = e->slots[slot];
-    if (n > 0 && !records && (sl.n_cands == 0 || !sl.overlaps.p))
-        return fail(GACT_HIP_EINVAL, "read_coverage: slot %d holds no records (run its candidates first, or pass records)", slot);
-    if (n > 0 && !records && ((size_t)n > sl.n_cands || (size_t)n > sl.overlaps.cap))
-        return fail(GACT_HIP_EINVAL, "read_coverage: n = %d beyond the %zu records of slot %d", n, sl.n_cands, slot);
+    if ((rc = slot_records_check(sl, slot, n, records, "read_coverage"))) return rc;
     if (n_reads == 0) return 0;
     const int32_t n_chosen = n == 0 ? 0 : sel ? n_sel : n;
     if ((rc = set_device(e))) return rc;
-    Slot::CoverBufs &cb = sl.cover;
-    if (!cb.ev0 && (hipEventCreate(&cb.ev0) != hipSuccess || hipEventCreate(&cb.ev1) != hipSuccess))
-        return fail(GACT_HIP_ENOMEM, "read_coverage: device allocation failed");
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    PassScratch<gact_cover_stats> &cb = sl.cover;
     const size_t n_diff = (size_t)positions + (size_t)n_reads;
     const size_t at_sel = records ? up16((size_t)n * sizeof(gact_overlap)) : 0;
     const size_t at_sums = up16(at_sel + (sel ? (size_t)n_chosen * sizeof(int32_t) : 0));
@@ -197,35 +191,19 @@ int gact_hip_read_coverage(gact_hip_engine *e, int slot, int32_t n, const gact_o
     const size_t at_diff = at_flag + 16;
     const size_t at_depth = up16(at_diff + n_diff * sizeof(int32_t));
     const size_t bytes = at_depth + (depth ? (size_t)positions * sizeof(int32_t) : 0);
-    if (bytes > cb.bytes) {
-        if (cb.p) (void)hipFree(cb.p);
-        cb.p = nullptr; cb.bytes = 0;
-        if (hipMalloc((void **)&cb.p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(GACT_HIP_ENOMEM, "read_coverage: device allocation failed (%d reads, %lld positions, %zu bytes)", n_reads,
-                        positions, bytes);
-        }
-        cb.bytes = bytes;
-    }
-    const int *d_sel = sel ? (const int *)(cb.p + at_sel) : nullptr;
-    const gact_path_summary *d_sums = sums ? (const gact_path_summary *)(cb.p + at_sums) : nullptr;
+    if (cb.reserve(bytes))
+        return fail(GACT_HIP_ENOMEM, "read_coverage: device allocation failed (%d reads, %lld positions, %zu bytes)", n_reads,
+                    positions, bytes);
     long long *d_off = (long long *)(cb.p + at_off);
     gact_read_cover *d_cover = (gact_read_cover *)(cb.p + at_cover);
     int *d_flag = (int *)(cb.p + at_flag), *d_diff = (int *)(cb.p + at_diff);
     int *d_depth = depth ? (int *)(cb.p + at_depth) : nullptr;
-    const gact_overlap *d_rec = sl.overlaps.p;
-    cb.stats = gact_cover_stats{};
-    cb.timed = false;
-    HIP_TRY(hipEventRecord(cb.ev0, sl.stream));
-    if (n_chosen > 0) {
-        if (records) {
-            HIP_TRY(hipMemcpyAsync(cb.p, records, (size_t)n * sizeof(gact_overlap), hipMemcpyHostToDevice, sl.stream));
-            d_rec = (const gact_overlap *)cb.p;
-        }
-        if (sel) HIP_TRY(hipMemcpyAsync(cb.p + at_sel, sel, (size_t)n_chosen * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
-        if (sums)
-            HIP_TRY(hipMemcpyAsync(cb.p + at_sums, sums, (size_t)n_chosen * sizeof(gact_path_summary), hipMemcpyHostToDevice, sl.stream));
-    }
+    if ((rc = cb.begin(sl.stream, "read_coverage"))) return rc;
+    DevRecords in;
+    if ((rc = slot_records_stage(sl, cb.p, n, records, n_chosen, sel, at_sel, sums, at_sums, in))) return rc;
+    const gact_overlap *d_rec = in.rec;
+    const int *d_sel = in.sel;
+    const gact_path_summary *d_sums = in.sums;
     HIP_TRY(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(hipMemsetAsync(d_cover, 0, at_diff + n_diff * sizeof(int32_t) - at_cover, sl.stream));
     if (n_chosen > 0)
@@ -247,24 +225,15 @@ int gact_hip_read_coverage(gact_hip_engine *e, int slot, int32_t n, const gact_o
     HIP_TRY(hipMemcpyAsync(cover, d_cover, (size_t)n_reads * sizeof(gact_read_cover), hipMemcpyDeviceToHost, sl.stream));
     if (depth && positions > 0)
         HIP_TRY(hipMemcpyAsync(depth, d_depth, (size_t)positions * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
-    HIP_TRY(hipEventRecord(cb.ev1, sl.stream));
-    HIP_TRY(hipEventSynchronize(cb.ev1));
-    HIP_TRY(hipEventElapsedTime(&cb.stats.device_ms, cb.ev0, cb.ev1));
+    if ((rc = cb.end(sl.stream))) return rc;
     cb.stats.reads = n_reads;
     for (int32_t i = 0; i < n_reads; i++) cb.stats.intervals += cover[i].n_intervals;
     cb.stats.positions = positions;
     cb.stats.scratch_bytes = (int64_t)cb.bytes;
-    cb.timed = true;
     return 0;
 }
 
 int gact_hip_last_cover_stats(gact_hip_engine *e, int slot, gact_cover_stats *stats)
 {
-    int rc = check_slot(e, slot);
-    if (rc) return rc;
-    if (!stats) return fail(GACT_HIP_EINVAL, "last_cover_stats: NULL argument");
-    const Slot &sl = e->slots[slot];
-    if (!sl.cover.timed) return fail(GACT_HIP_EINVAL, "last_cover_stats: slot %d has taken no coverage yet", slot);
-    *stats = sl.cover.stats;
-    return 0;
+    return last_pass_stats(e, slot, &Slot::cover, stats, "last_cover_stats", "has taken no coverage yet");
 }

@@ -122,6 +122,77 @@ template <class T> struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+// The two events around a pass's work on a stream (gact_pass.hpp), made on first use.  The elapsed time is read once per call.
+struct PassTimer {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    int create(const char *who)
+    {
+        if (ev0 || (hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess)) return 0;
+        (void)hipGetLastError();
+        return fail(GACT_HIP_ENOMEM, "%s: device allocation failed", who);
+    }
+    int start(hipStream_t stream, const char *who)
+    {
+        int rc = create(who);
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(ev0, stream));
+        return 0;
+    }
+    int stop(hipStream_t stream, float *ms)
+    {
+        HIP_TRY(hipEventRecord(ev1, stream));
+        HIP_TRY(hipEventSynchronize(ev1));
+        HIP_TRY(hipEventElapsedTime(ms, ev0, ev1));
+        return 0;
+    }
+    void release()
+    {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        ev0 = ev1 = nullptr;
+    }
+};
+
+// What a pass behind a run keeps between its calls (gact_pass.hpp): one allocation that only grows, to exactly what the
+// largest call so far needed, the events around a call, and the figures of the last one (gact_hip_last_*_stats).
+template <class Stats> struct PassScratch {
+    PassTimer timer;
+    uint8_t *p = nullptr;
+    size_t bytes = 0;
+    Stats stats{};
+    bool timed = false;
+    // non-zero: the device refused (the runtime's sticky error is cleared; the caller words the failure)
+    int reserve(size_t want)
+    {
+        if (want <= bytes) return 0;
+        if (p) (void)hipFree(p);
+        p = nullptr; bytes = 0;
+        if (hipMalloc((void **)&p, want) != hipSuccess) { (void)hipGetLastError(); return -1; }
+        bytes = want;
+        return 0;
+    }
+    int begin(hipStream_t stream, const char *who)
+    {
+        stats = Stats{};
+        timed = false;
+        return timer.start(stream, who);
+    }
+    int end(hipStream_t stream)
+    {
+        int rc = timer.stop(stream, &stats.device_ms);
+        timed = rc == 0;
+        return rc;
+    }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        timer.release();
+        p = nullptr; bytes = 0;
+    }
+};
+
+inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
 // The figures of ONE merged launch: events and counters of its own, recorded / copied behind that launch and
 // never touched again, so that a caller that asks for its run's statistics after its fetch reads them whatever the merge
 // slot is doing by then (the slot's own events and counters are re-recorded as soon as its arrays are free).  Records are
@@ -131,6 +202,14 @@ struct LaunchStats {
     int *h_counter = nullptr;            // pinned: 2 x kCounterInts ints (the lane's own, the side lane's)
     bool two_phase = false, wide = false, lin = false, aff = false, overlapped = false, lane = false, side_used = false;
     int routed_raw = 0, roles = 0;
+    void release()
+    {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev_mid) (void)hipEventDestroy(ev_mid);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (ev_done) (void)hipEventDestroy(ev_done);
+        if (h_counter) (void)hipHostFree(h_counter);
+    }
 };
 
 struct Slot {
@@ -208,7 +287,7 @@ struct Slot {
         DevBuf<uint8_t> cols;
         DevBuf<uint32_t> ops;
         int *d_counter = nullptr;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;       // around the whole call (gact_hip_last_paths_stats)
+        PassTimer timer;                               // around the whole call (gact_hip_last_paths_stats)
         gact_paths_stats stats{};
         bool timed = false;
         void release()
@@ -216,94 +295,72 @@ struct Slot {
             cands.release(); records.release(); col_off.release(); op_off.release();
             n_cols.release(); n_ops.release(); cols.release(); ops.release();
             if (d_counter) (void)hipFree(d_counter);
-            if (ev0) (void)hipEventDestroy(ev0);
-            if (ev1) (void)hipEventDestroy(ev1);
-            d_counter = nullptr; ev0 = ev1 = nullptr;
+            timer.release();
+            d_counter = nullptr;
         }
     } path;
-    // gact_hip_candidates_summaries (gact_summary.hpp): one allocation, exactly what the largest selection so far needed
-    struct SummaryBufs {
-        uint8_t *p = nullptr;                          // candidates | records | summaries | pop counter
-        size_t bytes = 0;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;       // around the whole call (gact_hip_last_summaries_stats)
-        gact_summaries_stats stats{};
-        bool timed = false;
-        void release()
-        {
-            if (p) (void)hipFree(p);
-            if (ev0) (void)hipEventDestroy(ev0);
-            if (ev1) (void)hipEventDestroy(ev1);
-            p = nullptr; bytes = 0; ev0 = ev1 = nullptr;
-        }
-    } summary;
-    // gact_hip_select_overlaps (gact_select.hpp): one allocation, grown to what the largest selection so far needed
-    struct SelectBufs {
-        uint8_t *p = nullptr;                          // host records | table | positions | flags | counts | sel
-        size_t bytes = 0;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;       // around the whole call (gact_hip_last_select_stats)
-        gact_select_stats stats{};
-        bool timed = false;
-        void release()
-        {
-            if (p) (void)hipFree(p);
-            if (ev0) (void)hipEventDestroy(ev0);
-            if (ev1) (void)hipEventDestroy(ev1);
-            p = nullptr; bytes = 0; ev0 = ev1 = nullptr;
-        }
-    } select;
-    // gact_hip_read_coverage (gact_cover.hpp): one allocation, grown to what the largest call so far needed
-    struct CoverBufs {
-        uint8_t *p = nullptr;                          // host records | sel | sums | offsets | cover | flag | differences | depth
-        size_t bytes = 0;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;       // around the whole call (gact_hip_last_cover_stats)
-        gact_cover_stats stats{};
-        bool timed = false;
-        void release()
-        {
-            if (p) (void)hipFree(p);
-            if (ev0) (void)hipEventDestroy(ev0);
-            if (ev1) (void)hipEventDestroy(ev1);
-            p = nullptr; bytes = 0; ev0 = ev1 = nullptr;
-        }
-    } cover;
-    // gact_hip_overlap_graph (gact_graph.hpp): one allocation, grown to what the largest call so far needed
-    struct GraphBufs {
-        uint8_t *p = nullptr;                          // host records | sel | sums | lens | clip | read table, degrees, counters | table | proposals | arcs
-        size_t bytes = 0;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;       // around the whole call (gact_hip_last_graph_stats)
-        gact_graph_stats stats{};
-        bool timed = false;
-        void release()
-        {
-            if (p) (void)hipFree(p);
-            if (ev0) (void)hipEventDestroy(ev0);
-            if (ev1) (void)hipEventDestroy(ev1);
-            p = nullptr; bytes = 0; ev0 = ev1 = nullptr;
-        }
-    } graph;
+    // The later passes (gact_pass.hpp), one allocation each:
+    // gact_hip_candidates_summaries (gact_summary.hpp): candidates | records | summaries | pop counter
+    PassScratch<gact_summaries_stats> summary;
+    // gact_hip_select_overlaps (gact_select.hpp): host records | table | positions | flags | counts | sel
+    PassScratch<gact_select_stats> select;
+    // gact_hip_read_coverage (gact_cover.hpp): host records | sel | sums | offsets | cover | flag | differences | depth
+    PassScratch<gact_cover_stats> cover;
+    // gact_hip_overlap_graph (gact_graph.hpp): host records | sel | sums | lens | clip | read table, degrees, counters | table | proposals | arcs
+    PassScratch<gact_graph_stats> graph;
     // gact_hip_pileup_add (gact_pileup.hpp): the events around this slot's adds; the counts are the engine's (Pileup)
-    hipEvent_t pile_ev0 = nullptr, pile_ev1 = nullptr;
+    PassTimer pile_timer;
+
+    // everything above but the stream, which goes back to the process's pool (gact_hip_destroy)
+    void release()
+    {
+        if (stream) (void)hipStreamSynchronize(stream);
+        tiles.release(); results.release(); states.release();
+        cands.release(); overlaps.release(); live.release(); chain_states.release(); deferred.release();
+        inline_ref.release(); inline_query.release();
+        path.release();
+        summary.release();
+        select.release();
+        cover.release();
+        graph.release();
+        pile_timer.release();
+        if (d_counter) (void)hipFree(d_counter);
+        if (d_flags) (void)hipFree(d_flags);
+        if (d_ws) (void)hipFree(d_ws);
+        if (side_stream) (void)hipStreamSynchronize(side_stream);
+        if (aux_stream) {
+            (void)hipStreamSynchronize(aux_stream);
+            (void)hipEventDestroy(aux_ev_a); (void)hipEventDestroy(aux_ev_b);
+            (void)hipStreamDestroy(aux_stream);
+        }
+        order.release();
+        side_live.release();
+        if (side_counter) (void)hipFree(side_counter);
+        if (side_ws) (void)hipFree(side_ws);
+        if (side_done) (void)hipEventDestroy(side_done);
+        if (side_go) (void)hipEventDestroy(side_go);
+        if (side_stream) (void)hipStreamDestroy(side_stream);
+        if (h_stage) (void)hipHostFree(h_stage);
+        if (h_records) (void)hipHostFree(h_records);
+        if (reg_out) { (void)hipHostUnregister(reg_out); (void)hipGetLastError(); }
+        if (ev_ready) (void)hipEventDestroy(ev_ready);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (ev_mid) (void)hipEventDestroy(ev_mid);
+    }
 };
 
 // gact_hip_pileup_* (gact_pileup.hpp): the open window of GACT_SET_REF and its counts, one allocation of the engine's
 struct Pileup {
-    uint8_t *p = nullptr;                 // counts (32 per position) | consensus (1 per position) | read table | alignments per read | state
-    size_t bytes = 0;
+    PassScratch<gact_pileup_stats> scratch;       // p: counts (32 per position) | consensus (1 per position) | read table | alignments per read | state;
+                                                  // the events around finish's own work; stats under mu: adds come from several threads
+    std::mutex mu;
     bool open = false;
     int32_t read_first = 0, n_reads = 0;
     int64_t base = 0, positions = 0;      // the window's first base in the set's concatenation, its bases
     size_t at_cons = 0, at_reads = 0, at_aln = 0, at_state = 0;       // where the parts of p begin
     int64_t ref_epoch = -1;               // gact_hip_engine::ref_epoch at begin: the window describes that upload of GACT_SET_REF
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;      // around begin's and finish's own work
-    std::mutex mu;                        // the statistics: adds come from several threads
-    gact_pileup_stats stats{};
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        p = nullptr; bytes = 0; ev0 = ev1 = nullptr; open = false;
-    }
+    void release() { scratch.release(); open = false; }
 };
 
 // device-side D-SOFT filter (dsoft_device.hpp)
@@ -1473,53 +1530,14 @@ void gact_hip_destroy(gact_hip_engine *e)
         fprintf(stderr, "[gact_hip] combiner: %ld merged launches carried %ld runs, %ld times a group that had come apart was joined again\n", e->cb.merged_launches, e->cb.merged_runs, e->cb.rejoins);
     (void)hipSetDevice(e->params.device_id);
     for (auto &sl : e->slots) {
-        if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-        sl.tiles.release(); sl.results.release(); sl.states.release();
-        sl.cands.release(); sl.overlaps.release(); sl.live.release(); sl.chain_states.release(); sl.deferred.release();
-        sl.inline_ref.release(); sl.inline_query.release();
-        sl.path.release();
-        sl.summary.release();
-        sl.select.release();
-        sl.cover.release();
-        sl.graph.release();
-        if (sl.pile_ev0) (void)hipEventDestroy(sl.pile_ev0);
-        if (sl.pile_ev1) (void)hipEventDestroy(sl.pile_ev1);
-        if (sl.d_counter) (void)hipFree(sl.d_counter);
-        if (sl.d_flags) (void)hipFree(sl.d_flags);
-        if (sl.d_ws) (void)hipFree(sl.d_ws);
-        if (sl.side_stream) (void)hipStreamSynchronize(sl.side_stream);
-        if (sl.aux_stream) {
-            (void)hipStreamSynchronize(sl.aux_stream);
-            (void)hipEventDestroy(sl.aux_ev_a); (void)hipEventDestroy(sl.aux_ev_b);
-            (void)hipStreamDestroy(sl.aux_stream);
-        }
-        sl.order.release();
-        sl.side_live.release();
-        if (sl.side_counter) (void)hipFree(sl.side_counter);
-        if (sl.side_ws) (void)hipFree(sl.side_ws);
-        if (sl.side_done) (void)hipEventDestroy(sl.side_done);
-        if (sl.side_go) (void)hipEventDestroy(sl.side_go);
-        if (sl.side_stream) (void)hipStreamDestroy(sl.side_stream);
-        if (sl.h_stage) (void)hipHostFree(sl.h_stage);
-        if (sl.h_records) (void)hipHostFree(sl.h_records);
-        if (sl.reg_out) { (void)hipHostUnregister(sl.reg_out); (void)hipGetLastError(); }
-        if (sl.ev_ready) (void)hipEventDestroy(sl.ev_ready);
-        if (sl.ev0) (void)hipEventDestroy(sl.ev0);
-        if (sl.ev1) (void)hipEventDestroy(sl.ev1);
-        if (sl.ev_mid) (void)hipEventDestroy(sl.ev_mid);
+        sl.release();
         if (sl.stream) {
             if (sl.stream_index >= 0) { (void)hipStreamSynchronize(sl.stream); g_streams.give(e->params.device_id, sl.stream_index, sl.stream); }
             else (void)hipStreamDestroy(sl.stream);
         }
     }
     for (Slot &sl : e->slots) sl.merged_stats.reset();
-    for (auto &r : e->cb.stats_pool) {
-        if (r->ev0) (void)hipEventDestroy(r->ev0);
-        if (r->ev_mid) (void)hipEventDestroy(r->ev_mid);
-        if (r->ev1) (void)hipEventDestroy(r->ev1);
-        if (r->ev_done) (void)hipEventDestroy(r->ev_done);
-        if (r->h_counter) (void)hipHostFree(r->h_counter);
-    }
+    for (auto &r : e->cb.stats_pool) r->release();
     e->cb.stats_pool.clear();
     for (auto &s : e->sets) s.release();
     e->pileup.release();
@@ -2129,292 +2147,6 @@ int gact_hip_extend_candidates(gact_hip_engine *e, int slot, int32_t n, const ga
     return gact_hip_candidates_fetch(e, slot, n, out);
 }
 
-// The selection of a path run or a summary run (`who` names the entry in the refusals): the selected candidates as the host
-// sees them (its copy of an uploaded list, else the device filter's list copied back), each tagged with its strand
-// (kCompInCand, as a merged run does), the reads' lengths, and the read sets the chains are to read.
-struct Selection {
-    std::vector<gact_candidate> tagged;
-    std::vector<int64_t> cap;                 // ref_len + query_len of each: every column consumes a base of one of the two reads
-    gact::SeqSetDev d_rs, d_qf, d_qr;
-};
-static int select_candidates(gact_hip_engine *e, int slot, int32_t n_sel, const int32_t *sel, int32_t rc_from, const char *who,
-                             Selection &sn)
-{
-    int rc;
-    Slot &sl = e->slots[slot];
-    if (sl.n_cands == 0)
-        return fail(GACT_HIP_EINVAL, "%s: slot %d holds no candidates (upload a list or run the device filter first)", who, slot);
-    for (int32_t k = 0; k < n_sel; k++) {
-        const int64_t idx = sel ? sel[k] : k;
-        if (idx < 0 || (size_t)idx >= sl.n_cands)
-            return fail(GACT_HIP_EINVAL, "%s: sel[%d] = %lld outside the %zu candidates of slot %d", who, k, (long long)idx,
-                        sl.n_cands, slot);
-    }
-    if ((rc = set_device(e))) return rc;
-    const SeqSet &rs = e->sets[GACT_SET_REF];
-    const SeqSet &qf = e->sets[GACT_SET_QUERY], &qr = e->sets[GACT_SET_QUERY_RC];
-    // the candidates as the host sees them
-    std::vector<gact_candidate> downloaded;
-    const gact_candidate *hc = sl.h_cands.data();
-    if (sl.h_cands.empty()) {
-        if (sl.cands_epoch != e->sets_epoch)
-            return fail(GACT_HIP_EINVAL, "%s: a read set was uploaded after the device filter made this slot's "
-                                         "candidates; run gact_hip_dsoft_query again", who);
-        downloaded.resize(sl.n_cands);
-        HIP_TRY(hipMemcpyAsync(downloaded.data(), sl.cands.p, sl.n_cands * sizeof(gact_candidate), hipMemcpyDeviceToHost, sl.stream));
-        HIP_TRY(hipStreamSynchronize(sl.stream));
-        hc = downloaded.data();
-    }
-    // strands, lengths, checks
-    sn.tagged.resize((size_t)n_sel);
-    sn.cap.resize((size_t)n_sel);
-    bool need_f = false, need_r = false;
-    for (int32_t k = 0; k < n_sel; k++) {
-        const int32_t idx = sel ? sel[k] : k;
-        gact_candidate c = hc[idx];
-        const bool comp = idx >= rc_from;
-        const SeqSet &qs = comp ? qr : qf;
-        (comp ? need_r : need_f) = true;
-        if (rs.n == 0 || qs.n == 0) return fail(GACT_HIP_EINVAL, "%s: read sets not uploaded", who);
-        if (c.ref_id < 0 || c.ref_id >= rs.n || c.query_id < 0 || c.query_id >= qs.n)
-            return fail(GACT_HIP_ERANGE, "candidate %d: sequence id out of range", idx);
-        const int64_t rl = rs.h_offsets[c.ref_id + 1] - rs.h_offsets[c.ref_id];
-        const int64_t ql = qs.h_offsets[c.query_id + 1] - qs.h_offsets[c.query_id];
-        if (c.ref_pos < 0 || c.ref_pos > rl || c.query_pos < 0 || c.query_pos > ql)
-            return fail(GACT_HIP_ERANGE, "candidate %d: position outside its read", idx);
-        if (comp) c.query_id |= gact::kCompBit;
-        sn.tagged[(size_t)k] = c;
-        sn.cap[(size_t)k] = rl + ql;
-    }
-    const bool raw = rs.has_other || (need_f && qf.has_other) || (need_r && qr.has_other);
-    sn.d_rs = rs.dev(raw); sn.d_qf = qf.dev_or(raw, rs); sn.d_qr = qr.dev_or(raw, rs);
-    return 0;
-}
-
-// the path run's pop counter and events, made on the slot's first path run or pileup add
-static int path_bufs_init(Slot::PathBufs &pb, const char *who)
-{
-    if (!pb.d_counter && (hipMalloc((void **)&pb.d_counter, sizeof(int)) != hipSuccess || hipEventCreate(&pb.ev0) != hipSuccess ||
-                          hipEventCreate(&pb.ev1) != hipSuccess))
-        return fail(GACT_HIP_ENOMEM, "%s: device allocation failed", who);
-    return 0;
-}
-
-// where the chunk of a path run that starts at candidate `first` ends: as many candidates as the budget's column bytes hold,
-// at least one; bytes: their column bytes
-static int32_t path_chunk_end(const gact_hip_engine *e, const std::vector<int64_t> &cap, int32_t first, int32_t n_sel, int64_t &bytes)
-{
-    int32_t end = first;
-    bytes = 0;
-    while (end < n_sel && (end == first || bytes + cap[(size_t)end] <= e->path_budget)) bytes += cap[(size_t)end++];
-    return end;
-}
-
-// One launch of chain_kernel for a second pass over a selection (the path run's chunks, the summary run): candidates
-// d_cands[0, n), tagged with their strands, popped through *d_counter (zeroed by the caller) into the sink.
-extern "C++" {                  // (a template: not in this file's extern "C")
-template <class Sink>
-static int launch_chain_kernel(gact_hip_engine *e, Slot &sl, const Selection &sn, const gact_candidate *d_cands, int n, int same_file,
-                               gact_overlap *d_records, int *d_counter, Sink sink)
-{
-    gact::ChainQueues q{};
-    q.pop_seed = d_counter;
-    q.list_n = -1;
-    const int groups_per_block = (gact::kBlockThreads / 64) * gact::kGroupsPerWave;
-    // (the slot's workspace is sized for grid_blocks blocks of the chain kernels)
-    const int blocks = std::max(1, std::min((n + groups_per_block - 1) / groups_per_block, e->grid_blocks));
-    auto k = e->C == 20 ? gact::chain_kernel<20, Sink> : gact::chain_kernel<32, Sink>;
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, sn.d_rs, sn.d_qf, sn.d_qr, d_cands, n,
-                       gact::kCompInCand, same_file, d_records, q, sink, sl.d_ws);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-}
-
-// One chunk of a path run (gact_hip_candidates_paths, gact_hip_pileup_add): candidates [first, end) of the selection, as many
-// as the budget's column bytes hold (at least one), their tagged copies, column offsets and zeroed column counts on the
-// device, and chain_kernel with a ColumnSink behind them on the slot's stream.  pb.d_counter is the caller's to have made.
-static int launch_path_chunk(gact_hip_engine *e, Slot &sl, const Selection &sn, int32_t first, int32_t n_sel, int same_file,
-                             const char *who, std::vector<int64_t> &col_off, int32_t &end, int64_t &bytes)
-{
-    Slot::PathBufs &pb = sl.path;
-    const std::vector<int64_t> &cap = sn.cap;
-    end = path_chunk_end(e, cap, first, n_sel, bytes);
-    const int32_t n = end - first;
-    col_off.assign((size_t)n + 1, 0);
-    for (int32_t k = 0; k < n; k++) col_off[(size_t)k + 1] = col_off[(size_t)k] + cap[(size_t)(first + k)];
-    if (pb.cands.reserve((size_t)n) || pb.records.reserve((size_t)n) || pb.col_off.reserve((size_t)n + 1) ||
-        pb.op_off.reserve((size_t)n) || pb.n_cols.reserve(2 * (size_t)n) || pb.n_ops.reserve((size_t)n) ||
-        pb.cols.reserve((size_t)bytes + 64))
-        return fail(GACT_HIP_ENOMEM, "%s: device allocation failed (%d candidates, %lld column bytes)", who, n, (long long)bytes);
-    HIP_TRY(hipMemcpyAsync(pb.cands.p, sn.tagged.data() + first, (size_t)n * sizeof(gact_candidate), hipMemcpyHostToDevice, sl.stream));
-    HIP_TRY(hipMemcpyAsync(pb.col_off.p, col_off.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, sl.stream));
-    HIP_TRY(hipMemsetAsync(pb.n_cols.p, 0, 2 * (size_t)n * sizeof(int32_t), sl.stream));
-    HIP_TRY(hipMemsetAsync(pb.d_counter, 0, sizeof(int), sl.stream));
-    return launch_chain_kernel(e, sl, sn, pb.cands.p, n, same_file, pb.records.p, pb.d_counter,
-                               gact::ColumnSink{{pb.cols.p, pb.col_off.p, pb.n_cols.p}});
-}
-
-// The path run (gact_path.hpp).  The host takes the selected candidates (its copy of an uploaded list, else the device
-// filter's list copied back), tags each with its strand (kCompInCand, as a merged run does), and cuts the selection into
-// chunks whose column buffers fit the budget; per chunk: the chain kernel, the op count, the counts back, the scan on the host,
-// the op write, the ops back.
-int gact_hip_candidates_paths(gact_hip_engine *e, int slot, int32_t n_sel, const int32_t *sel, int32_t rc_from,
-                              int same_file, gact_overlap *records, gact_path *paths,
-                              uint32_t *ops, int64_t ops_cap, int64_t *ops_needed)
-{
-    int rc = check_slot(e, slot);
-    if (rc) return rc;
-    if (n_sel < 0 || (n_sel > 0 && (!records || !paths)) || ops_cap < 0)
-        return fail(GACT_HIP_EINVAL, "candidates_paths: bad arguments");
-    if (e->big_cb)
-        return fail(GACT_HIP_EINVAL, "candidates_paths: tile_size %d > GACT_HIP_FAST_TILE (%d): paths come from the register-tiled "
-                                     "int32 chain kernel, which the tiles of gact_big.hpp do not run on", e->params.tile_size,
-                    GACT_HIP_FAST_TILE);
-    Slot &sl = e->slots[slot];
-    if (ops_needed) *ops_needed = 0;
-    if (n_sel == 0) return 0;                 // (nothing asked for: also on a slot without candidates, e.g. a feeder with no reads)
-    Selection sn;
-    if ((rc = select_candidates(e, slot, n_sel, sel, rc_from, "candidates_paths", sn))) return rc;
-    Slot::PathBufs &pb = sl.path;
-    if ((rc = path_bufs_init(pb, "candidates_paths"))) return rc;
-    pb.stats = gact_paths_stats{};
-    pb.timed = false;
-    HIP_TRY(hipEventRecord(pb.ev0, sl.stream));
-    int64_t total_ops = 0;
-    bool room = ops != nullptr;
-    std::vector<int64_t> col_off, op_off;
-    std::vector<int32_t> n_cols, n_ops;
-    for (int32_t first = 0; first < n_sel;) {
-        int32_t end = first;
-        int64_t bytes = 0;
-        if ((rc = launch_path_chunk(e, sl, sn, first, n_sel, same_file, "candidates_paths", col_off, end, bytes))) return rc;
-        const int32_t n = end - first;
-        const int op_blocks = std::max(1, std::min((n + 3) / 4, 4096));
-        hipLaunchKernelGGL(gact::path_ops_kernel<false>, dim3(op_blocks), dim3(256), 0, sl.stream, pb.cols.p, pb.col_off.p, pb.n_cols.p,
-                           n, pb.n_ops.p, nullptr, nullptr);
-        HIP_TRY(hipGetLastError());
-        n_cols.resize(2 * (size_t)n);
-        n_ops.resize((size_t)n);
-        HIP_TRY(hipMemcpyAsync(records + first, pb.records.p, (size_t)n * sizeof(gact_overlap), hipMemcpyDeviceToHost, sl.stream));
-        HIP_TRY(hipMemcpyAsync(n_cols.data(), pb.n_cols.p, 2 * (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
-        HIP_TRY(hipMemcpyAsync(n_ops.data(), pb.n_ops.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
-        HIP_TRY(hipStreamSynchronize(sl.stream));
-        // ---- the exclusive scan of the counts, and the ops themselves where the caller has room for them
-        op_off.resize((size_t)n);
-        int64_t chunk_ops = 0;
-        for (int32_t k = 0; k < n; k++) {
-            op_off[(size_t)k] = chunk_ops;
-            gact_path &p = paths[first + k];
-            p.op_offset = total_ops + chunk_ops;
-            p.n_ops = n_ops[(size_t)k];
-            p.n_columns = n_cols[2 * (size_t)k] + n_cols[2 * (size_t)k + 1];
-            chunk_ops += n_ops[(size_t)k];
-        }
-        room = room && total_ops + chunk_ops <= ops_cap;
-        if (room && chunk_ops > 0) {
-            if (pb.ops.reserve((size_t)chunk_ops)) return fail(GACT_HIP_ENOMEM, "candidates_paths: device allocation failed (%lld ops)", (long long)chunk_ops);
-            HIP_TRY(hipMemcpyAsync(pb.op_off.p, op_off.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, sl.stream));
-            hipLaunchKernelGGL(gact::path_ops_kernel<true>, dim3(op_blocks), dim3(256), 0, sl.stream, pb.cols.p, pb.col_off.p, pb.n_cols.p,
-                               n, nullptr, pb.op_off.p, pb.ops.p);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(ops + total_ops, pb.ops.p, (size_t)chunk_ops * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
-            HIP_TRY(hipStreamSynchronize(sl.stream));
-        }
-        total_ops += chunk_ops;
-        first = end;
-        pb.stats.chunks++;
-        pb.stats.column_bytes = std::max(pb.stats.column_bytes, bytes);
-        for (int32_t k = 0; k < n; k++) pb.stats.columns += n_cols[2 * (size_t)k] + n_cols[2 * (size_t)k + 1];
-    }
-    HIP_TRY(hipEventRecord(pb.ev1, sl.stream));
-    HIP_TRY(hipEventSynchronize(pb.ev1));
-    HIP_TRY(hipEventElapsedTime(&pb.stats.device_ms, pb.ev0, pb.ev1));
-    pb.stats.ops = total_ops;
-    pb.timed = true;
-    if (ops_needed) *ops_needed = total_ops;
-    if (!room && total_ops > 0)
-        return fail(GACT_HIP_EINVAL, "candidates_paths: the ops need room for %lld words, ops_cap is %lld", (long long)total_ops,
-                    (long long)ops_cap);
-    return 0;
-}
-
-int gact_hip_last_paths_stats(gact_hip_engine *e, int slot, gact_paths_stats *stats)
-{
-    int rc = check_slot(e, slot);
-    if (rc) return rc;
-    if (!stats) return fail(GACT_HIP_EINVAL, "last_paths_stats: NULL argument");
-    const Slot &sl = e->slots[slot];
-    if (!sl.path.timed) return fail(GACT_HIP_EINVAL, "last_paths_stats: slot %d has made no path run yet", slot);
-    *stats = sl.path.stats;
-    return 0;
-}
-
-// The summary run (gact_summary.hpp): the same selection, one chain_kernel launch (CountSink) over all of it, records and summaries back.
-int gact_hip_candidates_summaries(gact_hip_engine *e, int slot, int32_t n_sel, const int32_t *sel, int32_t rc_from,
-                                  int same_file, gact_overlap *records, gact_path_summary *sums)
-{
-    int rc = check_slot(e, slot);
-    if (rc) return rc;
-    if (n_sel < 0 || (n_sel > 0 && (!records || !sums)))
-        return fail(GACT_HIP_EINVAL, "candidates_summaries: bad arguments");
-    if (e->big_cb)
-        return fail(GACT_HIP_EINVAL, "candidates_summaries: tile_size %d > GACT_HIP_FAST_TILE (%d): summaries come from the "
-                                     "register-tiled int32 chain kernel, which the tiles of gact_big.hpp do not run on",
-                    e->params.tile_size, GACT_HIP_FAST_TILE);
-    Slot &sl = e->slots[slot];
-    if (n_sel == 0) return 0;                 // (as gact_hip_candidates_paths)
-    Selection sn;
-    if ((rc = select_candidates(e, slot, n_sel, sel, rc_from, "candidates_summaries", sn))) return rc;
-    Slot::SummaryBufs &sb = sl.summary;
-    if (!sb.ev0 && (hipEventCreate(&sb.ev0) != hipSuccess || hipEventCreate(&sb.ev1) != hipSuccess))
-        return fail(GACT_HIP_ENOMEM, "candidates_summaries: device allocation failed");
-    // candidates | records | summaries | pop counter: 16 + 56 + 32 bytes per candidate, each array 16-byte aligned
-    const size_t n = (size_t)n_sel;
-    const size_t at_records = n * sizeof(gact_candidate);
-    const size_t at_sums = (at_records + n * sizeof(gact_overlap) + 15) & ~(size_t)15;
-    const size_t at_counter = at_sums + n * sizeof(gact_path_summary);
-    const size_t bytes = at_counter + 16;
-    if (bytes > sb.bytes) {
-        if (sb.p) (void)hipFree(sb.p);
-        sb.p = nullptr; sb.bytes = 0;
-        if (hipMalloc((void **)&sb.p, bytes) != hipSuccess)
-            return fail(GACT_HIP_ENOMEM, "candidates_summaries: device allocation failed (%d candidates, %zu bytes)", n_sel, bytes);
-        sb.bytes = bytes;
-    }
-    gact_candidate *d_cands = (gact_candidate *)sb.p;
-    gact_overlap *d_records = (gact_overlap *)(sb.p + at_records);
-    gact_path_summary *d_sums = (gact_path_summary *)(sb.p + at_sums);
-    int *d_counter = (int *)(sb.p + at_counter);
-    sb.stats = gact_summaries_stats{};
-    sb.timed = false;
-    HIP_TRY(hipEventRecord(sb.ev0, sl.stream));
-    HIP_TRY(hipMemcpyAsync(d_cands, sn.tagged.data(), n * sizeof(gact_candidate), hipMemcpyHostToDevice, sl.stream));
-    // (a chain with no tile over the threshold never walks: its summary stays zero; the counter starts at zero)
-    HIP_TRY(hipMemsetAsync(d_sums, 0, n * sizeof(gact_path_summary) + 16, sl.stream));
-    if ((rc = launch_chain_kernel(e, sl, sn, d_cands, n_sel, same_file, d_records, d_counter, gact::CountSink{d_sums}))) return rc;
-    HIP_TRY(hipMemcpyAsync(records, d_records, n * sizeof(gact_overlap), hipMemcpyDeviceToHost, sl.stream));
-    HIP_TRY(hipMemcpyAsync(sums, d_sums, n * sizeof(gact_path_summary), hipMemcpyDeviceToHost, sl.stream));
-    HIP_TRY(hipEventRecord(sb.ev1, sl.stream));
-    HIP_TRY(hipEventSynchronize(sb.ev1));
-    HIP_TRY(hipEventElapsedTime(&sb.stats.device_ms, sb.ev0, sb.ev1));
-    sb.stats.launches = 1;
-    sb.stats.scratch_bytes = (int64_t)sb.bytes;
-    sb.timed = true;
-    return 0;
-}
-
-int gact_hip_last_summaries_stats(gact_hip_engine *e, int slot, gact_summaries_stats *stats)
-{
-    int rc = check_slot(e, slot);
-    if (rc) return rc;
-    if (!stats) return fail(GACT_HIP_EINVAL, "last_summaries_stats: NULL argument");
-    const Slot &sl = e->slots[slot];
-    if (!sl.summary.timed) return fail(GACT_HIP_EINVAL, "last_summaries_stats: slot %d has made no summary run yet", slot);
-    *stats = sl.summary.stats;
-    return 0;
-}
-
 int gact_hip_sync(gact_hip_engine *e, int slot)
 {
     int rc = check_slot(e, slot);
@@ -2736,6 +2468,8 @@ int gact_hip_measure_valu_rate(gact_hip_engine *e, double *lane_ops_per_s)
 
 #include "dsoft_engine.hpp"      // gact_hip_dsoft_build / _query / candidates_download
 #include "gact_gather.hpp"       // gact_hip_comm_*: the RCCL gather of a sharded job
+#include "gact_pass.hpp"         // what the passes below share: their selection, records, refusals and last_*_stats
+#include "gact_path_run.hpp"     // gact_hip_candidates_paths / _summaries: the alignments again, as CIGARs or as counts
 #include "gact_select.hpp"       // gact_hip_select_overlaps: one overlap per class, behind every other kernel
 #include "gact_cover.hpp"        // gact_hip_read_coverage: per-read coverage of an overlap set, behind those
 #include "gact_graph.hpp"        // gact_hip_overlap_graph: containment, dovetail arcs and their transitive flags, behind those

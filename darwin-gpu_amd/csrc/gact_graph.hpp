@@ -360,17 +360,11 @@ int gact_hip_overlap_graph(gact_hip_engine *e, int slot, int32_t n, const gact_o
                         clip[2 * (size_t)i + 1], i, read_lens[i]);
     }
     Slot &sl = e->slots[slot];
-    if (n > 0 && !records && (sl.n_cands == 0 || !sl.overlaps.p))
-        return fail(GACT_HIP_EINVAL, "overlap_graph: slot %d holds no records (run its candidates first, or pass records)", slot);
-    if (n > 0 && !records && ((size_t)n > sl.n_cands || (size_t)n > sl.overlaps.cap))
-        return fail(GACT_HIP_EINVAL, "overlap_graph: n = %d beyond the %zu records of slot %d", n, sl.n_cands, slot);
+    if ((rc = slot_records_check(sl, slot, n, records, "overlap_graph"))) return rc;
     if (n_reads == 0) return 0;
     const int32_t n_chosen = n == 0 ? 0 : sel ? n_sel : n;
     if ((rc = set_device(e))) return rc;
-    Slot::GraphBufs &gb = sl.graph;
-    if (!gb.ev0 && (hipEventCreate(&gb.ev0) != hipSuccess || hipEventCreate(&gb.ev1) != hipSuccess))
-        return fail(GACT_HIP_ENOMEM, "overlap_graph: device allocation failed");
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    PassScratch<gact_graph_stats> &gb = sl.graph;
     const size_t nv = 2 * (size_t)n_reads, n_props = 2 * (size_t)n_chosen;
     size_t slots = 2;
     while (slots < 2 * n_props) slots <<= 1;
@@ -391,17 +385,8 @@ int gact_hip_overlap_graph(gact_hip_engine *e, int slot, int32_t n, const gact_o
     const size_t at_csr = at_props + n_props * sizeof(gact_graph_arc);
     const size_t at_arcs = up16(at_csr + n_props * sizeof(int));
     const size_t bytes = at_arcs + n_props * sizeof(gact_graph_arc);
-    if (bytes > gb.bytes) {
-        if (gb.p) (void)hipFree(gb.p);
-        gb.p = nullptr; gb.bytes = 0;
-        if (hipMalloc((void **)&gb.p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(GACT_HIP_ENOMEM, "overlap_graph: device allocation failed (%d reads, %d records, %zu bytes)", n_reads, n_chosen, bytes);
-        }
-        gb.bytes = bytes;
-    }
-    const int *d_sel = sel ? (const int *)(gb.p + at_sel) : nullptr;
-    const gact_path_summary *d_sums = sums ? (const gact_path_summary *)(gb.p + at_sums) : nullptr;
+    if (gb.reserve(bytes))
+        return fail(GACT_HIP_ENOMEM, "overlap_graph: device allocation failed (%d reads, %d records, %zu bytes)", n_reads, n_chosen, bytes);
     int *d_lens = (int *)(gb.p + at_lens);
     const int *d_clip = clip ? (const int *)(gb.p + at_clip) : nullptr;
     gact_graph_read *d_reads = (gact_graph_read *)(gb.p + at_reads);
@@ -411,19 +396,12 @@ int gact_hip_overlap_graph(gact_hip_engine *e, int slot, int32_t n, const gact_o
     unsigned *d_cby = (unsigned *)(gb.p + at_cby);
     uint8_t *d_classes = gb.p + at_classes;
     gact_graph_arc *d_props = (gact_graph_arc *)(gb.p + at_props), *d_arcs = (gact_graph_arc *)(gb.p + at_arcs);
-    const gact_overlap *d_rec = sl.overlaps.p;
-    gb.stats = gact_graph_stats{};
-    gb.timed = false;
-    HIP_TRY(hipEventRecord(gb.ev0, sl.stream));
-    if (n_chosen > 0) {
-        if (records) {
-            HIP_TRY(hipMemcpyAsync(gb.p, records, (size_t)n * sizeof(gact_overlap), hipMemcpyHostToDevice, sl.stream));
-            d_rec = (const gact_overlap *)gb.p;
-        }
-        if (sel) HIP_TRY(hipMemcpyAsync(gb.p + at_sel, sel, (size_t)n_chosen * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
-        if (sums)
-            HIP_TRY(hipMemcpyAsync(gb.p + at_sums, sums, (size_t)n_chosen * sizeof(gact_path_summary), hipMemcpyHostToDevice, sl.stream));
-    }
+    if ((rc = gb.begin(sl.stream, "overlap_graph"))) return rc;
+    DevRecords in;
+    if ((rc = slot_records_stage(sl, gb.p, n, records, n_chosen, sel, at_sel, sums, at_sums, in))) return rc;
+    const gact_overlap *d_rec = in.rec;
+    const int *d_sel = in.sel;
+    const gact_path_summary *d_sums = in.sums;
     HIP_TRY(hipMemcpyAsync(d_lens, read_lens, (size_t)n_reads * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
     if (clip) HIP_TRY(hipMemcpyAsync(gb.p + at_clip, clip, nv * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(hipMemsetAsync(d_reads, 0, at_first - at_reads, sl.stream));
@@ -472,9 +450,7 @@ int gact_hip_overlap_graph(gact_hip_engine *e, int slot, int32_t n, const gact_o
     const bool room = total == 0 || (arcs && arcs_cap >= total);
     if (room && total > 0)
         HIP_TRY(hipMemcpyAsync(arcs, d_arcs, (size_t)total * sizeof(gact_graph_arc), hipMemcpyDeviceToHost, sl.stream));
-    HIP_TRY(hipEventRecord(gb.ev1, sl.stream));
-    HIP_TRY(hipEventSynchronize(gb.ev1));
-    HIP_TRY(hipEventElapsedTime(&gb.stats.device_ms, gb.ev0, gb.ev1));
+    if ((rc = gb.end(sl.stream))) return rc;
     gb.stats.reads = n_reads;
     gb.stats.contained = (int32_t)counters[gact::kGraphContained];
     for (int c = 0; c < 8; c++) gb.stats.by_class[c] = (int64_t)counters[c];
@@ -484,7 +460,6 @@ int gact_hip_overlap_graph(gact_hip_engine *e, int slot, int32_t n, const gact_o
     gb.stats.transitive = total - gb.stats.kept;
     gb.stats.table_slots = (int64_t)slots;
     gb.stats.scratch_bytes = (int64_t)gb.bytes;
-    gb.timed = true;
     if (!room)
         return fail(GACT_HIP_EINVAL, "overlap_graph: %d arcs, room for %lld: call again with room for *n_arcs", total,
                     arcs ? (long long)arcs_cap : 0ll);
@@ -493,11 +468,5 @@ int gact_hip_overlap_graph(gact_hip_engine *e, int slot, int32_t n, const gact_o
 
 int gact_hip_last_graph_stats(gact_hip_engine *e, int slot, gact_graph_stats *stats)
 {
-    int rc = check_slot(e, slot);
-    if (rc) return rc;
-    if (!stats) return fail(GACT_HIP_EINVAL, "last_graph_stats: NULL argument");
-    const Slot &sl = e->slots[slot];
-    if (!sl.graph.timed) return fail(GACT_HIP_EINVAL, "last_graph_stats: slot %d has made no overlap graph yet", slot);
-    *stats = sl.graph.stats;
-    return 0;
+    return last_pass_stats(e, slot, &Slot::graph, stats, "last_graph_stats", "has made no overlap graph yet");
 }

@@ -206,10 +206,7 @@ pileup_reads_kernel(const uint32_t *__restrict__ counts, const uint8_t *__restri
 
 static int pileup_refuse_big_tiles(gact_hip_engine *e, const char *who)
 {
-    if (!e->big_cb) return 0;
-    return fail(GACT_HIP_EINVAL, "%s: tile_size %d > GACT_HIP_FAST_TILE (%d): the pileup counts the path run's columns, which come "
-                                 "from the register-tiled int32 chain kernel, which the tiles of gact_big.hpp do not run on", who,
-                e->params.tile_size, GACT_HIP_FAST_TILE);
+    return refuse_big_tiles(e, who, "the pileup counts the path run's columns, which come from");
 }
 
 // One allocation: counts (32 positions) | consensus (positions) | read table (32 n_reads) | alignments per read (4 n_reads) |
@@ -227,9 +224,8 @@ int gact_hip_pileup_begin(gact_hip_engine *e, int32_t read_first, int32_t n_read
         return fail(GACT_HIP_EINVAL, "pileup_begin: the window [%d, %lld) lies outside the %d reads of GACT_SET_REF", read_first,
                     (long long)read_first + n_reads, rs.n);
     if ((rc = set_device(e))) return rc;
-    if (!pl.ev0 && (hipEventCreate(&pl.ev0) != hipSuccess || hipEventCreate(&pl.ev1) != hipSuccess))
-        return fail(GACT_HIP_ENOMEM, "pileup_begin: device allocation failed");
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    PassScratch<gact_pileup_stats> &ps = pl.scratch;
+    if ((rc = ps.timer.create("pileup_begin"))) return rc;
     const int64_t base = rs.h_offsets[(size_t)read_first];
     const int64_t positions = rs.h_offsets[(size_t)read_first + (size_t)n_reads] - base;
     const size_t at_cons = (size_t)positions * sizeof(gact_pileup_col);
@@ -237,19 +233,12 @@ int gact_hip_pileup_begin(gact_hip_engine *e, int32_t read_first, int32_t n_read
     const size_t at_aln = at_reads + (size_t)n_reads * sizeof(gact_read_pileup);
     const size_t at_state = up16(at_aln + (size_t)n_reads * sizeof(int32_t));
     const size_t bytes = at_state + sizeof(gact::PileupState);
-    if (bytes > pl.bytes) {
-        if (pl.p) (void)hipFree(pl.p);
-        pl.p = nullptr; pl.bytes = 0;
-        if (hipMalloc((void **)&pl.p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(GACT_HIP_ENOMEM, "pileup_begin: device allocation failed (%d reads, %lld positions, %zu bytes)", n_reads,
-                        (long long)positions, bytes);
-        }
-        pl.bytes = bytes;
-    }
+    if (ps.reserve(bytes))
+        return fail(GACT_HIP_ENOMEM, "pileup_begin: device allocation failed (%d reads, %lld positions, %zu bytes)", n_reads,
+                    (long long)positions, bytes);
     hipStream_t stream = e->slots[0].stream;
-    if (at_cons) HIP_TRY(hipMemsetAsync(pl.p, 0, at_cons, stream));
-    HIP_TRY(hipMemsetAsync(pl.p + at_reads, 0, bytes - at_reads, stream));
+    if (at_cons) HIP_TRY(hipMemsetAsync(ps.p, 0, at_cons, stream));
+    HIP_TRY(hipMemsetAsync(ps.p + at_reads, 0, bytes - at_reads, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     pl.at_cons = at_cons; pl.at_reads = at_reads; pl.at_aln = at_aln; pl.at_state = at_state;
     pl.read_first = read_first; pl.n_reads = n_reads;
@@ -257,9 +246,9 @@ int gact_hip_pileup_begin(gact_hip_engine *e, int32_t read_first, int32_t n_read
     pl.ref_epoch = e->ref_epoch;
     {
         std::lock_guard<std::mutex> lk(pl.mu);
-        pl.stats = gact_pileup_stats{};
-        pl.stats.positions = positions;
-        pl.stats.scratch_bytes = (int64_t)pl.bytes;
+        ps.stats = gact_pileup_stats{};
+        ps.stats.positions = positions;
+        ps.stats.scratch_bytes = (int64_t)ps.bytes;
     }
     pl.open = true;
     return 0;
@@ -299,13 +288,11 @@ int gact_hip_pileup_add(gact_hip_engine *e, int slot, int32_t n_sel, const int32
     sn.cap.resize(kept);
     const int32_t n_in = (int32_t)kept;
     if ((rc = path_bufs_init(sl.path, "pileup_add"))) return rc;
-    if (!sl.pile_ev0 && (hipEventCreate(&sl.pile_ev0) != hipSuccess || hipEventCreate(&sl.pile_ev1) != hipSuccess))
-        return fail(GACT_HIP_ENOMEM, "pileup_add: device allocation failed");
     Slot::PathBufs &pb = sl.path;
     gact::PileupWin win;
-    win.counts = (uint32_t *)pl.p;
-    win.n_aln = (int32_t *)(pl.p + pl.at_aln);
-    win.state = (gact::PileupState *)(pl.p + pl.at_state);
+    win.counts = (uint32_t *)pl.scratch.p;
+    win.n_aln = (int32_t *)(pl.scratch.p + pl.at_aln);
+    win.state = (gact::PileupState *)(pl.scratch.p + pl.at_state);
     win.read_first = pl.read_first; win.n_reads = pl.n_reads;
     win.base = pl.base;
     // Every chunk's arrays at their largest before the first launch: a DevBuf that grows frees its old memory, and chunk i's
@@ -330,7 +317,8 @@ int gact_hip_pileup_add(gact_hip_engine *e, int slot, int32_t n_sel, const int32
     gact::PileupState st{};
     float ms = 0;
     auto queue_and_wait = [&]() -> int {
-        HIP_TRY(hipEventRecord(sl.pile_ev0, sl.stream));
+        int trc = sl.pile_timer.start(sl.stream, "pileup_add");
+        if (trc) return trc;
         for (int32_t first = 0; first < n_in;) {
             int32_t end = first;
             int64_t bytes = 0;
@@ -346,10 +334,7 @@ int gact_hip_pileup_add(gact_hip_engine *e, int slot, int32_t n_sel, const int32
             chunks++;
         }
         HIP_TRY(hipMemcpyAsync(&st, win.state, sizeof st, hipMemcpyDeviceToHost, sl.stream));
-        HIP_TRY(hipEventRecord(sl.pile_ev1, sl.stream));
-        HIP_TRY(hipEventSynchronize(sl.pile_ev1));
-        HIP_TRY(hipEventElapsedTime(&ms, sl.pile_ev0, sl.pile_ev1));
-        return 0;
+        return sl.pile_timer.stop(sl.stream, &ms);
     };
     if ((rc = queue_and_wait())) {
         // earlier chunks' copies out of col_offs and sn.tagged, and their kernels, may still be queued: wait before those go
@@ -360,11 +345,12 @@ int gact_hip_pileup_add(gact_hip_engine *e, int slot, int32_t n_sel, const int32
     }
     {
         std::lock_guard<std::mutex> lk(pl.mu);
-        pl.stats.device_ms += ms;
-        pl.stats.adds++;
-        pl.stats.chunks += chunks;
-        pl.stats.alignments = std::max(pl.stats.alignments, (int64_t)st.alignments);       // (counted since begin, by every slot's adds)
-        pl.stats.columns = std::max(pl.stats.columns, (int64_t)st.columns);
+        gact_pileup_stats &ts = pl.scratch.stats;
+        ts.device_ms += ms;
+        ts.adds++;
+        ts.chunks += chunks;
+        ts.alignments = std::max(ts.alignments, (int64_t)st.alignments);       // (counted since begin, by every slot's adds)
+        ts.columns = std::max(ts.columns, (int64_t)st.columns);
     }
     if (st.flag) {
         // reported once: the flag word is cleared, so that later adds (of other slots too) answer for themselves.  The other
@@ -387,12 +373,13 @@ int gact_hip_pileup_finish(gact_hip_engine *e, int32_t min_depth, gact_pileup_co
     Pileup &pl = e->pileup;
     const SeqSet &rs = e->sets[GACT_SET_REF];
     hipStream_t stream = e->slots[0].stream;
-    const uint32_t *d_counts = (const uint32_t *)pl.p;
-    uint8_t *d_cons = pl.p + pl.at_cons;
-    gact_read_pileup *d_reads = (gact_read_pileup *)(pl.p + pl.at_reads);
+    PassScratch<gact_pileup_stats> &ps = pl.scratch;
+    const uint32_t *d_counts = (const uint32_t *)ps.p;
+    uint8_t *d_cons = ps.p + pl.at_cons;
+    gact_read_pileup *d_reads = (gact_read_pileup *)(ps.p + pl.at_reads);
     const uint8_t *own = rs.d_raw + pl.base;
     const size_t full = (size_t)std::max(1, e->prop.multiProcessorCount) * 8;              // eight waves on every SIMD
-    HIP_TRY(hipEventRecord(pl.ev0, stream));
+    if ((rc = ps.timer.start(stream, "pileup_finish"))) return rc;
     if (pl.positions > 0) {
         const size_t want = ((size_t)pl.positions + gact::kPileupBlock - 1) / gact::kPileupBlock;
         hipLaunchKernelGGL(gact::pileup_consensus_kernel, dim3((unsigned)std::min(want, full * 4)), dim3(gact::kPileupBlock), 0, stream,
@@ -403,7 +390,7 @@ int gact_hip_pileup_finish(gact_hip_engine *e, int32_t min_depth, gact_pileup_co
         const size_t want = ((size_t)pl.n_reads + gact::kPileupBlock / 64 - 1) / (gact::kPileupBlock / 64);
         hipLaunchKernelGGL(gact::pileup_reads_kernel, dim3((unsigned)std::min(want, full)), dim3(gact::kPileupBlock), 0, stream, d_counts,
                            own, d_cons, rs.d_offsets + pl.read_first, (long long)pl.base, pl.n_reads, (uint32_t)min_depth,
-                           (const int32_t *)(pl.p + pl.at_aln), d_reads);
+                           (const int32_t *)(ps.p + pl.at_aln), d_reads);
         HIP_TRY(hipGetLastError());
     }
     if (counts && pl.positions > 0)
@@ -411,12 +398,10 @@ int gact_hip_pileup_finish(gact_hip_engine *e, int32_t min_depth, gact_pileup_co
     if (consensus && pl.positions > 0) HIP_TRY(hipMemcpyAsync(consensus, d_cons, (size_t)pl.positions, hipMemcpyDeviceToHost, stream));
     if (reads && pl.n_reads > 0)
         HIP_TRY(hipMemcpyAsync(reads, d_reads, (size_t)pl.n_reads * sizeof(gact_read_pileup), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipEventRecord(pl.ev1, stream));
-    HIP_TRY(hipEventSynchronize(pl.ev1));
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, pl.ev0, pl.ev1));
+    if ((rc = ps.timer.stop(stream, &ms))) return rc;
     std::lock_guard<std::mutex> lk(pl.mu);
-    pl.stats.device_ms += ms;
+    ps.stats.device_ms += ms;
     return 0;
 }
 
@@ -426,6 +411,6 @@ int gact_hip_last_pileup_stats(gact_hip_engine *e, gact_pileup_stats *stats)
     Pileup &pl = e->pileup;
     if (!pl.open) return fail(GACT_HIP_EINVAL, "last_pileup_stats: no window is open (gact_hip_pileup_begin first)");
     std::lock_guard<std::mutex> lk(pl.mu);
-    *stats = pl.stats;
+    *stats = pl.scratch.stats;
     return 0;
 }

@@ -187,43 +187,27 @@ int gact_hip_select_overlaps(gact_hip_engine *e, int slot, int32_t n, const gact
         return fail(GACT_HIP_EINVAL, "select_overlaps: bad arguments (n = %d, at most %d; sel_cap = %d)", n, gact::kSelectMaxRecords, sel_cap);
     if (n == 0) return 0;
     Slot &sl = e->slots[slot];
-    if (!records && (sl.n_cands == 0 || !sl.overlaps.p))
-        return fail(GACT_HIP_EINVAL, "select_overlaps: slot %d holds no records (run its candidates first, or pass records)", slot);
-    if (!records && ((size_t)n > sl.n_cands || (size_t)n > sl.overlaps.cap))
-        return fail(GACT_HIP_EINVAL, "select_overlaps: n = %d beyond the %zu records of slot %d", n, sl.n_cands, slot);
+    if ((rc = slot_records_check(sl, slot, n, records, "select_overlaps"))) return rc;
     if ((rc = set_device(e))) return rc;
-    Slot::SelectBufs &sb = sl.select;
-    if (!sb.ev0 && (hipEventCreate(&sb.ev0) != hipSuccess || hipEventCreate(&sb.ev1) != hipSuccess))
-        return fail(GACT_HIP_ENOMEM, "select_overlaps: device allocation failed");
+    PassScratch<gact_select_stats> &sb = sl.select;
     size_t slots = 2;
     while (slots < 2 * (size_t)n) slots <<= 1;
     const size_t nb = ((size_t)n + gact::kSelectBlock - 1) / gact::kSelectBlock;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t at_table = records ? up16((size_t)n * sizeof(gact_overlap)) : 0;
     const size_t at_pos = at_table + slots * sizeof(int);
     const size_t at_flags = up16(at_pos + (size_t)n * sizeof(int));
     const size_t at_counts = at_flags + nb * (gact::kSelectBlock / 64) * sizeof(unsigned long long);
     const size_t at_sel = up16(at_counts + (2 * nb + 2) * sizeof(int));
     const size_t bytes = at_sel + (size_t)n * sizeof(int);
-    if (bytes > sb.bytes) {
-        if (sb.p) (void)hipFree(sb.p);
-        sb.p = nullptr; sb.bytes = 0;
-        if (hipMalloc((void **)&sb.p, bytes) != hipSuccess)
-            return fail(GACT_HIP_ENOMEM, "select_overlaps: device allocation failed (%d records, %zu bytes)", n, bytes);
-        sb.bytes = bytes;
-    }
+    if (sb.reserve(bytes)) return fail(GACT_HIP_ENOMEM, "select_overlaps: device allocation failed (%d records, %zu bytes)", n, bytes);
     int *d_table = (int *)(sb.p + at_table), *d_pos = (int *)(sb.p + at_pos);
     unsigned long long *d_flags = (unsigned long long *)(sb.p + at_flags);
     int *d_counts = (int *)(sb.p + at_counts), *d_emitted = d_counts + nb, *d_totals = d_counts + 2 * nb;
     int *d_sel = (int *)(sb.p + at_sel);
-    const gact_overlap *d_rec = sl.overlaps.p;
-    sb.stats = gact_select_stats{};
-    sb.timed = false;
-    HIP_TRY(hipEventRecord(sb.ev0, sl.stream));
-    if (records) {
-        HIP_TRY(hipMemcpyAsync(sb.p, records, (size_t)n * sizeof(gact_overlap), hipMemcpyHostToDevice, sl.stream));
-        d_rec = (const gact_overlap *)sb.p;
-    }
+    if ((rc = sb.begin(sl.stream, "select_overlaps"))) return rc;
+    DevRecords in;
+    if ((rc = slot_records_stage(sl, sb.p, n, records, n, nullptr, 0, nullptr, 0, in))) return rc;
+    const gact_overlap *d_rec = in.rec;
     HIP_TRY(hipMemsetAsync(d_table, 0xff, slots * sizeof(int), sl.stream));          // kSelectEmpty everywhere
     const dim3 grid((unsigned)nb), block(gact::kSelectBlock);
     hipLaunchKernelGGL(gact::select_insert_kernel, grid, block, 0, sl.stream, d_rec, n, mode, d_table, (uint32_t)(slots - 1), d_pos);
@@ -240,14 +224,11 @@ int gact_hip_select_overlaps(gact_hip_engine *e, int slot, int32_t n, const gact
     const bool room = sel && sel_cap >= totals[0];
     if (room && totals[0] > 0)
         HIP_TRY(hipMemcpyAsync(sel, d_sel, (size_t)totals[0] * sizeof(int), hipMemcpyDeviceToHost, sl.stream));
-    HIP_TRY(hipEventRecord(sb.ev1, sl.stream));
-    HIP_TRY(hipEventSynchronize(sb.ev1));
-    HIP_TRY(hipEventElapsedTime(&sb.stats.device_ms, sb.ev0, sb.ev1));
+    if ((rc = sb.end(sl.stream))) return rc;
     sb.stats.emitted = totals[1];
     sb.stats.selected = totals[0];
     sb.stats.table_slots = (int64_t)slots;
     sb.stats.scratch_bytes = (int64_t)sb.bytes;
-    sb.timed = true;
     if (!room)
         return fail(GACT_HIP_EINVAL, "select_overlaps: %d records selected, room for %d: call again with room for *n_sel", totals[0],
                     sel ? sel_cap : 0);
@@ -256,11 +237,5 @@ int gact_hip_select_overlaps(gact_hip_engine *e, int slot, int32_t n, const gact
 
 int gact_hip_last_select_stats(gact_hip_engine *e, int slot, gact_select_stats *stats)
 {
-    int rc = check_slot(e, slot);
-    if (rc) return rc;
-    if (!stats) return fail(GACT_HIP_EINVAL, "last_select_stats: NULL argument");
-    const Slot &sl = e->slots[slot];
-    if (!sl.select.timed) return fail(GACT_HIP_EINVAL, "last_select_stats: slot %d has made no selection yet", slot);
-    *stats = sl.select.stats;
-    return 0;
+    return last_pass_stats(e, slot, &Slot::select, stats, "last_select_stats", "has made no selection yet");
 }

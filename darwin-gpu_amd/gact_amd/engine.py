@@ -4,6 +4,7 @@ Plumbing only: numpy arrays in, numpy arrays out.  Fails loudly when the HIP
 library is missing or no device is present -- there is no CPU fallback.
 """
 import ctypes as C
+import glob
 import os
 import subprocess
 
@@ -12,10 +13,8 @@ import numpy as np
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))   # darwin-gpu_amd/
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.path.join(_PKG, "libgact_hip.so")
-SOURCES = [os.path.join(_PKG, "csrc", f) for f in
-           ("gact_engine.hip", "gact_kernels.hpp", "gact_device.hpp", "gact_chain.hpp", "gact_p16.hpp", "gact_p16s.hpp", "gact_lin.hpp",
-            "gact_aff.hpp", "gact_roles.hpp", "gact_coop.hpp", "gact_policy.hpp", "gact_big.hpp", "gact_gather.hpp", "gact_chain_kernel.hpp", "gact_path.hpp", "gact_summary.hpp", "gact_select.hpp", "gact_cover.hpp", "gact_graph.hpp", "gact_pileup.hpp",
-            "dsoft_device.hpp", "dsoft_engine.hpp")] + \
+# gact_engine.hip (the one translation unit, first) and every header under csrc/: none can be left out of the staleness check
+SOURCES = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.hip"))) + sorted(glob.glob(os.path.join(_PKG, "csrc", "*.hpp"))) + \
           [os.path.join(_ROOT, "include", "gact_hip.h")]
 
 SET_REF, SET_QUERY, SET_QUERY_RC = 0, 1, 2
@@ -175,6 +174,10 @@ class DsoftInfo(C.Structure):
 
 class GactHipError(RuntimeError):
     pass
+
+
+def _ptr(a):
+    return a.ctypes.data if a is not None else None
 
 
 def build(force=False, verbose=False):
@@ -540,7 +543,7 @@ class Engine:
         needed = C.c_int64()
         for attempt in (0, 1):
             ops = np.empty(cap, dtype=np.uint32)
-            rc = self.L.gact_hip_candidates_paths(self.h, slot, n, sel.ctypes.data if sel is not None else None, int(rc_from),
+            rc = self.L.gact_hip_candidates_paths(self.h, slot, n, _ptr(sel), int(rc_from),
                                                   int(same_file), records.ctypes.data, paths.ctypes.data, ops.ctypes.data, cap,
                                                   C.byref(needed))
             if rc == -1 and attempt == 0 and needed.value > cap:
@@ -549,12 +552,27 @@ class Engine:
             self._check(rc)
             return records, paths, ops[:int(needed.value)]
 
+    def _stats(self, fn, Struct, *args):
+        """a last_*_stats entry's figures as a dict (an array field as a list)"""
+        st = Struct()
+        self._check(fn(self.h, *args, C.byref(st)))
+        return {n: (list(getattr(st, n)) if isinstance(getattr(st, n), C.Array) else getattr(st, n)) for n, _ in Struct._fields_}
+
+    def _records_arg(self, records, n, slot):
+        """(records, n) of select_overlaps, read_coverage and overlap_graph: the caller's OVERLAP_DTYPE records (n None: all of
+        them), else records [0, n) of the slot's device array (n None: as many as the slot holds candidates)"""
+        if records is not None:
+            records = np.ascontiguousarray(records, dtype=OVERLAP_DTYPE)
+            n = len(records) if n is None else n
+            assert n <= len(records)
+        elif n is None:
+            n = self._n_cands.get(slot, 0)
+        return records, int(n)
+
     def last_paths_stats(self, slot=0):
         """the slot's last path run: device ms (HIP events around the whole call), chunks, most column bytes of one chunk,
         columns, ops"""
-        st = PathsStats()
-        self._check(self.L.gact_hip_last_paths_stats(self.h, slot, C.byref(st)))
-        return {n: getattr(st, n) for n, _ in PathsStats._fields_}
+        return self._stats(self.L.gact_hip_last_paths_stats, PathsStats, slot)
 
     def candidates_summaries(self, sel=None, n=None, rc_from=0x7fffffff, same_file=True, slot=0):
         """the alignments of candidates_paths reduced on the device, same selection: (records OVERLAP_DTYPE, sums
@@ -565,16 +583,14 @@ class Engine:
         n = int(n or 0)
         records = np.zeros(n, dtype=OVERLAP_DTYPE)
         sums = np.zeros(n, dtype=SUMMARY_DTYPE)
-        self._check(self.L.gact_hip_candidates_summaries(self.h, slot, n, sel.ctypes.data if sel is not None else None,
+        self._check(self.L.gact_hip_candidates_summaries(self.h, slot, n, _ptr(sel),
                                                          int(rc_from), int(same_file), records.ctypes.data, sums.ctypes.data))
         return records, sums
 
     def last_summaries_stats(self, slot=0):
         """the slot's last summary run: device ms (HIP events around the whole call), chain-kernel launches, device bytes
         the call holds for itself"""
-        st = SummariesStats()
-        self._check(self.L.gact_hip_last_summaries_stats(self.h, slot, C.byref(st)))
-        return {n: getattr(st, n) for n, _ in SummariesStats._fields_}
+        return self._stats(self.L.gact_hip_last_summaries_stats, SummariesStats, slot)
 
     def select_overlaps(self, n=None, records=None, mode="pair", slot=0):
         """every overlap once, chosen on the device: the ascending int32 indices of the records to keep, usable as `sel` of
@@ -586,25 +602,17 @@ class Engine:
             if mode not in _SELECT_MODES:
                 raise GactHipError("select_overlaps: unknown mode %r (\"exact\" or \"pair\")" % (mode,))
             mode = _SELECT_MODES[mode]
-        if records is not None:
-            records = np.ascontiguousarray(records, dtype=OVERLAP_DTYPE)
-            n = len(records) if n is None else n
-            assert n <= len(records)
-        elif n is None:
-            n = self._n_cands.get(slot, 0)
-        n = int(n)
+        records, n = self._records_arg(records, n, slot)
         sel = np.empty(max(n, 0), dtype=np.int32)
         n_sel = C.c_int32()
-        self._check(self.L.gact_hip_select_overlaps(self.h, slot, n, records.ctypes.data if records is not None else None,
+        self._check(self.L.gact_hip_select_overlaps(self.h, slot, n, _ptr(records),
                                                     mode, sel.ctypes.data, n, C.byref(n_sel)))
         return sel[:n_sel.value].copy()
 
     def last_select_stats(self, slot=0):
         """the slot's last selection: device ms (HIP events around the whole call), emitted records, selected records,
         table slots, device bytes the call holds for itself"""
-        st = SelectStats()
-        self._check(self.L.gact_hip_last_select_stats(self.h, slot, C.byref(st)))
-        return {n: getattr(st, n) for n, _ in SelectStats._fields_}
+        return self._stats(self.L.gact_hip_last_select_stats, SelectStats, slot)
 
     def read_coverage(self, read_lens, n=None, records=None, sel=None, sums=None, sides="both", min_depth=3, depth=False, slot=0):
         """per-read coverage of an overlap set, swept on the device: one COVER_DTYPE record per read of `read_lens` -- intervals
@@ -620,13 +628,7 @@ class Engine:
                 raise GactHipError("read_coverage: unknown sides %r (\"ref\", \"query\" or \"both\")" % (sides,))
             sides = _COVER_SIDES[sides]
         read_lens = np.ascontiguousarray(read_lens, dtype=np.int32)
-        if records is not None:
-            records = np.ascontiguousarray(records, dtype=OVERLAP_DTYPE)
-            n = len(records) if n is None else n
-            assert n <= len(records)
-        elif n is None:
-            n = self._n_cands.get(slot, 0)
-        n = int(n)
+        records, n = self._records_arg(records, n, slot)
         if sel is not None:
             sel = np.ascontiguousarray(sel, dtype=np.int32)
         if sums is not None:
@@ -634,18 +636,15 @@ class Engine:
             assert len(sums) == (len(sel) if sel is not None else n)
         cover = np.zeros(len(read_lens), dtype=COVER_DTYPE)
         per_base = np.zeros(int(read_lens.astype(np.int64).clip(0).sum()), dtype=np.int32) if depth else None
-        ptr = lambda a: a.ctypes.data if a is not None else None
-        self._check(self.L.gact_hip_read_coverage(self.h, slot, n, ptr(records), len(sel) if sel is not None else 0, ptr(sel),
-                                                  ptr(sums), int(sides), int(min_depth), len(read_lens), ptr(read_lens),
-                                                  ptr(cover), ptr(per_base)))
+        self._check(self.L.gact_hip_read_coverage(self.h, slot, n, _ptr(records), len(sel) if sel is not None else 0, _ptr(sel),
+                                                  _ptr(sums), int(sides), int(min_depth), len(read_lens), _ptr(read_lens),
+                                                  _ptr(cover), _ptr(per_base)))
         return (cover, per_base) if depth else cover
 
     def last_cover_stats(self, slot=0):
         """the slot's last coverage call: device ms (HIP events around the whole call), reads, intervals counted, positions,
         device bytes the call holds for itself"""
-        st = CoverStats()
-        self._check(self.L.gact_hip_last_cover_stats(self.h, slot, C.byref(st)))
-        return {n: getattr(st, n) for n, _ in CoverStats._fields_}
+        return self._stats(self.L.gact_hip_last_cover_stats, CoverStats, slot)
 
     def overlap_graph(self, read_lens, n=None, records=None, sel=None, sums=None, clip=None, params=None, classes=False, slot=0):
         """the overlap graph of an overlap set, made on the device: (reads, arcs) -- one GRAPH_READ_DTYPE record per read of
@@ -656,13 +655,7 @@ class Engine:
         span_begin / span_end.  params: None, a GraphParams, or a dict of max_hang, int_permille, min_ovlp, fuzz
         (include/gact_hip.h gact_hip_overlap_graph)"""
         read_lens = np.ascontiguousarray(read_lens, dtype=np.int32)
-        if records is not None:
-            records = np.ascontiguousarray(records, dtype=OVERLAP_DTYPE)
-            n = len(records) if n is None else n
-            assert n <= len(records)
-        elif n is None:
-            n = self._n_cands.get(slot, 0)
-        n = int(n)
+        records, n = self._records_arg(records, n, slot)
         if sel is not None:
             sel = np.ascontiguousarray(sel, dtype=np.int32)
         n_chosen = len(sel) if sel is not None else max(n, 0)
@@ -676,14 +669,13 @@ class Engine:
             params = GraphParams(**params)
         reads = np.zeros(len(read_lens), dtype=GRAPH_READ_DTYPE)
         cls = np.zeros(n_chosen, dtype=np.uint8) if classes else None
-        ptr = lambda a: a.ctypes.data if a is not None else None
         n_arcs = C.c_int64()
         cap = n_chosen                              # (room for 2 * n_chosen always suffices; most sets need less than half)
         for attempt in range(2):
             arcs = np.zeros(cap, dtype=GRAPH_ARC_DTYPE)
-            rc = self.L.gact_hip_overlap_graph(self.h, slot, n, ptr(records), len(sel) if sel is not None else 0, ptr(sel), ptr(sums),
-                                               len(read_lens), ptr(read_lens), ptr(clip), C.byref(params) if params is not None else None,
-                                               ptr(reads), ptr(cls), ptr(arcs), cap, C.byref(n_arcs))
+            rc = self.L.gact_hip_overlap_graph(self.h, slot, n, _ptr(records), len(sel) if sel is not None else 0, _ptr(sel), _ptr(sums),
+                                               len(read_lens), _ptr(read_lens), _ptr(clip), C.byref(params) if params is not None else None,
+                                               _ptr(reads), _ptr(cls), _ptr(arcs), cap, C.byref(n_arcs))
             if rc == 0 or attempt or n_arcs.value <= cap:
                 break
             cap = n_arcs.value                      # (EINVAL with *n_arcs filled: once more with room for them)
@@ -694,9 +686,7 @@ class Engine:
     def last_graph_stats(self, slot=0):
         """the slot's last overlap graph: device ms (HIP events around the whole call), reads, contained reads, chosen records
         per class (a list of 8), arcs proposed, arcs, transitive arcs, kept arcs, table slots, device bytes the call holds"""
-        st = GraphStats()
-        self._check(self.L.gact_hip_last_graph_stats(self.h, slot, C.byref(st)))
-        return {n: (list(getattr(st, n)) if n == "by_class" else getattr(st, n)) for n, _ in GraphStats._fields_}
+        return self._stats(self.L.gact_hip_last_graph_stats, GraphStats, slot)
 
     def pileup_begin(self, read_first=0, n_reads=None):
         """opens the pileup window: reads [read_first, read_first + n_reads) of SET_REF (n_reads None: to the set's end), counts
@@ -717,7 +707,7 @@ class Engine:
         if sel is not None:
             sel = np.ascontiguousarray(sel, dtype=np.int32)
             n = len(sel)
-        self._check(self.L.gact_hip_pileup_add(self.h, slot, int(n or 0), sel.ctypes.data if sel is not None else None,
+        self._check(self.L.gact_hip_pileup_add(self.h, slot, int(n or 0), _ptr(sel),
                                                int(rc_from), int(same_file)))
 
     def pileup_finish(self, min_depth=3, counts=True, consensus=True):
@@ -730,16 +720,13 @@ class Engine:
         reads = np.zeros(n_reads, dtype=READ_PILEUP_DTYPE)
         cnt = np.zeros((n_pos, 8), dtype=np.uint32) if counts else None
         cons = np.zeros(n_pos, dtype=np.uint8) if consensus else None
-        ptr = lambda a: a.ctypes.data if a is not None else None
-        self._check(self.L.gact_hip_pileup_finish(self.h, int(min_depth), ptr(cnt), ptr(cons), ptr(reads)))
+        self._check(self.L.gact_hip_pileup_finish(self.h, int(min_depth), _ptr(cnt), _ptr(cons), _ptr(reads)))
         return reads, cnt, cons
 
     def last_pileup_stats(self):
         """the pileup since pileup_begin: device ms of its adds and finishes (HIP events), adds, path-run chunks, alignments
         counted, their columns, the window's positions, device bytes the window holds"""
-        st = PileupStats()
-        self._check(self.L.gact_hip_last_pileup_stats(self.h, C.byref(st)))
-        return {n: getattr(st, n) for n, _ in PileupStats._fields_}
+        return self._stats(self.L.gact_hip_last_pileup_stats, PileupStats)
 
     def register_output(self, out, slot=0):
         """page-locks a caller-owned record array that will be fetched into repeatedly (opt-in; it must outlive the

@@ -1,8 +1,8 @@
 """GPU suite for the per-base pileup and consensus (gact_hip_pileup_begin / _add / _finish): counts, consensus bytes and the
 per-read table equal tests/pileup_model.py's -- fed with the chain model's CIGARs on the crafted candidates of
 tests/path_cases.py, with the path run's own ops at both tile geometries and both scorings -- and the depth equals
-gact_hip_read_coverage's; one selection added in five ways gives the same bytes; windows, what a slot keeps, the refusals, and
-the driver's --pileup.  Exact equality everywhere: integers and bytes are equal or the test fails."""
+gact_hip_read_coverage's; one selection added in five ways gives the same bytes; windows, what a slot keeps, the figures of
+all six passes behind one run on one slot, the refusals, and the driver's --pileup.  Exact equality everywhere: integers and bytes are equal or the test fails."""
 import os
 import re
 import subprocess
@@ -286,6 +286,67 @@ def test_an_add_leaves_the_slots_records_and_statistics_as_they_were():
         assert a.tobytes() == b.tobytes()
     _equal(eng.pileup_finish(), ref["one"])
     eng.close()
+
+
+def test_every_pass_of_one_slot_keeps_its_own_figures():
+    """all six passes behind one run on ONE slot: each one's last_*_stats, read again after every other pass has run, is what
+    it was directly after its own call (device_ms included: a call's time is read once and kept), and each result is its model's"""
+    from gact_amd import engine
+    from conftest import workload_block
+    from cover_model import cover
+    from graph_model import graph
+    from select_model import select
+    blk = workload_block("ecoli10x_small")
+    lens = np.array([len(r) for r in blk.rs.reads], dtype=np.int32)
+    eng, n, nf = engine_with(blk.rs, blk.cf, blk.cr)
+    eng.candidates_run_mixed(n, nf)
+    first, got = {}, {}
+    got["select"] = eng.select_overlaps(mode="pair")
+    first["select"] = eng.last_select_stats()
+    sel = got["select"][:40].copy()
+    assert len(sel) == 40 and 0 < nf < n
+    got["summaries"] = eng.candidates_summaries(sel=sel, rc_from=nf)
+    first["summaries"] = eng.last_summaries_stats()
+    got["paths"] = eng.candidates_paths(sel=sel, rc_from=nf)
+    first["paths"] = eng.last_paths_stats()
+    sums = got["summaries"][1]
+    got["cover"] = eng.read_coverage(lens, sel=sel, sums=sums, min_depth=2, depth=True)
+    first["cover"] = eng.last_cover_stats()
+    got["graph"] = eng.overlap_graph(lens, sel=sel, sums=sums, classes=True)
+    first["graph"] = eng.last_graph_stats()
+    eng.pileup_begin()
+    eng.pileup_add(sel=sel, rc_from=nf)
+    got["pileup"] = eng.pileup_finish(min_depth=2)
+    first["pileup"] = eng.last_pileup_stats()
+    again = dict(select=eng.last_select_stats(), summaries=eng.last_summaries_stats(), paths=eng.last_paths_stats(),
+                 cover=eng.last_cover_stats(), graph=eng.last_graph_stats(), pileup=eng.last_pileup_stats())
+    records = eng.candidates_fetch(n).copy()
+    eng.close()
+    for name in first:
+        assert again[name] == first[name], (name, first[name], again[name])
+        assert first[name]["device_ms"] > 0, name
+    # every pass counted its own input, not a neighbour's
+    assert first["select"]["selected"] == len(got["select"]) and first["select"]["emitted"] == int(records["emitted"].sum())
+    assert first["summaries"]["launches"] == 1 and first["paths"]["chunks"] == 1 and first["paths"]["ops"] == len(got["paths"][2])
+    assert first["cover"]["reads"] == first["graph"]["reads"] == len(lens) and first["pileup"]["adds"] == 1
+    # ... and every result is its model's
+    assert got["select"].tolist() == select(records, "pair").tolist()
+    rec_s, _ = got["summaries"]
+    rec_p, paths, ops = got["paths"]
+    assert rec_s.tobytes() == rec_p.tobytes() == records[sel].tobytes()
+    for k in range(len(sel)):
+        assert sums[k].tobytes() == engine.summarise(ops_of(paths, ops, k)).tobytes(), (k, sums[k])
+    want_cover, want_depth = cover(records, lens, sel=sel, sums=sums, min_depth=2)
+    assert got["cover"][0].tobytes() == want_cover.tobytes() and np.array_equal(got["cover"][1], want_depth)
+    assert first["cover"]["intervals"] == int(want_cover["n_intervals"].sum())
+    want_graph = graph(records, lens, sel=sel, sums=sums)
+    for name, g in zip(("reads", "arcs", "classes"), got["graph"]):
+        assert g.tobytes() == want_graph[name].tobytes(), name
+    for name, count in want_graph["counts"].items():
+        assert first["graph"][name] == count, name
+    want_pileup = _model(blk.rs, rec_p, paths, ops, min_depth=2)
+    _same(got["pileup"], want_pileup, "the 40 selected")
+    assert first["pileup"]["alignments"] == int(want_pileup[2]["n_alignments"].sum()) > 0
 
 
 def test_refusals():
