@@ -308,6 +308,8 @@ struct Slot {
     PassScratch<gact_cover_stats> cover;
     // gact_hip_overlap_graph (gact_graph.hpp): host records | sel | sums | lens | clip | read table, degrees, counters | table | proposals | arcs
     PassScratch<gact_graph_stats> graph;
+    // gact_hip_unitigs (gact_unitig.hpp): arcs | reads | lens | clip | degrees, counters, flag | links | ranking records | scans | unitigs, layout, places | bases
+    PassScratch<gact_unitig_stats> unitig;
     // gact_hip_pileup_add (gact_pileup.hpp): the events around this slot's adds; the counts are the engine's (Pileup)
     PassTimer pile_timer;
 
@@ -323,6 +325,7 @@ struct Slot {
         select.release();
         cover.release();
         graph.release();
+        unitig.release();
         pile_timer.release();
         if (d_counter) (void)hipFree(d_counter);
         if (d_flags) (void)hipFree(d_flags);
@@ -2474,6 +2477,7 @@ int gact_hip_measure_valu_rate(gact_hip_engine *e, double *lane_ops_per_s)
 #include "gact_cover.hpp"        // gact_hip_read_coverage: per-read coverage of an overlap set, behind those
 #include "gact_graph.hpp"        // gact_hip_overlap_graph: containment, dovetail arcs and their transitive flags, behind those
 #include "gact_pileup.hpp"       // gact_hip_pileup_*: per-base pileup and consensus from the alignments' columns
+#include "gact_unitig.hpp"       // gact_hip_unitigs: tip cut, chain ranking, layout and bases of the graph's unitigs, behind every other kernel
 
 #ifdef GACT_STAMPS
 // diagnostic build: per-wave (start, queues empty, end, iterations) of the last main launch

@@ -43,6 +43,14 @@ GRAPH_READ_DTYPE = np.dtype([(n, "<i4") for n in ("n_hits", "n_internal", "n_con
 assert GRAPH_ARC_DTYPE.itemsize == 32 and GRAPH_READ_DTYPE.itemsize == 32
 GRAPH_NONE, GRAPH_SELF, GRAPH_DROPPED, GRAPH_INTERNAL, GRAPH_QUERY_CONTAINED, GRAPH_TARGET_CONTAINED, GRAPH_SHORT, \
     GRAPH_DOVETAIL = range(8)
+# the unitigs of an overlap graph (include/gact_hip.h gact_hip_unitigs): a unitig, an entry of its layout, and where a read went
+UNITIG_DTYPE = np.dtype([(n, "<i4") for n in ("first", "last", "n_reads", "circular")] +
+                        [(n, "<i8") for n in ("layout_at", "seq_at", "length")])
+UNITIG_ENTRY_DTYPE = np.dtype([("vertex", "<i4"), ("take", "<i4"), ("start", "<i8")])
+UNITIG_PLACE_DTYPE = np.dtype([(n, "<i4") for n in ("unitig", "rank", "orient", "state")])
+assert UNITIG_DTYPE.itemsize == 40 and UNITIG_ENTRY_DTYPE.itemsize == 16 and UNITIG_PLACE_DTYPE.itemsize == 16
+UNITIG_PLACED, UNITIG_CONTAINED, UNITIG_EMPTY, UNITIG_TIP = range(4)
+UNITIG_DEFAULT_TIP_READS = 3
 # the kinds a position of a pileup counts (include/gact_hip.h GACT_PILEUP_*), and the per-read table of pileup_finish
 PILEUP_A, PILEUP_C, PILEUP_G, PILEUP_T, PILEUP_OTHER, PILEUP_DEL, PILEUP_INS, PILEUP_DEPTH = range(8)
 PILEUP_COL_DTYPE = np.dtype([("n", "<u4", (8,))])
@@ -144,6 +152,20 @@ class GraphStats(C.Structure):
     _fields_ = [("device_ms", C.c_float), ("reads", C.c_int32), ("contained", C.c_int32), ("by_class", C.c_int64 * 8),
                 ("proposed", C.c_int64), ("arcs", C.c_int64), ("transitive", C.c_int64), ("kept", C.c_int64),
                 ("table_slots", C.c_int64), ("scratch_bytes", C.c_int64)]
+
+
+class UnitigParams(C.Structure):
+    """the default is GACT_UNITIG_DEFAULT_TIP_READS"""
+    _fields_ = [("tip_reads", C.c_int32)]
+
+    def __init__(self, tip_reads=UNITIG_DEFAULT_TIP_READS):
+        super().__init__(tip_reads)
+
+
+class UnitigStats(C.Structure):
+    _fields_ = [("device_ms", C.c_float)] + \
+               [(n, C.c_int32) for n in ("reads", "placed", "cut", "contained", "unitigs", "circular", "longest_reads", "rank_launches")] + \
+               [(n, C.c_int64) for n in ("longest_bases", "e0_arcs", "e1_arcs", "joins", "links", "scratch_bytes")]
 
 
 class PileupStats(C.Structure):
@@ -327,6 +349,14 @@ def load():
     except AttributeError:
         pass
     try:
+        L.gact_hip_unitigs.argtypes = [vp, C.c_int, i32, vp, vp, vp, C.c_int64, vp, C.POINTER(UnitigParams), vp, C.POINTER(i32), vp, vp,
+                                       vp, C.c_int64, C.POINTER(C.c_int64)]
+        L.gact_hip_unitigs.restype = C.c_int
+        L.gact_hip_last_unitig_stats.argtypes = [vp, C.c_int, C.POINTER(UnitigStats)]
+        L.gact_hip_last_unitig_stats.restype = C.c_int
+    except AttributeError:
+        pass
+    try:
         L.gact_hip_pileup_begin.argtypes = [vp, i32, i32]
         L.gact_hip_pileup_add.argtypes = [vp, C.c_int, i32, vp, i32, C.c_int]
         L.gact_hip_pileup_finish.argtypes = [vp, i32, vp, vp, vp]
@@ -368,7 +398,7 @@ EXPORTS = ("gact_hip_create", "gact_hip_destroy", "gact_hip_last_error", "gact_h
            "gact_hip_candidates_paths", "gact_hip_last_paths_stats", "gact_hip_candidates_summaries",
            "gact_hip_last_summaries_stats", "gact_hip_format_paf", "gact_hip_select_overlaps", "gact_hip_last_select_stats",
            "gact_hip_read_coverage", "gact_hip_last_cover_stats", "gact_hip_overlap_graph", "gact_hip_last_graph_stats",
-           "gact_hip_pileup_begin", "gact_hip_pileup_add",
+           "gact_hip_unitigs", "gact_hip_last_unitig_stats", "gact_hip_pileup_begin", "gact_hip_pileup_add",
            "gact_hip_pileup_finish", "gact_hip_last_pileup_stats")
 
 
@@ -687,6 +717,46 @@ class Engine:
         """the slot's last overlap graph: device ms (HIP events around the whole call), reads, contained reads, chosen records
         per class (a list of 8), arcs proposed, arcs, transitive arcs, kept arcs, table slots, device bytes the call holds"""
         return self._stats(self.L.gact_hip_last_graph_stats, GraphStats, slot)
+
+    def unitigs(self, read_lens, reads, arcs, clip=None, tip_reads=UNITIG_DEFAULT_TIP_READS, seq=False, slot=0):
+        """the unitigs of an overlap graph, made on the device: (unitigs, layout, places) -- UNITIG_DTYPE records ascending by
+        their first vertex, the UNITIG_ENTRY_DTYPE entries of their layouts one unitig after the other, and one
+        UNITIG_PLACE_DTYPE record per read -- or (unitigs, layout, places, bases) with the unitigs' bases as bytes, spelled
+        from the reads of SET_REF, when `seq` is set.  read_lens and clip as overlap_graph took them, reads and arcs as it
+        returned them; tip_reads: dead ends of at most that many reads are cut, 0 cuts nothing
+        (include/gact_hip.h gact_hip_unitigs)"""
+        read_lens = np.ascontiguousarray(read_lens, dtype=np.int32)
+        reads = np.ascontiguousarray(reads, dtype=GRAPH_READ_DTYPE)
+        arcs = np.ascontiguousarray(arcs, dtype=GRAPH_ARC_DTYPE)
+        n = len(read_lens)
+        assert len(reads) == n
+        if clip is not None:
+            clip = np.ascontiguousarray(clip, dtype=np.int32).reshape(-1)
+            assert len(clip) == 2 * n
+        params = UnitigParams(int(tip_reads))
+        unitigs = np.zeros(n, dtype=UNITIG_DTYPE)
+        layout = np.zeros(n, dtype=UNITIG_ENTRY_DTYPE)
+        places = np.zeros(n, dtype=UNITIG_PLACE_DTYPE)
+        n_unitigs, seq_len = C.c_int32(), C.c_int64()
+        cap = int(read_lens.astype(np.int64).sum()) // 2 if seq else 0    # (most sets need far less than their reads' bases)
+        for attempt in range(2):
+            bases = np.zeros(cap, dtype=np.uint8) if seq else None
+            rc = self.L.gact_hip_unitigs(self.h, slot, n, _ptr(read_lens), _ptr(clip), _ptr(reads), len(arcs), _ptr(arcs),
+                                         C.byref(params), _ptr(unitigs), C.byref(n_unitigs), _ptr(layout), _ptr(places),
+                                         _ptr(bases), cap, C.byref(seq_len))
+            if rc == 0 or attempt or not seq or seq_len.value <= cap:
+                break
+            cap = seq_len.value                     # (EINVAL with *seq_len filled: once more with room for the bases)
+        self._check(rc)
+        unitigs = unitigs[:n_unitigs.value].copy()
+        layout = layout[:int(unitigs["n_reads"].sum())].copy()
+        return (unitigs, layout, places, bases[:seq_len.value].tobytes()) if seq else (unitigs, layout, places)
+
+    def last_unitig_stats(self, slot=0):
+        """the slot's last unitig call: device ms (HIP events around the whole call), reads, reads placed, cut as tips and
+        contained, unitigs, circular ones, the longest in reads and in bases, ranking launches, arcs with flags == 0, those
+        left after the tip cut, joins and links among them, device bytes the call holds"""
+        return self._stats(self.L.gact_hip_last_unitig_stats, UnitigStats, slot)
 
     def pileup_begin(self, read_first=0, n_reads=None):
         """opens the pileup window: reads [read_first, read_first + n_reads) of SET_REF (n_reads None: to the set's end), counts

@@ -3,7 +3,7 @@
 //   darwin_hip <REF.fasta> <READS.fasta> CPU_THREADS [--params params.cfg]
 //              [--candidates FILE | --dump-candidates FILE [--dsoft-only]] [--device-dsoft]
 //              [--device D] [--shard R/W] [--recode] [--cigar] [--paf] [--unique exact|pair] [--coverage K]
-//              [--pileup K] [--gfa]
+//              [--pileup K] [--gfa [--unitigs K]]
 //
 // Plays the part of reference darwin.cpp:451-646 for the GACT stage: owns the
 // globals gact.cpp reads, loads params.cfg and the two FASTA files, builds the
@@ -45,6 +45,11 @@
 // whole reads -- and darwin.gfa gets `H VN:Z:1.0`, one `S <name> <clipped bases> LN:i:<n>` line per read that is not contained
 // and has a non-empty clip, in id order, and one `L <u name> <+|-> <v name> <+|-> <min(ov_u, ov_v)>M L1:i:<len>` line per kept
 // arc, in the arc list's order.  Every other output byte is as without the flag.
+// --unitigs K (with --gfa; K >= 0): behind the graph call one gact_hip_unitigs call with tip_reads = K and bases, over the same
+// lengths, clip, reads and arcs, and darwin.utg.gfa gets `H VN:Z:1.0`; per unitig, numbered from 1 in the call's order, one
+// `S utg<6 digits><l|c> <bases> LN:i:<length>` line (l linear, c circular) followed by one `a <utg> <start> <read name>:<b>-<e>
+// <+|-> <take>` line per entry of its layout, [b, e) the read's clip; and then one `L <utg> <+|-> <utg> <+|-> <min(ov_u, ov_v)>M`
+// line per link (include/gact_hip.h, rule 7), in the arc list's order.  Every other output byte is as without the flag.
 //
 // --device D: the GPU this process uses (the reference is single-device, cuda_host.cu:195).  --shard R/W: this
 // process is rank R of W -- it extends every W-th candidate (host filter) or the R-th contiguous range of reads
@@ -87,6 +92,7 @@ static int unique_mode = -1;                     // --unique: GACT_SELECT_EXACT 
 static int coverage_depth = 0;                   // --coverage K: min_depth of darwin.cover.tsv, 0: no table
 static int pileup_depth = 0;                     // --pileup K: min_depth of darwin.cons.fa, 0: no consensus
 static bool want_gfa = false;                    // --gfa: darwin.gfa, the overlap graph of the records written
+static int unitig_tips = -1;                     // --unitigs K: tip_reads of darwin.utg.gfa, -1: no unitigs
 // --coverage, --gfa: the records every feeder wrote a line for, in its file's order, and with --paf their summaries
 static std::vector<std::vector<gact_overlap> > cover_records;
 static std::vector<std::vector<gact_path_summary> > cover_sums;
@@ -371,6 +377,56 @@ static int write_coverage(gact_hip_engine *e, std::vector<int32_t> *spans)
     return 0;
 }
 
+// --unitigs: one call over what the graph call of --gfa returned, on slot 0, then darwin.utg.gfa
+static int write_unitigs(gact_hip_engine *e, const std::vector<int32_t> &lens, const std::vector<int32_t> &clip,
+                         const std::vector<gact_graph_read> &reads, const std::vector<gact_graph_arc> &arcs, int64_t n_arcs)
+{
+    const size_t n = lens.size();
+    int64_t room = 0, seq_len = 0;
+    for (size_t i = 0; i < n; i++) room += clip.empty() ? lens[i] : clip[2 * i + 1] - clip[2 * i];      // (every read is placed once at most)
+    std::vector<gact_unitig> utg(n);
+    std::vector<gact_unitig_entry> layout(n);
+    std::vector<gact_unitig_place> places(n);
+    std::vector<uint8_t> seq((size_t)room + 1);
+    int32_t n_utg = 0;
+    const gact_unitig_params params = {unitig_tips};
+    const int rc = gact_hip_unitigs(e, 0, (int32_t)n, lens.data(), clip.empty() ? nullptr : clip.data(), reads.data(), n_arcs,
+                                    arcs.data(), &params, utg.data(), &n_utg, layout.data(), places.data(), seq.data(), room, &seq_len);
+    if (rc != 0) { printf("\ngact_hip_unitigs failed: %s\n\n", gact_hip_last_error()); return 1; }
+    FILE *f = fopen("darwin.utg.gfa", "w");
+    if (!f) { fprintf(stderr, "--unitigs: cannot write darwin.utg.gfa\n"); return 1; }
+    fprintf(f, "H\tVN:Z:1.0\n");
+    auto name = [&](int32_t j) {
+        char buf[32];
+        snprintf(buf, sizeof buf, "utg%06d%c", j + 1, utg[(size_t)j].circular ? 'c' : 'l');
+        return std::string(buf);
+    };
+    for (int32_t j = 0; j < n_utg; j++) {
+        const gact_unitig &u = utg[(size_t)j];
+        fprintf(f, "S\t%s\t", name(j).c_str());
+        fwrite(seq.data() + u.seq_at, 1, (size_t)u.length, f);
+        fprintf(f, "\tLN:i:%lld\n", (long long)u.length);
+        for (int32_t r = 0; r < u.n_reads; r++) {
+            const gact_unitig_entry &en = layout[(size_t)(u.layout_at + r)];
+            const size_t i = (size_t)(en.vertex >> 1);
+            fprintf(f, "a\t%s\t%lld\t%s:%d-%d\t%c\t%d\n", name(j).c_str(), (long long)en.start, reads_descrips[i][0].c_str(),
+                    clip.empty() ? 0 : clip[2 * i], clip.empty() ? lens[i] : clip[2 * i + 1], en.vertex & 1 ? '-' : '+', en.take);
+        }
+    }
+    for (int64_t k = 0; k < n_arcs; k++) {
+        const gact_graph_arc &a = arcs[(size_t)k];
+        const gact_unitig_place &pu = places[(size_t)(a.u >> 1)], &pv = places[(size_t)(a.v >> 1)];
+        if (a.flags || pu.state != GACT_UNITIG_PLACED || pv.state != GACT_UNITIG_PLACED) continue;       // (not an arc of E1)
+        const bool fu = pu.orient == (a.u & 1), fv = pv.orient == (a.v & 1);
+        // a join inside a unitig: the two vertices are neighbours in it, in the order the arc's direction gives
+        if (pu.unitig == pv.unitig && fu == fv && pv.rank == pu.rank + (fu ? 1 : -1)) continue;
+        fprintf(f, "L\t%s\t%c\t%s\t%c\t%dM\n", name(pu.unitig).c_str(), fu ? '+' : '-', name(pv.unitig).c_str(), fv ? '+' : '-',
+                std::min(a.ov_u, a.ov_v));
+    }
+    fclose(f);
+    return 0;
+}
+
 // --gfa: one call over the records all feeders kept, on slot 0, then darwin.gfa.  clip: the spans of --coverage, or empty
 static int write_gfa(gact_hip_engine *e, const std::vector<int32_t> &clip)
 {
@@ -402,7 +458,7 @@ static int write_gfa(gact_hip_engine *e, const std::vector<int32_t> &clip)
                 reads_descrips[(size_t)(a.v >> 1)][0].c_str(), a.v & 1 ? '-' : '+', std::min(a.ov_u, a.ov_v), a.len);
     }
     fclose(f);
-    return 0;
+    return unitig_tips >= 0 ? write_unitigs(e, lens, clip, reads, arcs, n_arcs) : 0;
 }
 
 // --pileup: the consensus of every reference sequence from the counts the feeders' adds left, then darwin.cons.fa
@@ -599,7 +655,7 @@ int main(int argc, char *argv[])
     if (argc >= 3 && strcmp(argv[1], "--selftest") == 0) return selftest(argv[2]);
     if (argc < 4) {
         fprintf(stderr, "Usage: darwin_hip <REFERENCE>.fasta <READS>.fasta CPU_THREADS --candidates FILE "
-                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K] [--gfa]]\n");
+                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K] [--gfa [--unitigs K]]]\n");
         return 1;
     }
     std::string cand_path, dump_path, cfg_path = "params.cfg", gather_id;
@@ -634,6 +690,13 @@ int main(int argc, char *argv[])
             pileup_depth = (int)k;
         }
         else if (!strcmp(argv[a], "--gfa")) want_gfa = true;
+        else if (!strcmp(argv[a], "--unitigs")) {
+            const char *v = a + 1 < argc ? argv[++a] : "";
+            char *end = nullptr;
+            const long k = strtol(v, &end, 10);
+            if (!*v || *end || k < 0 || k > 0x7fffffffL) { fprintf(stderr, "--unitigs wants an integer >= 0, not '%s'\n", v); return 1; }
+            unitig_tips = (int)k;
+        }
         else if (!strcmp(argv[a], "--rccl-gather") && a + 1 < argc) gather_id = argv[++a];
         else if (!strcmp(argv[a], "--device") && a + 1 < argc) setenv("GACT_HIP_DEVICE", argv[++a], 1);   // read by GPU_init
         else if (!strcmp(argv[a], "--shard") && a + 1 < argc) {
@@ -676,6 +739,11 @@ int main(int argc, char *argv[])
         // the graph is over one read set, from the records of one process's feeders: the host-filter mode keeps none, a rank of a
         // sharded job holds part of every read's overlaps, and with two files ref and query ids name different sequences
         fprintf(stderr, "--gfa: only with --device-dsoft and one input file used for both sides, and not with --shard\n");
+        return 1;
+    }
+    if (unitig_tips >= 0 && !want_gfa) {
+        // the unitigs are made from what the graph call of --gfa returns
+        fprintf(stderr, "--unitigs: only with --gfa\n");
         return 1;
     }
     std::map<std::string, double> cfg = parse_cfg(cfg_path);

@@ -474,6 +474,78 @@ typedef struct { float device_ms; int32_t reads, contained; int64_t by_class[8],
                  table_slots, scratch_bytes; } gact_graph_stats;
 int gact_hip_last_graph_stats(gact_hip_engine *e, int slot, gact_graph_stats *stats);
 
+/* ---- unitigs: tip cut, unambiguous paths, their layouts and their bases, made on the device ----
+ * The last step of a layout stage, on what gact_hip_overlap_graph returned: the short dead ends are cut, every unambiguous path of
+ * kept arcs becomes a unitig, and one sequence is spelled per unitig (csrc/gact_unitig.hpp).  All integer, lengths and offsets
+ * in 64 bits, order-free: every output is the same on every call and every slot.
+ * Inputs.
+ *   read_lens, clip  the ones passed to gact_hip_overlap_graph (clip NULL: every read whole)
+ *   reads, arcs      what that call returned, host arrays; of reads only contained_by is read; arcs ascending by (u, len, v)
+ *   params           NULL: tip_reads = GACT_UNITIG_DEFAULT_TIP_READS, after miniasm's "fewer than 4 reads": a parameter, not a
+ *                    measurement.  tip_reads >= 0; 0 cuts nothing
+ * The rule.
+ *   1 Vertices as in the graph.  Read i is live iff contained_by < 0 and its clipped length cl(i) = ce - cb (len without a clip) is
+ *     positive; the others get state GACT_UNITIG_CONTAINED or GACT_UNITIG_EMPTY, CONTAINED first
+ *   2 E0 = the arcs with flags == 0.  out(x) = the arcs of the current set out of x, in(x) = out(x^1).  An arc u -> v is a join iff
+ *     out(u) == 1 and in(v) == 1; joins are closed under complement.  A chain is a maximal path of joins, a vertex without joins a
+ *     chain of one; it is linear, with head h and tail t, or a cycle.  No arc joins the two vertices of one read, so no chain
+ *     holds both x and x^1, and the complement of a chain is another chain, with head t^1
+ *   3 Tip cut, one simultaneous round on E0: a linear chain of c reads is a tip iff c <= tip_reads and (in(h) == 0 or
+ *     out(t) == 0) -- so an isolated short chain and a live read without arcs are cut; a cycle never is.  Every read of a tip
+ *     gets state GACT_UNITIG_TIP.  E1 = E0 without the arcs that touch a TIP read.  Two tips at one junction are both cut, and
+ *     when every branch at a junction is short, all of them are: known, not repaired
+ *   4 Unitigs are the chains of E1 over the live reads that are not cut, one per complement pair: of a linear chain the
+ *     orientation with the smaller head vertex (a chain of one read is its even vertex); of a cycle the orientation that holds
+ *     the lowest vertex id m of the cycle and its complement (m is even), opened in front of m: first = m, last = the vertex
+ *     joined to m, circular = 1.  Numbered ascending by first
+ *   5 Layout.  Entry layout_at + r is the vertex of rank r; take = len of the join to the next entry, the clipped length for the
+ *     last entry of a linear unitig, len of the closing arc last -> first for the last entry of a circular one; start = the sum
+ *     of the takes before it; length = the sum of the takes; seq_at = the sum of the lengths of the lower-numbered unitigs.
+ *     places[i] = (unitig, rank, orient = the low bit of the read's vertex in the emitted orientation, GACT_UNITIG_PLACED), or
+ *     (-1, -1, 0, state) for a read that is not placed
+ *   6 Bases (seq != NULL): an entry with vertex 2 i + s and take T gives the first T bases of the clipped read in that
+ *     orientation -- s == 0: bytes [cb, cb + T) of read i of GACT_SET_REF; s == 1: the complements of bytes ce - 1, ce - 2, ...
+ *     (ACGTNacgtn to TGCANtgcan; any other byte gives N, and is not refused) -- at seq[seq_at + start ...].  seq_cap < *seq_len:
+ *     GACT_HIP_EINVAL with everything else filled and *seq_len set; call again with room, as with arcs_cap.  seq == NULL: no
+ *     bases, *seq_len (where given) is still the total length
+ *   7 Links are not an output: every arc of E1 that is not a join inside a unitig runs from the tail of an oriented unitig to
+ *     the head of one, the closing arc of a circular unitig (and its complement) among them; the orientation is + when the
+ *     vertex's low bit is places[].orient.  The driver and the model derive them
+ * Refused with GACT_HIP_EINVAL, outputs untouched: a NULL among read_lens, reads, n_unitigs, places, unitigs, layout; n_reads < 0
+ * or > 2^30; n_arcs < 0 or > 2^29; tip_reads < 0; a negative length; a clip outside 0 <= cb <= ce <= len; an arc with u or v
+ * outside [0, 2 n_reads), with u>>1 == v>>1 or with len < 1; arcs not (strictly) ascending by (u, len, v); an arc with flags == 0
+ * that names a read that is not live, or whose complement v^1 -> u^1 is not an arc with flags == 0; with seq: seq_len NULL,
+ * GACT_SET_REF not uploaded, of another number of sequences or of other lengths than read_lens, or an arc with flags == 0 longer
+ * than the clipped length of the read it leaves (the bases of its take would lie outside the clip; the graph call makes none).
+ * The arc checks run on the device.  n_reads == 0 returns 0 with *n_unitigs = 0 and *seq_len = 0.
+ * Synchronous on the slot's stream; the slot's records and every other statistic stay as they were.  Device memory of its own, one
+ * allocation per slot, grown on demand: 32 bytes per arc, about 300 per read (8 more with a clip), and with seq the reads'
+ * clipped lengths.  Out of scope: bubble popping, repeated rounds of cleaning, pruning of short overlaps, sharded jobs, and
+ * taking the arcs from the graph call's scratch. */
+#define GACT_UNITIG_DEFAULT_TIP_READS 3
+#define GACT_UNITIG_PLACED    0
+#define GACT_UNITIG_CONTAINED 1
+#define GACT_UNITIG_EMPTY     2   /* clipped length 0 */
+#define GACT_UNITIG_TIP       3
+typedef struct { int32_t tip_reads; } gact_unitig_params;
+typedef struct { int32_t first, last, n_reads, circular; int64_t layout_at, seq_at, length; } gact_unitig;   /* 40 bytes */
+typedef struct { int32_t vertex, take; int64_t start; } gact_unitig_entry;                                    /* 16 bytes */
+typedef struct { int32_t unitig, rank, orient, state; } gact_unitig_place;                                    /* 16 bytes */
+int gact_hip_unitigs(gact_hip_engine *e, int slot, int32_t n_reads, const int32_t *read_lens, const int32_t *clip,
+                     const gact_graph_read *reads, int64_t n_arcs, const gact_graph_arc *arcs,
+                     const gact_unitig_params *params /* NULL: the defaults */,
+                     gact_unitig *unitigs /* room for n_reads */, int32_t *n_unitigs,
+                     gact_unitig_entry *layout /* room for n_reads */, gact_unitig_place *places /* n_reads */,
+                     uint8_t *seq /* NULL: no bases */, int64_t seq_cap, int64_t *seq_len);
+/* What the slot's last gact_hip_unitigs call that got as far as the device did: HIP events on the slot's stream around the whole
+ * call (copies and kernels), the reads, those placed in a unitig, cut as tips and contained, the unitigs, the circular ones, the
+ * longest unitig in reads and in bases, the launches of the ranking kernel (three sweeps of ceil(log2(2 n_reads)) rounds), the
+ * arcs of E0 and of E1, the joins of E1 (a cycle's closing join among them), the links (rule 7), and the device memory the call
+ * holds for itself. */
+typedef struct { float device_ms; int32_t reads, placed, cut, contained, unitigs, circular, longest_reads, rank_launches;
+                 int64_t longest_bases, e0_arcs, e1_arcs, joins, links, scratch_bytes; } gact_unitig_stats;
+int gact_hip_last_unitig_stats(gact_hip_engine *e, int slot, gact_unitig_stats *stats);
+
 /* Per-base pileup and consensus of the reads of GACT_SET_REF from the overlaps' alignments, counted on the device: every chosen
  * candidate's alignment (the one gact_hip_candidates_paths returns as a CIGAR) is stacked on its target read, every position
  * counts what the other reads say there, and the majority is the consensus.  The pileup belongs to the engine, not to a slot:
