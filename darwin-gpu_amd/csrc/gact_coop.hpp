@@ -15,8 +15,10 @@
 //     block's walk lock and walks EVERY posted job of the block -- its own and the other three waves', up to 64, one per
 //     lane -- in one instruction stream, then goes on.  A walk batch is ~30 jobs in the steady state: the walk's
 //     instructions per tile drop by that factor over 8;
-//   * the walk itself is walk_chain_lin's, move for move (same cells, same order, same stop tests, same band rule); the
-//     bases of a cell come out of the loader's staging words, which stay in LDS until their bank is loaded again.
+//   * the walk itself is walk_chain_lin's, move for move (same cells, same order, same stop tests, same band rule), as
+//     straight-line code: eight moves per trip without a branch, finished lanes riding along with their updates masked,
+//     positions carried from move to move (gact_walk_pos.hpp).  The bases of a cell come out of the loader's
+//     staging words, which stay in LDS until their bank is loaded again.
 //
 // Hand-over: LDS words only.  A job's fields are written before its state word (posted), a lane claims a job with a
 // compare-and-swap on the state word, a result is written before the state word says done; the pointer words a walk reads
@@ -27,6 +29,7 @@
 #pragma once
 
 #include "gact_lin.hpp"
+#include "gact_walk_pos.hpp"
 
 namespace gact {
 
@@ -58,7 +61,6 @@ __device__ __forceinline__ void coop_walk_batch(const KParams &kp, const uint32_
 {
     constexpr int CW = L::kWalkCols, QN = L::kWalkQuads, ROW = kWsRow;
     constexpr int kSeg = StageGeom<L::kSlotsPerLane, L::kLanes>::kSeg;
-    constexpr uint32_t kMagic = (65536u + CW - 1) / CW;
     constexpr uint32_t kM = 3u, kI = 2u, kD = 1u;               // align.h:23 numbering, as the pass tags them
     typedef __attribute__((address_space(3))) const uint8_t LdsByte;
     typedef __attribute__((address_space(3))) const uint32_t LdsWord;
@@ -78,7 +80,7 @@ __device__ __forceinline__ void coop_walk_batch(const KParams &kp, const uint32_
     if ((st0 & 3u) == 1u) active = atomicCAS(&jstate[lane], st0, st0 + 1u) == st0;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     if (!__any(active)) return;
-    int p0 = 0, kA = 0, nlim_i = 0, nlim_j = 0, nis = 0, njs = 0, v = 0, v0 = 0, band_lim = -1;
+    int kA = 0, nlim_i = 0, nlim_j = 0, nis = 0, njs = 0, v0 = 0, band_lim = -1;
     uint32_t ws_off = 0;
     int rpos0 = 0, qpos0 = 0, dir = 0, seg = 0;
     int l = 0, c = 0, k = 0;
@@ -90,77 +92,93 @@ __device__ __forceinline__ void coop_walk_batch(const KParams &kp, const uint32_
         int l0, c0, k0;
         L::walk_start(R, Q, 0, l0, c0, k0);                       // (lane and column of (R, Q); the step comes with the job)
         k0 = jb.k0;
-        p0 = l0 * CW + c0; kA = k0 - l0;
+        kA = k0 - l0;
         nlim_i = -imin(early, R); nlim_j = -imin(early, Q);
         const bool rev = (jb.where >> 16) & 1u;
         seg = (int)(jb.where >> 17);
         dir = rev ? -1 : 1;                                        // a step up the tile (nis - 1): slice index + 1 when reversed
         rpos0 = (int)(jb.where & 0xffu) + (rev ? 0 : R - 1);
         qpos0 = (int)((jb.where >> 8) & 0xffu) + (rev ? 0 : Q - 1);
-        v = v0;
         l = l0; c = c0; k = k0;
-        go = (R >= 1) & (Q >= 1) & (early > 0) & (v != 0);
+        go = (R >= 1) & (Q >= 1) & (early > 0) & (v0 != 0);
     }
     uint32_t cur = 0, rcode = 0, qcode = 0;
     TbRegion<CW> rg;
     rg.l0 = 0; rg.fbase[0] = rg.fbase[1] = rg.fbase[2] = 0; rg.qbase0 = 0;
-    int off0 = 0, off1 = 0;
-    auto fetch = [&](int fl, int fc, int fk) {
-        const int off = fl == rg.l0 ? off0 : off1;
-        const uint32_t row = ((uint32_t)fk >> 3 << 5) + (uint32_t)off;
-        const uint32_t w = *(LdsWord *)(cache + (((uint32_t)fc >> 1 << 2) + row));
-        return __builtin_amdgcn_ubfe(w, (((uint32_t)fc & 1u) << 4) + 14u - (((uint32_t)fk & 7u) << 1), 2u);
+    // What a trip (a refill and its eight moves) keeps, gact_walk_pos.hpp: the column relative to lane rg.l0 (cr < 0: in
+    // the lane before), its clamp, kA + rg.l0, and the byte address of column 0's half-word in the region cache for lane
+    // rg.l0 (off_a) and what the lane before adds to it (off_d).  A finished lane keeps those of its last refill.
+    int cr = 0, cr_min = 0, k_lane = 0, dv = 0;
+    uint32_t off_a = 0, off_d = 0;
+    const uint32_t cache_a = (uint32_t)(uintptr_t)cache;                   // LDS byte addresses: the lane's region cache,
+    const uint32_t seg_a = (uint32_t)(uintptr_t)(stage + seg);             // the tile's ref segment (the query's: kSeg words on)
+    // (twice the bit position of a base from LDS address 0: rpos0 + dir * nis bases into the segment, walk_pos2)
+    const int dir2 = 2 * dir, rfix2 = 2 * rpos0 + 8 * (int)seg_a, qfix2 = 2 * qpos0 + 8 * (int)seg_a;
+    // The three LDS reads of a cell -- its column's half-word of pointer codes out of the region cache, the staged words
+    // of its two bases (load_pair_packed: base d of a slice sits at bit 2 * (16 kFront + bit0 + d) of its segment) --
+    // are issued together; what does not need them runs before land() waits for all three at once.
+    uint32_t pw = 0, rw = 0, qw = 0;
+    int rp2 = 0, qp2 = 0;
+    auto issue = [&]() {
+        const uint32_t pa = ((uint32_t)k >> 3 << 5) + (((uint32_t)cr << 1) + off_a) + ((uint32_t)walk_lane_before(cr) & off_d);
+        rp2 = walk_pos2(rfix2, dir2, nis); qp2 = walk_pos2(qfix2, dir2, njs);   // nis, njs <= 0; forward slices are walked downwards
+        const uint32_t ra = ((uint32_t)rp2 >> 3) & ~3u, qa = ((uint32_t)qp2 >> 3) & ~3u;
+        asm volatile("ds_read_u16 %0, %3\n\t"
+                     "ds_read_b32 %1, %4\n\t"
+                     "ds_read_b32 %2, %5 offset:%6"
+                     : "=&v"(pw), "=&v"(rw), "=&v"(qw) : "v"(pa), "v"(ra), "v"(qa), "n"(4 * kSeg) : "memory");
     };
-    // the two bases of the cell the walk stands on, out of the tile's staged slices (load_pair_packed: base d of a slice
-    // sits at bit 2 * (16 kFront + bit0 + d) of its segment)
-    auto bases = [&]() {
-        const int rp = rpos0 + dir * nis, qp = qpos0 + dir * njs;         // nis, njs <= 0; forward slices are walked downwards
-        const uint32_t rw = stage[seg + (rp >> 4)], qw = stage[seg + kSeg + (qp >> 4)];
-        rcode = __builtin_amdgcn_ubfe(rw, ((uint32_t)rp & 15u) << 1, 2u);
-        qcode = __builtin_amdgcn_ubfe(qw, ((uint32_t)qp & 15u) << 1, 2u);
+    auto land = [&]() {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pw), "+v"(rw), "+v"(qw) :: "memory");
+        // (v_bfe_u32 takes the low five bits of its offset: 2 * (position & 15) of a base; a half-word's rows run from bit 14 down)
+        cur = __builtin_amdgcn_ubfe(pw, (uint32_t)(__mul24(k, -2) + 14) & 15u, 2u);
+        rcode = __builtin_amdgcn_ubfe(rw, (uint32_t)rp2, 2u);
+        qcode = __builtin_amdgcn_ubfe(qw, (uint32_t)qp2, 2u);
     };
 #ifdef GACT_STAMPS
     unsigned long long n_trips = 0, n_lane_trips = 0;
 #endif
-    // ---- refill (every walking lane at the same trip: one memory round trip), then eight moves: walk_chain_lin, statement
-    //      for statement
+    // ---- refill (every walking lane at the same trip: one memory round trip), then eight moves: walk_chain_lin's, move for
+    //      move, as straight-line code.  `go` and `redo` are data: a lane that has finished rides along to the end of the
+    //      trip and every update of its state is masked by `go`, so its nis, njs, dv, l, c, k and redo stay what they were --
+    //      no branch inside a move, one wave-uniform test per trip (`go` only ever falls).
     while (__any(go)) {
         if (go) {
             tb_refill_oct<CW, QN, ROW>(ws_all, ws_off, scratch, l, c, k, rg);
-            off0 = 4 * (-8 * rg.fbase[0] - 4 * rg.qbase0);
-            off1 = 4 * (16 - 8 * rg.fbase[1] - 4 * (QN - 2));
-            cur = fetch(l, c, k);
-            bases();
+            off_a = cache_a + (uint32_t)(4 * (-8 * rg.fbase[0] - 4 * rg.qbase0));
+            off_d = cache_a + (uint32_t)(4 * (16 - 8 * rg.fbase[1] - 4 * (QN - 2)) + 2 * CW) - off_a;
+            walk_trip_begin<CW>(l, c, cr, cr_min);
+            k_lane = kA + l;
+            issue();
+            land();
         }
-#pragma unroll 1
+#pragma unroll
         for (int m = 0; m < 8; m++) {
-            if (!__any(go)) break;
 #ifdef GACT_STAMPS
-            n_trips++; n_lane_trips += (unsigned long long)__builtin_popcountll(__ballot(go));
+            n_trips += __any(go) ? 1ull : 0ull; n_lane_trips += (unsigned long long)__builtin_popcountll(__ballot(go));
 #endif
-            if (go) {
-                const bool diag = cur == kM;
-                const int sub = rcode == qcode ? v_match : v_mism;
-                v -= diag ? sub : v_gap;
-                nis -= cur != kD;
-                njs -= cur != kI;
-                const int p = imax(p0 + njs, 0);
-                l = (int)(__umul24((uint32_t)p, kMagic) >> 16);
-                c = p + __mul24(l, -CW);
-                k = imax(kA + l + nis, 0);
-                if (m == 7) {
-                    // (the next refill is due: still a refill's worth of moves inside the stored band?  gact_lin.hpp LinBand)
-                    redo = redo | ((band_lim >= 0) & ((unsigned)(nis - njs + band_lim) > (unsigned)(2 * band_lim)));
-                } else {
-                    cur = fetch(l, c, k);
-                    bases();
-                }
-                go = !((diag && v == 0) || nis <= nlim_i || njs <= nlim_j || redo);
+            const bool diag = cur == kM;
+            const int sub = rcode == qcode ? v_match : v_mism;
+            const int cost = diag ? sub : v_gap;
+            dv += go ? cost : 0;
+            nis -= (int)(go & (cur != kD));
+            const int dj = (int)(go & (cur != kI));
+            njs -= dj;
+            walk_col_left(cr, cr_min, dj);
+            k = imax(k_lane + nis + walk_lane_before(cr), 0);
+            if (m == 7) {
+                // (the next refill is due: still a refill's worth of moves inside the stored band?  gact_lin.hpp LinBand)
+                redo = redo | (go & (band_lim >= 0) & ((unsigned)(nis - njs + band_lim) > (unsigned)(2 * band_lim)));
+            } else {
+                issue();
             }
+            go = go & !((diag && dv == v0) || nis <= nlim_i || njs <= nlim_j || redo);
+            if (m != 7) land();
         }
+        walk_trip_end<CW>(rg.l0, cr, l, c);
     }
     if (active) {
-        done[lane].ref_steps = -nis; done[lane].query_steps = -njs; done[lane].dv = v0 - v; done[lane].redo = redo ? 1 : 0;
+        done[lane].ref_steps = -nis; done[lane].query_steps = -njs; done[lane].dv = dv; done[lane].redo = redo ? 1 : 0;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __hip_atomic_store(&jstate[lane], st0 + 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
