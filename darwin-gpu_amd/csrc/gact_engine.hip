@@ -193,6 +193,18 @@ template <class Stats> struct PassScratch {
 
 inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
+// What a run ran as, for gact_hip_last_run_stats: reset by launch_run, filled by the launches (gact_launch.hpp); a merged launch's
+// is copied into its record
+struct RunShape {
+    bool two_phase = false;              // seed launch + packed main launch(es)
+    bool wide = false, lin = false, aff = false;       // the first pass's main launch: wide layout, linear-gap pass, drifted affine pass
+    bool overlapped = false;             // seeded while its main launch was running
+    bool lane = false;                   // had a critical lane (a wide main launch beside the split one)
+    bool side_used = false;              // had launches on the side lane
+    int routed_raw = 0;                  // candidates aligned from raw bytes beside the 2-bit launches
+    int roles = 0;                       // main launch(es) with DP waves and walker waves (1, gact_roles.hpp) / cooperative walks (2, gact_coop.hpp)
+};
+
 // The figures of ONE merged launch: events and counters of its own, recorded / copied behind that launch and
 // never touched again, so that a caller that asks for its run's statistics after its fetch reads them whatever the merge
 // slot is doing by then (the slot's own events and counters are re-recorded as soon as its arrays are free).  Records are
@@ -200,8 +212,7 @@ inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 struct LaunchStats {
     hipEvent_t ev0 = nullptr, ev_mid = nullptr, ev1 = nullptr, ev_done = nullptr;
     int *h_counter = nullptr;            // pinned: 2 x kCounterInts ints (the lane's own, the side lane's)
-    bool two_phase = false, wide = false, lin = false, aff = false, overlapped = false, lane = false, side_used = false;
-    int routed_raw = 0, roles = 0;
+    RunShape shape;
     void release()
     {
         if (ev0) (void)hipEventDestroy(ev0);
@@ -215,7 +226,8 @@ struct LaunchStats {
 struct Slot {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_mid = nullptr;
-    bool timed = false, two_phase = false, wide = false, lin = false, aff = false;
+    bool timed = false;
+    RunShape shape;                      // of the last run on this slot's own launches
     // the run's three times as gact_hip_last_run_stats first read them: the runtime makes an elapsed time from its events anew
     // at every reading and two readings of the same events differ by a nanosecond now and then, so a run's times are read once
     // and kept until the slot's events are recorded again (forget_times)
@@ -231,17 +243,14 @@ struct Slot {
                                          // empty for lists the device filter made (valid by construction)
     int64_t checked_key[4] = {-1, -1, -1, -1};   // {first, n, rc_from, sets_epoch} of the last range that passed the check
     DevBuf<gact_overlap> overlaps;
-    int *d_counter = nullptr;            // see queues()
+    int *d_counter = nullptr;            // see queues() (gact_launch.hpp)
     DevBuf<int> live;
-    DevBuf<int> deferred;                // route_kernel's two candidate lists (launch_extend), n entries each
+    DevBuf<int> deferred;                // route_kernel's two candidate lists (gact_launch.hpp launch_extend), n entries each
     DevBuf<int> order;                   // ordered seeding: the run's candidates by length class, longest first (run_overlapped)
     hipStream_t aux_stream = nullptr;    // overlapped seeding: the second seed launch and the main launch behind it
     hipEvent_t aux_ev_a = nullptr, aux_ev_b = nullptr;
     long merge_gen = -1;                 // which merged launch carried this slot's last run (Combiner::merged_launches then): its peers have the same
     long merge_prev_gen = -1;            // ... and the one before that (two halves of a group that came apart have it in common)
-    bool overlapped = false;             // the last run seeded while its main launch was running
-    bool lane = false;                   // ... had a critical lane (a wide main launch beside the split one)
-    int roles = 0;                       // ... ran its main launch(es) with DP waves and walker waves (1, gact_roles.hpp) / cooperative walks (2, gact_coop.hpp)
     // call combiner (Combiner below; all under its mutex)
     std::thread::id last_thread;         // who called last for this slot, and when: is a run from it likely soon?
     std::chrono::steady_clock::time_point last_call{};
@@ -250,12 +259,11 @@ struct Slot {
     int merged_callers = 1;              // how many callers' runs that launch carried
     std::shared_ptr<LaunchStats> merged_stats;   // ... and that launch's own figures (written by the leader before the run counts as launched)
     hipEvent_t ev_ready = nullptr;       // candidates of this slot are in place (recorded before a merged gather)
-    int routed_raw = 0;                  // how many candidates the last run aligned from raw bytes beside the 2-bit launches
     DevBuf<gact::ChainState> chain_states;
     uint32_t *d_ws = nullptr;
     int *d_flags = nullptr;
     // side lane: queues, workspace and stream of the raw-byte launches that run BESIDE the 2-bit launches of a routed
-    // run (launch_extend); made on first use
+    // run (gact_launch.hpp launch_extend); made on first use
     hipStream_t side_stream = nullptr;
     hipEvent_t side_go = nullptr;          // route_kernel has run: the side lane's launches may read its lists
     hipEvent_t side_done = nullptr;
@@ -263,10 +271,9 @@ struct Slot {
     DevBuf<int> side_live;
     uint32_t *side_ws = nullptr;
     int side_blocks = 0;                 // grid the side workspace is sized for
-    bool side_used = false;              // the last run had launches on it
     int stream_index = -1;              // of `stream` in the process's pool (StreamPool)
     int64_t routed_key[4] = {-1, -1, -1, -1};   // (first, n, rc_from, sets_epoch) routed_host was counted for
-    int routed_host[2] = {0, 0};        // candidates of that range whose reads are plain A/C/G/T / the rest (launch_extend)
+    int routed_host[2] = {0, 0};        // candidates of that range whose reads are plain A/C/G/T / the rest (gact_launch.hpp count_routed)
     gact_candidate *h_stage = nullptr;  // pinned staging for candidates_upload: hipMemcpyAsync from the caller's pageable array
     size_t h_stage_cap = 0;             // has the runtime pin those pages first, and with eight feeder threads at it at once
                                         // that call took 8 ms for some of them (profiles/r04/upload_trace_*.txt)
@@ -528,7 +535,7 @@ struct gact_hip_engine {
     std::atomic<bool> caller_keeps_runs_in_flight{false};      // set_option("runs_in_flight", 1): the caller says so itself -- every launch takes the throughput layout
     bool team_when_shared = false;      // GACT_HIP_TEAM_WHEN_SHARED=1: a split linear-gap launch that shares the machine walks by teams
     bool overlap_seed = true;   // GACT_HIP_NO_OVERLAP unset: a large run on an idle engine seeds in length order, most of it beside its main launch
-    bool side_lane = true;      // GACT_HIP_NO_SIDE_LANE unset: few raw-byte candidates run beside the 2-bit launches (launch_extend)
+    bool side_lane = true;      // GACT_HIP_NO_SIDE_LANE unset: few raw-byte candidates run beside the 2-bit launches (gact_launch.hpp launch_extend)
     bool route_other = true;    // GACT_HIP_NO_ROUTING unset: raw-byte kernels only for candidates with a non-ACGT read
     bool chain_prio = true;     // main launch: longest chains first in the DP issue order too
     bool static_prio = false;   // GACT_HIP_STATIC_PRIO: fixed thresholds instead of the ranking (read once, at create)
@@ -600,9 +607,6 @@ void note_call(gact_hip_engine *e, int slot)
 constexpr int kMoreCount = 8 + 2 * gact::kBuckets + gact::kEpochs, kMorePop = kMoreCount + gact::kBuckets;
 constexpr int kOrderHist = kMorePop + gact::kBuckets, kOrderCursor = kOrderHist + gact::kBuckets;
 constexpr int kCounterInts = kOrderCursor + gact::kBuckets;
-
-// GACT_HIP_POISON_WS: seeded garbage over the slot's whole traceback workspace (poison_kernel)
-int poison_ws(gact_hip_engine *e, Slot &sl, uint32_t salt);
 
 // The slots' streams belong to the process, not to an engine: slot k of every engine on a device runs on the k-th stream the
 // process made there.  The runtime deals a process's streams onto few hardware queues (four unless GPU_MAX_HW_QUEUES says
@@ -751,53 +755,6 @@ int launch_tiles(gact_hip_engine *e, Slot &sl, const SeqSet &rs, const SeqSet &q
     return 0;
 }
 
-// what a seed launch + main launch pair runs on: the slot's own stream, counters, hand-off lists and workspace, or
-// the slot's side lane.  Chain states and records are indexed by candidate and shared.
-struct Lane {
-    hipStream_t stream;
-    int *d_counter;
-    int *live;
-    size_t live_cap;
-    uint32_t *d_ws;
-    size_t ws_words;
-    int max_blocks;                      // 0: whatever the kernel's occupancy allows (the workspace is sized for it)
-};
-
-Lane main_lane(gact_hip_engine *e, Slot &sl) { return Lane{sl.stream, sl.d_counter, sl.live.p, sl.live.cap, sl.d_ws, e->ws_words_total, 0}; }
-
-gact::ChainQueues queues(const Lane &ln, Slot &sl)
-{
-    gact::ChainQueues q;
-    q.pop_seed = ln.d_counter;
-    q.seed_cells = reinterpret_cast<unsigned long long *>(ln.d_counter + 2);
-    q.bucket_count = ln.d_counter + 8;
-    q.bucket_pop = ln.d_counter + 8 + gact::kBuckets;
-    q.live = ln.live;
-    q.live_stride = (int)(ln.live_cap / (2 * gact::kBuckets));       // (the second half: the second set of overlapped seeding)
-    q.states = sl.chain_states.p;
-    q.longest_now = ln.d_counter + 8 + 2 * gact::kBuckets;
-    q.band_redos = ln.d_counter + 6;
-    q.list_count = nullptr;
-    q.list = nullptr;
-    q.list_n = -1;
-    q.more_flag = nullptr;
-    q.more_count = q.more_pop = q.more_live = nullptr;
-    q.leave_longest = 0;
-    return q;
-}
-
-// the second stream of overlapped seeding (run_pass)
-int ensure_aux_stream(Slot &sl)
-{
-    if (sl.aux_stream) return 0;
-    int lo = 0, hi = 0;
-    HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    HIP_TRY(hipStreamCreateWithPriority(&sl.aux_stream, hipStreamNonBlocking, hi));
-    HIP_TRY(hipEventCreateWithFlags(&sl.aux_ev_a, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&sl.aux_ev_b, hipEventDisableTiming));
-    return 0;
-}
-
 // device arrays of a slot for a list of n candidates
 int reserve_candidates(Slot &sl, size_t n)
 {
@@ -805,453 +762,7 @@ int reserve_candidates(Slot &sl, size_t n)
             sl.deferred.reserve(2 * n) || sl.order.reserve(n)) ? -1 : 0;
 }
 
-// the second set of queues of a lane as a launch's own set
-gact::ChainQueues second_queues(const Lane &ln, Slot &sl)
-{
-    gact::ChainQueues q = queues(ln, sl);
-    q.pop_seed = ln.d_counter + 1;
-    q.bucket_count = ln.d_counter + kMoreCount;
-    q.bucket_pop = ln.d_counter + kMorePop;
-    q.live = ln.live + (size_t)gact::kBuckets * q.live_stride;
-    return q;
-}
-
-int poison_lane(gact_hip_engine *e, const Lane &ln, uint32_t salt)
-{
-    if (!e->poison) return 0;
-    hipLaunchKernelGGL(gact::poison_kernel, dim3(e->prop.multiProcessorCount * 8), dim3(256), 0, ln.stream, ln.d_ws,
-                       ln.ws_words + 64, e->poison * 0x01000193u + salt);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int poison_ws(gact_hip_engine *e, Slot &sl, uint32_t salt) { return poison_lane(e, main_lane(e, sl), salt); }
-
-size_t ws_words_for(const gact_hip_engine *e, int blocks)
-{
-    const size_t groups = (size_t)blocks * (gact::kBlockThreads / 64) * gact::kGroupsPerWave;
-    return groups * gact::kSlots * (size_t)e->kp.ws_words;             // two tiles per group in the p16 kernel
-}
-
-// the side lane of a slot, for `count` candidates on at most `blocks` blocks
-int side_lane(gact_hip_engine *e, Slot &sl, int count, int blocks, Lane *out)
-{
-    if (!sl.side_stream) {
-        int lo = 0, hi = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        // ahead of the slot's own stream: its main launch must find room while the 2-bit seed launch drains
-        HIP_TRY(hipStreamCreateWithPriority(&sl.side_stream, hipStreamNonBlocking, hi));
-        HIP_TRY(hipEventCreateWithFlags(&sl.side_done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&sl.side_go, hipEventDisableTiming));
-        HIP_TRY(hipMalloc((void **)&sl.side_counter, kCounterInts * sizeof(int)));
-    }
-    if (blocks > sl.side_blocks) {
-        if (sl.side_ws) (void)hipFree(sl.side_ws);
-        sl.side_ws = nullptr; sl.side_blocks = 0;
-        if (hipMalloc((void **)&sl.side_ws, (ws_words_for(e, blocks) + 64) * sizeof(uint32_t)) != hipSuccess)
-            return fail(GACT_HIP_ENOMEM, "side workspace allocation failed (%zu MiB)", ws_words_for(e, blocks) * 4 >> 20);
-        sl.side_blocks = blocks;
-        HIP_TRY(hipMemsetAsync(sl.side_ws, 0xA5, (ws_words_for(e, blocks) + 64) * sizeof(uint32_t), sl.side_stream));
-    }
-    if (sl.side_live.reserve(2 * (size_t)count * gact::kBuckets)) return fail(GACT_HIP_ENOMEM, "device allocation failed");
-    *out = Lane{sl.side_stream, sl.side_counter, sl.side_live.p, sl.side_live.cap, sl.side_ws, ws_words_for(e, sl.side_blocks), sl.side_blocks};
-    return 0;
-}
-
-// int32 kernel alone, or (scoring permitting) int32 seed launch for the first
-// tiles followed by the packed-int16 main launch for the rest of every chain
-int launch_big_extend(gact_hip_engine *e, Slot &sl, int first, int n, int rc_from, int same_file)
-{
-    const SeqSet &rs = e->sets[GACT_SET_REF];
-    const SeqSet &qf = e->sets[GACT_SET_QUERY], &qr = e->sets[GACT_SET_QUERY_RC];
-    sl.two_phase = false; sl.routed_raw = 0; sl.side_used = false;
-    const Lane own = main_lane(e, sl);
-    const int blocks = std::max(1, std::min((n + 3) / 4, e->big_blocks));
-    auto k = e->big_cb == 16 ? gact::big_extend_kernel<16> : gact::big_extend_kernel<32>;
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(gact::kBlockThreads), 0, sl.stream, e->kp, rs.dev(true), qf.dev_or(true, rs),
-                       qr.dev_or(true, rs), sl.cands.p, first, n, rc_from, same_file, sl.overlaps.p, queues(own, sl),
-                       reinterpret_cast<uint8_t *>(sl.d_ws));
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// the engine's capabilities as the launch policy sees them (gact_policy.hpp)
-gact_policy::Caps policy_caps(const gact_hip_engine *e)
-{
-    gact_policy::Caps c;
-    c.C = e->C; c.p16 = e->p16; c.seed16 = e->seed16; c.lin = e->lin; c.aff = e->aff; c.aff_seed = e->aff_seed; c.split = e->split; c.tagged = e->tagged;
-    c.mismatch_below_extend = e->params.mismatch < e->params.gap_extend;
-    c.shared_twelfths = e->shared_twelfths; c.lone_lane = e->lone_lane; c.overlap_big = e->overlap_big; c.roles = e->roles; c.coop = (e->lin && e->split && e->C == 20) ? e->coop : -1; c.overlap_seed = e->overlap_seed; c.crit_lane = e->crit_lane; c.crit_lane_always = e->crit_lane_always;
-    c.lane_small = e->lane_small; c.lane_small_factor = e->lane_small_factor; c.lane_blocks = e->lane_blocks; c.team_when_shared = e->team_when_shared;
-    c.wide = e->wide; c.wide_blocks_per_cu = e->wide_blocks_per_cu; c.cus = e->prop.multiProcessorCount;
-    c.grid_blocks = e->grid_blocks; c.seed_grid_blocks = e->seed_grid_blocks; c.seed_lin_grid_blocks = e->seed_lin_grid_blocks;
-    c.lin_grid_blocks = e->lin_grid_blocks; c.aff_grid_blocks = e->aff_grid_blocks; c.wide_lin_grid_blocks = e->wide_lin_grid_blocks;
-    c.role_grid_blocks = e->role_grid_blocks; c.role_dp_waves = gact::kRoleDp;
-    c.ws_words_per_tile = (size_t)e->kp.ws_words;
-    c.role_ws_words_per_block = gact::role_ws_words<gact::SplitLayoutLin<7, 13>>(1);
-    c.coop_ws_words_per_block = gact::coop_ws_words<gact::SplitLayoutLin<7, 13>>(1);
-    return c;
-}
-
-// strands: -1 what [first, first + n) and rc_from say; else bit 0 = forward-strand candidates present, bit 1 =
-// reverse-complement ones (merged runs: rc_from == kCompInCand, the strand travels with the candidate)
-template <int C>
-int launch_extend(gact_hip_engine *e, Slot &sl, int first, int n, int rc_from, int same_file, int strands = -1)
-{
-    const SeqSet &rs = e->sets[GACT_SET_REF];
-    const SeqSet &qf = e->sets[GACT_SET_QUERY], &qr = e->sets[GACT_SET_QUERY_RC];
-    const bool need_f = strands >= 0 ? (strands & 1) != 0 : first < rc_from, need_r = strands >= 0 ? (strands & 2) != 0 : first + n > rc_from;
-    // Sets that hold bytes other than A/C/G/T (N, lower case) are compared as raw bytes like align.cpp:134.  With the
-    // packed kernels that is decided per CANDIDATE: the launches on the 2-bit image put off every candidate one of whose
-    // two reads holds such a byte (SeqSetDev::other, from pack_kernel), and a second pair of launches on the raw bytes
-    // takes those -- one soft-masked read no longer moves a whole launch onto the slower kernels.
-    const bool any_other = rs.has_other || (need_f && qf.has_other) || (need_r && qr.has_other);
-    const bool mixed = any_other && e->p16 && e->route_other;
-    gact::KParams kp = e->kp;
-    const int64_t longest = std::min(rs.max_len, std::max(need_f ? qf.max_len : 0, need_r ? qr.max_len : 0));
-    // GACT_HIP_STATIC_PRIO: thirds of the longest possible chain instead of the ranking against what is running
-    const bool static_prio = e->static_prio;
-    kp.prio_bases[0] = !e->chain_prio ? 0x7fffffff : static_prio ? (int32_t)std::min<int64_t>(longest / 3, 0x7fffffff) : 0;
-    const int rank16 = e->rank16;                    // above 3/4 of the longest running chain: priority 2, above 1/2: 1
-    kp.prio_bases[1] = !e->chain_prio ? 0x7fffffff : static_prio ? (int32_t)std::min<int64_t>(2 * longest / 3, 0x7fffffff) : rank16;
-    sl.two_phase = e->p16;
-    sl.routed_raw = 0;
-    sl.overlapped = false;
-    sl.lane = false;
-    sl.roles = 0;
-    // Is another slot of this engine still running?  Then this launch shares the machine (feeder threads, steps in
-    // flight) and what counts is throughput: the wide layout -- faster per chain, slower per cell, made for a launch
-    // that has the CUs to itself and lasts as long as its longest chain -- is not taken on its own account.
-    bool shared_machine = e->caller_keeps_runs_in_flight.load(std::memory_order_relaxed);
-    if (e->shared_hint && !shared_machine)
-        for (const Slot &other : e->slots)
-            if (&other != &sl && other.timed && other.ev1 && hipEventQuery(other.ev1) == hipErrorNotReady) { shared_machine = true; break; }
-    (void)hipGetLastError();                 // (hipErrorNotReady is an answer, not a failure)
-
-    // one seed launch + (packed kernels) one main launch over `count` candidates at most
-    // GACT_HIP_TRACE: every launch named on stderr and waited for (a faulting kernel is the last one named)
-    static const bool trace = opt_env("trace") != nullptr;
-    auto traced = [&](const Lane &ln, const char *what, int blocks, int count) -> int {
-        if (!trace) return 0;
-        fprintf(stderr, "[gact_hip] %s: %d blocks, %d candidates ... ", what, blocks, count);
-        fflush(stderr);
-        HIP_TRY(hipStreamSynchronize(ln.stream));
-        int dbg[8];
-        HIP_TRY(hipMemcpy(dbg, ln.d_counter, sizeof dbg, hipMemcpyDeviceToHost));
-        fprintf(stderr, "done (popped %d)\n", dbg[0]);
-        return 0;
-    };
-    // second_set: the pass files and pops its chains in the lane's second set of queues (the raw-byte pass behind the 2-bit
-    // one on the same lane: the first set keeps its counts for the statistics, nothing is cleared between the passes).
-    // WHAT the pass runs as -- kernels, grids, sequence -- is gact_policy::plan_pass's answer (gact_policy.hpp: a pure function
-    // of the count and the engine's capabilities); what follows launches it.
-    auto run_pass = [&](const Lane &ln, bool raw, const int *list, const int *list_count, int count, bool first_pass, bool second_set = false) -> int {
-        namespace pol = gact_policy;
-        pol::Inputs in;
-        in.count = count; in.raw = raw; in.listed = list != nullptr; in.second_set = second_set; in.shared_machine = shared_machine;
-        in.own_lane = ln.stream == sl.stream; in.trace = trace; in.poison = e->poison != 0; in.lane_max_blocks = ln.max_blocks;
-        const pol::Plan plan = pol::plan_pass(policy_caps(e), in);
-        const gact::SeqSetDev d_rs = rs.dev(raw), d_qf = qf.dev_or(raw, rs), d_qr = qr.dev_or(raw, rs);
-        gact::ChainQueues cq = second_set ? second_queues(ln, sl) : queues(ln, sl);
-        cq.list = list; cq.list_count = list_count;
-        if (trace) {
-            fprintf(stderr, "[gact_hip] pass raw=%d listed=%d side=%d count=%d first=%d n=%d rc_from=%d plan=%s\n", (int)raw, list != nullptr,
-                    ln.stream != sl.stream, count, first, n, rc_from, pol::describe(plan).c_str());
-            fprintf(stderr, "[gact_hip]   ws %p + %zu MiB, counter %p, cands %p (%zu), overlaps %p, live %p (%zu), states %p (%zu x %zu B)\n", (void *)ln.d_ws,
-                    ln.ws_words * 4 >> 20, (void *)ln.d_counter, (void *)sl.cands.p, sl.cands.cap, (void *)sl.overlaps.p, (void *)ln.live,
-                    ln.live_cap, (void *)sl.chain_states.p, sl.chain_states.cap, sizeof(gact::ChainState));
-            fprintf(stderr, "[gact_hip]   ref raw %p packed %p offsets %p (%lld bases), query %p %p, rc %p %p\n", (void *)rs.d_raw, (void *)rs.d_packed,
-                    (void *)rs.d_offsets, (long long)rs.total, (void *)qf.d_raw, (void *)qf.d_packed, (void *)qr.d_raw, (void *)qr.d_packed);
-        }
-        using gact::extend_p16_kernel;
-        using RolesL = gact::SplitLayoutLin<7, 13>;
-        using RowL = gact::SplitLayoutLinRow<7, 13>;     // the same launches on the row-drifted pass (gact_lin.hpp 12.)
-        using RowTeamL = gact::SplitLayoutLinRowTeam<7, 13>;
-        const bool lin_row = e->lin_row;
-        // a main launch of the plan's kernel: the same arguments whatever the kernel
-        auto launch_main = [&](pol::MainK k, bool two_sets, int blocks, hipStream_t stream, const gact::ChainQueues &q, uint32_t *ws) -> int {
-            using M = pol::MainK;
-            const dim3 g((unsigned)blocks), b256(gact::kBlockThreads), brole(gact::kRoleThreads);
-#define GACT_LAUNCH_MAIN(KERNEL, BLOCK) hipLaunchKernelGGL(KERNEL, g, BLOCK, 0, stream, kp, e->kc, d_rs, d_qf, d_qr, same_file, sl.overlaps.p, q, ws)
-            if constexpr (C == 20) {
-                if (lin_row) switch (k) {
-                case M::RolesLin: if (two_sets) GACT_LAUNCH_MAIN((gact::extend_roles_kernel<RowL, true>), brole); else GACT_LAUNCH_MAIN((gact::extend_roles_kernel<RowL, false>), brole); break;
-                case M::CoopLin: if (two_sets) GACT_LAUNCH_MAIN((gact::extend_coop_kernel<RowL, true>), b256); else GACT_LAUNCH_MAIN((gact::extend_coop_kernel<RowL, false>), b256); break;
-                case M::SplitLin: if (two_sets) GACT_LAUNCH_MAIN((extend_p16_kernel<RowL, false, true>), b256); else GACT_LAUNCH_MAIN((extend_p16_kernel<RowL, false>), b256); break;
-                case M::SplitLinTeam: GACT_LAUNCH_MAIN((extend_p16_kernel<RowTeamL, false>), b256); break;
-                default: break;
-                }
-                const bool row_done = lin_row && (k == M::RolesLin || k == M::CoopLin || k == M::SplitLin || k == M::SplitLinTeam);
-                if (!row_done) switch (k) {
-                case M::RolesLin: if (two_sets) GACT_LAUNCH_MAIN((gact::extend_roles_kernel<RolesL, true>), brole); else GACT_LAUNCH_MAIN((gact::extend_roles_kernel<RolesL, false>), brole); break;
-                case M::CoopLin: if (two_sets) GACT_LAUNCH_MAIN((gact::extend_coop_kernel<RolesL, true>), b256); else GACT_LAUNCH_MAIN((gact::extend_coop_kernel<RolesL, false>), b256); break;
-                case M::SplitLin: if (two_sets) GACT_LAUNCH_MAIN((extend_p16_kernel<gact::SplitLayoutLin<7, 13>, false, true>), b256); else GACT_LAUNCH_MAIN((extend_p16_kernel<gact::SplitLayoutLin<7, 13>, false>), b256); break;
-                case M::SplitLinTeam: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::SplitLayoutLinTeam<7, 13>, false>), b256); break;
-                case M::WideLin: if (two_sets) GACT_LAUNCH_MAIN((extend_p16_kernel<gact::WideLayoutLin, false, true>), b256); else GACT_LAUNCH_MAIN((extend_p16_kernel<gact::WideLayoutLin, false>), b256); break;
-                case M::SplitAffNeg: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::SplitLayoutAff<7, 13, true>, false>), b256); break;
-                case M::SplitAff: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::SplitLayoutAff<7, 13, false>, false>), b256); break;
-                default: break;
-                }
-            }
-            switch (k) {
-            case M::WideTaggedRaw: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::WideLayoutTagged, true>), b256); break;
-            case M::WideTagged: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::WideLayoutTagged, false>), b256); break;
-            case M::WideRaw: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::WideLayout, true>), b256); break;
-            case M::Wide: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::WideLayout, false>), b256); break;
-            case M::SplitTaggedRaw: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::SplitLayout<7, 13, true>, true>), b256); break;
-            case M::SplitTagged: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::SplitLayout<7, 13, true>, false>), b256); break;
-            case M::SplitRaw: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::SplitLayout<7, 13>, true>), b256); break;
-            case M::Split: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::SplitLayout<7, 13>, false>), b256); break;
-            case M::UniformTaggedRaw: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::UniformLayout<C, gact::kGroup, true>, true>), b256); break;
-            case M::UniformTagged: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::UniformLayout<C, gact::kGroup, true>, false>), b256); break;
-            case M::UniformRaw: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::UniformLayout<C>, true>), b256); break;
-            case M::Uniform: GACT_LAUNCH_MAIN((extend_p16_kernel<gact::UniformLayout<C>, false>), b256); break;
-            default: break;
-            }
-#undef GACT_LAUNCH_MAIN
-            HIP_TRY(hipGetLastError());
-            return 0;
-        };
-        auto launch_seed = [&](pol::SeedK k, int blocks, hipStream_t stream, const gact::ChainQueues &q, uint32_t *ws) -> int {
-            using S = pol::SeedK;
-            const dim3 g((unsigned)blocks), b256(gact::kBlockThreads);
-#define GACT_LAUNCH_SEED(KERNEL) hipLaunchKernelGGL(KERNEL, g, b256, 0, stream, kp, e->kc, d_rs, d_qf, d_qr, sl.cands.p, first, n, rc_from, same_file, sl.overlaps.p, q, ws)
-            if constexpr (C == 20) {
-                switch (k) {
-                case S::P16Lin: GACT_LAUNCH_SEED((gact::seed_p16_kernel<C, false, 1>)); break;
-                case S::P16Aff: GACT_LAUNCH_SEED((gact::seed_p16_kernel<C, false, 2>)); break;
-                case S::P16AffNeg: GACT_LAUNCH_SEED((gact::seed_p16_kernel<C, false, 3>)); break;
-                default: break;
-                }
-            }
-            switch (k) {
-            case S::P16Raw: GACT_LAUNCH_SEED((gact::seed_p16_kernel<C, true>)); break;
-            case S::P16: GACT_LAUNCH_SEED((gact::seed_p16_kernel<C, false>)); break;
-            case S::Int32:
-                hipLaunchKernelGGL((gact::chain_kernel<C, gact::SeedSink>), g, b256, 0, stream, kp, d_rs, d_qf, d_qr, sl.cands.p, n, rc_from,
-                                   same_file, sl.overlaps.p, q, gact::SeedSink{first, e->p16 ? 1 : 0}, ws);
-                break;
-            default: break;
-            }
-#undef GACT_LAUNCH_SEED
-            HIP_TRY(hipGetLastError());
-            return 0;
-        };
-        int rc = 0;
-        // Overlapped, ordered seeding (round 4).  One at a time a run was: seed launch (every first tile, ~2 ms on ecoli10x) ->
-        // main launch, whose longest chains -- the ones that end last -- started only then.  Here the candidates are first
-        // sorted by the length class of the chain they can make (two tiny launches), and
-        //   slot stream : seed launch A (the longest nA: as many as main launch 1 has tile slots)  ->  main launch 1, on two
-        //                 thirds of the resident blocks, popping set 1 (A's hand-offs), later set 2
-        //   aux stream  : [after A] seed launch B (the rest, on the last third of the blocks, into a SECOND set of queues)
-        //                 -> flag -> main launch 2 (that third of the blocks, set 2)
-        // Every producer / consumer pair of a set of queues is still separated by a launch boundary (or by the flag written
-        // in stream order behind seed launch B plus an acquire, extend_p16_kernel): nothing is handed over between running
-        // launches.  The two thirds / one third of the workspace go with the blocks.
-        if (plan.seq == pol::Seq::Overlapped) {
-            if ((rc = ensure_aux_stream(sl))) return rc;
-            const int ob = std::max(1, std::min((count + 255) / 256, 1024));
-            hipLaunchKernelGGL(gact::order_hist_kernel, dim3(ob), dim3(256), 0, ln.stream, sl.cands.p, first, count, rc_from, d_rs.offsets,
-                               d_qf.offsets, d_qr.offsets, kp.early, ln.d_counter + kOrderHist);
-            hipLaunchKernelGGL(gact::order_scatter_kernel, dim3(ob), dim3(256), 0, ln.stream, sl.cands.p, first, count, rc_from,
-                               d_rs.offsets, d_qf.offsets, d_qr.offsets, kp.early, ln.d_counter + kOrderHist,
-                               ln.d_counter + kOrderCursor, sl.order.p);
-            HIP_TRY(hipGetLastError());
-            const int nA = plan.nA;
-            // seed launch A
-            gact::ChainQueues qa = queues(ln, sl);
-            qa.list = sl.order.p; qa.list_n = nA;
-            if ((rc = launch_seed(plan.seed, plan.seed_blocks, ln.stream, qa, ln.d_ws))) return rc;
-            if (first_pass) HIP_TRY(hipEventRecord(sl.ev_mid, ln.stream));
-            HIP_TRY(hipEventRecord(sl.aux_ev_a, ln.stream));
-            // aux stream: seed launch B into the second set, the flag, main launch 2
-            HIP_TRY(hipStreamWaitEvent(sl.aux_stream, sl.aux_ev_a, 0));
-            gact::ChainQueues qb = second_queues(ln, sl);
-            qb.list = sl.order.p + nA; qb.list_n = count - nA;
-            if (count > nA && (rc = launch_seed(plan.seed, plan.seedB_blocks, sl.aux_stream, qb, ln.d_ws + plan.ws_split))) return rc;
-            HIP_TRY(hipMemsetAsync(ln.d_counter + 7, 0xff, sizeof(int), sl.aux_stream));
-            // (both main launches take set 1 -- the longer chains, complete since seed launch A ended -- and then set 2,
-            //  open by the time main launch 2 starts)
-            gact::ChainQueues q2 = queues(ln, sl);
-            {
-                const gact::ChainQueues s2 = second_queues(ln, sl);
-                q2.more_flag = ln.d_counter + 7;
-                q2.more_count = s2.bucket_count; q2.more_pop = s2.bucket_pop; q2.more_live = s2.live;
-            }
-            // (the critical lane, ChainQueues::leave_longest: main launch 2 in the wide layout, main launch 1 leaves it that many
-            //  of the longest chains -- GACT_HIP_CRIT_LANE_ALWAYS; a run this size is bound by throughput)
-            if (count > nA && (rc = launch_main(plan.lane ? pol::MainK::WideLin : plan.main, true, plan.main2_blocks, sl.aux_stream, q2, ln.d_ws + plan.ws_split))) return rc;
-            HIP_TRY(hipEventRecord(sl.aux_ev_b, sl.aux_stream));
-            // main launch 1: set 1, then set 2
-            gact::ChainQueues q1 = q2;
-            q1.leave_longest = plan.leave_longest;
-            if ((rc = launch_main(plan.main, true, plan.main_blocks, ln.stream, q1, ln.d_ws))) return rc;
-            HIP_TRY(hipStreamWaitEvent(ln.stream, sl.aux_ev_b, 0));
-            if (first_pass) { sl.wide = false; sl.lin = true; sl.lane = plan.lane; sl.roles = plan.roles ? 1 : plan.coop ? 2 : 0; }
-            sl.overlapped = true;
-            return 0;
-        }
-        // ---- seed launch, then the main launch(es)
-        if ((rc = launch_seed(plan.seed, plan.seed_blocks, ln.stream, cq, ln.d_ws))) return rc;
-        if ((rc = traced(ln, raw ? "seed launch (raw bytes)" : "seed launch (2-bit)", plan.seed_blocks, count))) return rc;
-        if (plan.seq == pol::Seq::SingleInt32) return 0;
-        if (first_pass) HIP_TRY(hipEventRecord(sl.ev_mid, ln.stream));
-        if ((rc = poison_lane(e, ln, 0x5bd1e995u))) return rc;      // the main launch reads nothing the seed launch stored
-        if (first_pass) { sl.wide = plan.wide; sl.lin = plan.lin; sl.aff = plan.aff; sl.roles = plan.roles ? 1 : plan.coop ? 2 : 0; }
-        if (plan.seq == pol::Seq::CritLane) {
-            // The critical lane beside a run's ONE split main launch (a run too small for overlapped seeding, e.g. the merged
-            // forward-strand calls of eight feeder threads: 33 k chains on 24.6 k tile slots last as long as their longest
-            // chain): the wide launch on a third of the blocks, on the second stream, behind the seed launch like the split one
-            if ((rc = ensure_aux_stream(sl))) return rc;
-            HIP_TRY(hipEventRecord(sl.aux_ev_a, ln.stream));
-            HIP_TRY(hipStreamWaitEvent(sl.aux_stream, sl.aux_ev_a, 0));
-            if ((rc = launch_main(pol::MainK::WideLin, false, plan.main2_blocks, sl.aux_stream, cq, ln.d_ws + plan.ws_split))) return rc;
-            HIP_TRY(hipEventRecord(sl.aux_ev_b, sl.aux_stream));
-            gact::ChainQueues cq1 = cq;
-            cq1.leave_longest = plan.leave_longest;
-            if ((rc = launch_main(plan.main, false, plan.main_blocks, ln.stream, cq1, ln.d_ws))) return rc;
-            HIP_TRY(hipStreamWaitEvent(ln.stream, sl.aux_ev_b, 0));
-            if (first_pass) sl.lane = true;
-            return 0;
-        }
-        if ((rc = launch_main(plan.main, false, plan.main_blocks, ln.stream, cq, ln.d_ws))) return rc;
-        return traced(ln, raw ? "main launch (raw bytes)" : "main launch (2-bit)", plan.main_blocks, count);
-    };
-
-    const Lane own = main_lane(e, sl);
-    sl.side_used = false;
-    if (!mixed) return run_pass(own, any_other, nullptr, nullptr, n, true);
-    // the candidates sorted by what their two reads hold: two lists, their lengths back on the host (they decide grids
-    // and layouts: the only host wait of a run, and only of a run over sets with such reads)
-    const gact::SeqSetDev o_rs = rs.dev(false), o_qf = qf.dev_or(false, rs), o_qr = qr.dev_or(false, rs);
-    hipLaunchKernelGGL(gact::route_kernel, dim3(std::max(1, std::min((n + 255) / 256, 1024))), dim3(256), 0, sl.stream, sl.cands.p, first, n,
-                       rc_from, o_rs.other, need_f ? o_qf.other : nullptr, need_r ? o_qr.other : nullptr, sl.deferred.p, sl.d_counter + 4);
-    HIP_TRY(hipGetLastError());
-    int routed[2] = {0, 0};
-    // The two lists' lengths decide grids and layouts.  A list the host holds (uploaded, not merged, not made by the device
-    // filter) is counted on the host from the sets' per-sequence flags -- no wait: with other slots' persistent launches on
-    // the machine, route_kernel (14 registers: it does not fit beside three 168-register waves) starts only when a block of
-    // theirs has left, and the host sat in this wait for milliseconds (1 % dirty reads, four steps in flight: -10 %).
-    const bool host_counts = strands < 0 && !sl.h_cands.empty() && (size_t)first + (size_t)n <= sl.h_cands.size() &&
-                             (!rs.has_other || (int32_t)rs.h_other.size() == rs.n) && (!need_f || !qf.has_other || (int32_t)qf.h_other.size() == qf.n) &&
-                             (!need_r || !qr.has_other || (int32_t)qr.h_other.size() == qr.n);
-    if (host_counts) {
-        const int64_t key[4] = {first, n, rc_from, e->sets_epoch};
-        if (memcmp(key, sl.routed_key, sizeof key)) {
-            int dirty = 0;
-            for (int k = first; k < first + n; k++) {
-                const gact_candidate &c = sl.h_cands[(size_t)k];
-                const SeqSet &qs = k >= rc_from ? qr : qf;
-                dirty += ((rs.has_other && rs.h_other[(size_t)c.ref_id]) || (qs.has_other && qs.h_other[(size_t)c.query_id])) ? 1 : 0;
-            }
-            memcpy(sl.routed_key, key, sizeof key);
-            sl.routed_host[0] = n - dirty; sl.routed_host[1] = dirty;
-        }
-        routed[0] = sl.routed_host[0]; routed[1] = sl.routed_host[1];
-    } else {
-        HIP_TRY(hipMemcpyAsync(routed, sl.d_counter + 4, sizeof routed, hipMemcpyDeviceToHost, sl.stream));
-        HIP_TRY(hipStreamSynchronize(sl.stream));
-    }
-    sl.routed_raw = routed[1];
-    int rc = 0;
-    // Few raw-byte candidates beside many others: their launches last as long as their longest chain (a wave alone on
-    // its SIMD issues every ~8 cycles: a lone chain advances at a third of the machine's per-SIMD rate), so they run
-    // BESIDE the 2-bit launches, on the slot's side lane, started first -- the 2-bit main launch's last blocks become
-    // resident as the side lane's blocks leave.  Many of them (more than the side lane holds at one tile pair per
-    // group): one pass after the other on the whole machine.
-    const int side_cap = std::max(1, e->prop.multiProcessorCount / 2);
-    const int raw_blocks = ((routed[1] + 2 * gact::kGroupsPerWave - 1) / (2 * gact::kGroupsPerWave) + 3) / 4;
-    if (routed[0] > 0 && routed[1] > 0 && e->side_lane && raw_blocks <= side_cap) {
-        Lane side;
-        if ((rc = side_lane(e, sl, routed[1], std::max(raw_blocks, std::min(side_cap, 16)), &side))) return rc;
-        // (the side lane's launches read route_kernel's lists: behind it on the device, whether or not the host waited for it)
-        HIP_TRY(hipEventRecord(sl.side_go, sl.stream));
-        HIP_TRY(hipStreamWaitEvent(side.stream, sl.side_go, 0));
-        HIP_TRY(hipMemsetAsync(side.d_counter, 0, kCounterInts * sizeof(int), side.stream));
-        // ... and the slot's own launches behind the side lane's reset: "started first" has to hold on the DEVICE.  With the
-        // host no longer waiting for route_kernel the own lane's seed launch followed it at once, filled the machine, the own
-        // main launch after it, and the side lane's blocks found room when that had ended: 31 + 14 ms one after the other.
-        // Now both lanes' seed launches become eligible together and the side lane's stream has the higher priority.
-        HIP_TRY(hipEventRecord(sl.side_go, side.stream));
-        HIP_TRY(hipStreamWaitEvent(sl.stream, sl.side_go, 0));
-        if ((rc = poison_lane(e, side, 0x1b873593u))) return rc;
-        if ((rc = run_pass(side, true, sl.deferred.p + n, sl.d_counter + 5, routed[1], false))) return rc;
-        HIP_TRY(hipEventRecord(sl.side_done, side.stream));
-        sl.side_used = true;
-        rc = run_pass(own, false, sl.deferred.p, sl.d_counter + 4, routed[0], true);
-        // (also when the own lane's pass could not be launched: the side lane's launches are under way and write this run's records)
-        if (hipStreamWaitEvent(sl.stream, sl.side_done, 0) != hipSuccess && !rc) return fail(GACT_HIP_EDEVICE, "hipStreamWaitEvent failed");
-        return rc;
-    }
-    if (routed[0] > 0 && (rc = run_pass(own, false, sl.deferred.p, sl.d_counter + 4, routed[0], true))) return rc;
-    if (routed[1] == 0) return 0;
-    if (routed[0] > 0) { int prc = poison_ws(e, sl, 0x1b873593u); if (prc) return prc; }
-    // (behind a 2-bit pass on the same lane: the second set of queues, still empty)
-    return run_pass(own, true, sl.deferred.p + n, sl.d_counter + 5, routed[1], routed[0] == 0, routed[0] > 0);
-}
-
-template <int C> int occupancy_blocks(int *out)
-{
-    int a = 0, b = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, gact::chain_kernel<C, gact::SeedSink>, gact::kBlockThreads, 0));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, gact::align_tiles_kernel<C>, gact::kBlockThreads, 0));
-    int m = std::min(a, b);
-    for (int v = 0; v < 14; v++) {
-        int c = m;
-        if (v == 12 || v == 13) continue;   // the linear-gap launches have their own grids (lin_occupancy_blocks, wide_lin_grid_blocks)
-        auto k = v == 13 ? gact::extend_p16_kernel<gact::WideLayoutLin, false>
-               : v == 0 ? gact::extend_p16_kernel<gact::UniformLayout<C>, true>
-               : v == 1 ? gact::extend_p16_kernel<gact::UniformLayout<C>, false>
-               : v == 2 ? gact::extend_p16_kernel<gact::SplitLayout<7, 13>, true>
-               : v == 3 ? gact::extend_p16_kernel<gact::SplitLayout<7, 13>, false>
-               : v == 4 ? gact::extend_p16_kernel<gact::WideLayout, true>
-               : v == 5 ? gact::extend_p16_kernel<gact::WideLayout, false>
-               : v == 6 ? gact::extend_p16_kernel<gact::SplitLayout<7, 13, true>, true>
-               : v == 7 ? gact::extend_p16_kernel<gact::SplitLayout<7, 13, true>, false>
-               : v == 8 ? gact::extend_p16_kernel<gact::WideLayoutTagged, true>
-               : v == 9 ? gact::extend_p16_kernel<gact::WideLayoutTagged, false>
-               : v == 10 ? gact::extend_p16_kernel<gact::UniformLayout<C, gact::kGroup, true>, true>
-                         : gact::extend_p16_kernel<gact::UniformLayout<C, gact::kGroup, true>, false>;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c, k, gact::kBlockThreads, 0));
-        m = std::min(m, c);
-    }
-    *out = std::max(1, m);
-    return 0;
-}
-
-int lin_occupancy_blocks(int *out)
-{
-    int a = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, gact::extend_p16_kernel<gact::SplitLayoutLin<7, 13>, false>,
-                                                         gact::kBlockThreads, 0));
-    int b = a, c = a, d = a;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, gact::extend_p16_kernel<gact::SplitLayoutLinTeam<7, 13>, false>,
-                                                         gact::kBlockThreads, 0));
-    // (the same launches on the row-drifted pass, gact_lin.hpp 12.: one grid serves whichever pass the scoring takes)
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c, gact::extend_p16_kernel<gact::SplitLayoutLinRow<7, 13>, false>,
-                                                         gact::kBlockThreads, 0));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d, gact::extend_p16_kernel<gact::SplitLayoutLinRowTeam<7, 13>, false>,
-                                                         gact::kBlockThreads, 0));
-    *out = std::max(1, std::min(std::min(a, b), std::min(c, d)));
-    return 0;
-}
-
-template <int C> int seed_occupancy_blocks(int *out, int *out_lin)
-{
-    int a = 0, b = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, gact::seed_p16_kernel<C, true>, gact::kBlockThreads, 0));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, gact::seed_p16_kernel<C, false>, gact::kBlockThreads, 0));
-    int c = b;
-    if constexpr (C == 20) {
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c, gact::seed_p16_kernel<C, false, 1>, gact::kBlockThreads, 0));
-        int d = b;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d, gact::seed_p16_kernel<C, false, 3>, gact::kBlockThreads, 0));
-        b = std::min(b, d);
-    }
-    *out = std::max(1, std::min(a, b));
-    *out_lin = std::max(1, c);          // the linear-gap seed kernel fits three waves per SIMD
-    return 0;
-}
+#include "gact_launch.hpp"        // lanes and queues, the launches of a run (launch_extend, launch_big_extend); gact_launch_table.hpp: which kernels
 
 int validate_tiles(gact_hip_engine *e, const SeqSet &rs, const SeqSet &qf, const SeqSet &qr, int n,
                    const gact_tile *tiles)
@@ -1426,13 +937,12 @@ int gact_hip_create(const gact_hip_params *p, gact_hip_engine **out)
     e->kc.ext4 = gact::pk2(4 * p->gap_extend);
     e->kc.s_mismatch = p->mismatch; e->kc.s_open = p->gap_open; e->kc.s_ext = p->gap_extend;
 
-    rc = (e->C == 20) ? occupancy_blocks<20>(&e->blocks_per_cu) : occupancy_blocks<32>(&e->blocks_per_cu);
-    if (rc) { delete e; return rc; }
+    // (which kernels stand behind each grid: gact_launch_table.hpp grid_blocks_per_cu)
+    if ((rc = grid_blocks_per_cu(e->C, Grid::Main, &e->blocks_per_cu))) { delete e; return rc; }
     e->grid_blocks = e->blocks_per_cu * e->prop.multiProcessorCount;
     {
         int sb = 0, sbl = 0;
-        rc = (e->C == 20) ? seed_occupancy_blocks<20>(&sb, &sbl) : seed_occupancy_blocks<32>(&sb, &sbl);
-        if (rc) { delete e; return rc; }
+        if ((rc = grid_blocks_per_cu(e->C, Grid::Seed, &sb)) || (rc = grid_blocks_per_cu(e->C, Grid::SeedLin, &sbl))) { delete e; return rc; }
         // the workspace is sized for grid_blocks groups
         e->seed_grid_blocks = std::min(sb * e->prop.multiProcessorCount, e->grid_blocks);
         e->seed_lin_grid_blocks = std::min(sbl * e->prop.multiProcessorCount, e->grid_blocks);
@@ -1444,17 +954,13 @@ int gact_hip_create(const gact_hip_params *p, gact_hip_engine **out)
         // offsets (gact_device.hpp tb_refill_oct): engines that never run it are sized without it, and one whose
         // workspace would pass 4 GiB runs the affine passes instead
         int lb = 0;
-        if ((rc = lin_occupancy_blocks(&lb))) { delete e; return rc; }
+        if ((rc = grid_blocks_per_cu(e->C, Grid::Lin, &lb))) { delete e; return rc; }
         e->lin_grid_blocks = std::max(e->grid_blocks, lb * e->prop.multiProcessorCount);
         // GACT_HIP_LIN_BLOCKS=<n>: a smaller persistent grid for the split linear-gap launch (measurements: fewer resident
         // tiles = a smaller live pointer footprint)
         if (const char *v = opt_env("lin_blocks")) e->lin_grid_blocks = std::max(1, std::min(atoi(v), e->lin_grid_blocks));
         int wb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wb, gact::extend_p16_kernel<gact::WideLayoutLin, false>, gact::kBlockThreads, 0) !=
-            hipSuccess) {
-            delete e;
-            return fail(GACT_HIP_EDEVICE, "hipOccupancyMaxActiveBlocksPerMultiprocessor failed");
-        }
+        if ((rc = grid_blocks_per_cu(e->C, Grid::WideLin, &wb))) { delete e; return rc; }
         e->wide_lin_grid_blocks = std::max(e->grid_blocks, wb * e->prop.multiProcessorCount);
         if ((ws_words_for(std::max(e->lin_grid_blocks, e->wide_lin_grid_blocks)) + 64) * sizeof(uint32_t) >= (1ull << 32)) {
             e->lin = false;
@@ -1464,29 +970,17 @@ int gact_hip_create(const gact_hip_params *p, gact_hip_engine **out)
     if (!e->lin) e->wide_lin_grid_blocks = e->grid_blocks;
     e->role_grid_blocks = 0;
     if (e->lin && e->split && e->C == 20) {
-        using RL = gact::SplitLayoutLin<7, 13>;
-        using RowL = gact::SplitLayoutLinRow<7, 13>;
-        int rb = 0, rb2 = 0, rb3 = 0, rb4 = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&rb, gact::extend_roles_kernel<RL, false>, gact::kRoleThreads, 0) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&rb2, gact::extend_roles_kernel<RL, true>, gact::kRoleThreads, 0) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&rb3, gact::extend_roles_kernel<RowL, false>, gact::kRoleThreads, 0) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&rb4, gact::extend_roles_kernel<RowL, true>, gact::kRoleThreads, 0) != hipSuccess) {
-            delete e;
-            return fail(GACT_HIP_EDEVICE, "hipOccupancyMaxActiveBlocksPerMultiprocessor failed");
-        }
-        e->role_grid_blocks = std::max(1, std::min(std::min(rb, rb2), std::min(rb3, rb4))) * e->prop.multiProcessorCount;
+        int rb = 0;
+        if ((rc = grid_blocks_per_cu(e->C, Grid::Role, &rb))) { delete e; return rc; }
+        e->role_grid_blocks = rb * e->prop.multiProcessorCount;
         if (const char *v = opt_env("role_blocks")) e->role_grid_blocks = std::max(1, std::min(atoi(v), e->role_grid_blocks));
     }
     e->roles = e->roles && e->role_grid_blocks > 0;
     e->aff_grid_blocks = e->grid_blocks;
     if (e->aff) {
         int ab = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&ab, gact::extend_p16_kernel<gact::SplitLayoutAff<7, 13, true>, false>,
-                                                         gact::kBlockThreads, 0) != hipSuccess) {
-            delete e;
-            return fail(GACT_HIP_EDEVICE, "hipOccupancyMaxActiveBlocksPerMultiprocessor failed");
-        }
-        e->aff_grid_blocks = std::max(1, ab) * e->prop.multiProcessorCount;
+        if ((rc = grid_blocks_per_cu(e->C, Grid::Aff, &ab))) { delete e; return rc; }
+        e->aff_grid_blocks = ab * e->prop.multiProcessorCount;
     }
     if (p->max_blocks > 0) {                // a small engine (gact_hip_params.max_blocks): every persistent grid capped, the workspace with them
         for (int *g : {&e->grid_blocks, &e->seed_grid_blocks, &e->seed_lin_grid_blocks, &e->lin_grid_blocks, &e->wide_lin_grid_blocks, &e->aff_grid_blocks})
@@ -1792,12 +1286,10 @@ static int launch_run(gact_hip_engine *e, Slot &sl, int first, int n, int rc_fro
     if ((rc = poison_ws(e, sl, 0))) return rc;
     HIP_TRY(hipEventRecord(sl.ev0, sl.stream));
     sl.forget_times();
-    sl.two_phase = false;
+    sl.shape = RunShape{};
     sl.merged_into = -1; sl.merged_callers = 1;
     if (n > 0) {
-        rc = e->big_cb ? launch_big_extend(e, sl, first, n, rc_from, same_file)
-           : (e->C == 20) ? launch_extend<20>(e, sl, first, n, rc_from, same_file, strands)
-                          : launch_extend<32>(e, sl, first, n, rc_from, same_file, strands);
+        rc = e->big_cb ? launch_big_extend(e, sl, first, n, rc_from, same_file) : launch_extend(e, sl, first, n, rc_from, same_file, strands);
         if (rc) return rc;
     }
     HIP_TRY(hipEventRecord(sl.ev1, sl.stream));
@@ -1856,17 +1348,16 @@ static int launch_merged(gact_hip_engine *e, const std::vector<RunReq *> &batch)
         SwapBack back{ms, *rec};
         if ((rc = launch_run(e, ms, 0, total, gact::kCompInCand, batch[0]->same_file, strands))) return rc;
     }
-    rec->two_phase = ms.two_phase; rec->wide = ms.wide; rec->lin = ms.lin; rec->aff = ms.aff; rec->overlapped = ms.overlapped;
-    rec->lane = ms.lane; rec->side_used = ms.side_used; rec->routed_raw = ms.routed_raw; rec->roles = ms.roles;
-    if (ms.two_phase) {
+    rec->shape = ms.shape;
+    if (rec->shape.two_phase) {
         // the counters as this launch leaves them, into the record's pinned array (a kernel copy: see bus_copy)
         void *hc = device_view(rec->h_counter);
         if (hc) {
             if ((rc = bus_copy(ms.stream, ms.d_counter, hc, kCounterInts * sizeof(int)))) return rc;
-            if (ms.side_used && (rc = bus_copy(ms.stream, ms.side_counter, (char *)hc + kCounterInts * sizeof(int), kCounterInts * sizeof(int)))) return rc;
+            if (rec->shape.side_used && (rc = bus_copy(ms.stream, ms.side_counter, (char *)hc + kCounterInts * sizeof(int), kCounterInts * sizeof(int)))) return rc;
         } else {
             HIP_TRY(hipMemcpyAsync(rec->h_counter, ms.d_counter, kCounterInts * sizeof(int), hipMemcpyDeviceToHost, ms.stream));
-            if (ms.side_used) HIP_TRY(hipMemcpyAsync(rec->h_counter + kCounterInts, ms.side_counter, kCounterInts * sizeof(int), hipMemcpyDeviceToHost, ms.stream));
+            if (rec->shape.side_used) HIP_TRY(hipMemcpyAsync(rec->h_counter + kCounterInts, ms.side_counter, kCounterInts * sizeof(int), hipMemcpyDeviceToHost, ms.stream));
         }
     }
     HIP_TRY(hipEventRecord(rec->ev_done, ms.stream));
@@ -2195,6 +1686,42 @@ static void keep_times(Slot &sl, gact_hip_run_stats *st)
     }
 }
 
+// What `shape` and the three events of a run say, into `st`.  The counters are the run's own lane's and, where it had launches
+// on the side lane, that lane's: the pinned copies a merged launch's record keeps (`pinned`: 2 x kCounterInts ints), else read
+// from the device now.  The caller has waited for the run.
+static int fill_run_stats(const gact_hip_engine *e, const RunShape &sh, hipEvent_t ev0, hipEvent_t ev_mid, hipEvent_t ev1, const int *pinned,
+                          const int *d_own, const int *d_side, gact_hip_run_stats *st)
+{
+    st->overlapped_seeding = sh.overlapped ? 1 : 0;
+    st->critical_lane = sh.lane ? 1 : 0;
+    st->role_waves = sh.roles;
+    HIP_TRY(hipEventElapsedTime(&st->total_ms, ev0, ev1));
+    st->main_ms = st->total_ms;
+    st->packed16 = sh.two_phase ? (sh.wide ? 3 : e->split ? 2 : 1) : 0;
+    st->seed_packed16 = (sh.two_phase && e->seed16) ? 1 : 0;
+    st->tagged_pointers = (sh.two_phase && e->tagged) ? 1 : 0;
+    st->linear_gap = (sh.two_phase && sh.lin) ? ((e->lin_row && !sh.wide) ? 3 : 1) : (sh.two_phase && sh.aff) ? 2 : 0;
+    st->raw_candidates = sh.routed_raw;
+    if (!sh.two_phase) return 0;
+    HIP_TRY(hipEventElapsedTime(&st->seed_ms, ev0, ev_mid));
+    HIP_TRY(hipEventElapsedTime(&st->main_ms, ev_mid, ev1));
+    int buf[kCounterInts];
+    const int *c = pinned;
+    if (!pinned) { HIP_TRY(hipMemcpy(buf, d_own, sizeof buf, hipMemcpyDeviceToHost)); c = buf; }
+    for (int b = 0; b < gact::kBuckets; b++) st->handed_off += c[8 + b] + c[kMoreCount + b];
+    memcpy(&st->seed_cells, &c[2], sizeof(int64_t));
+    st->band_redos = c[6];
+    if (sh.side_used) {                 // launches beside: their share of both figures
+        c = pinned ? pinned + kCounterInts : buf;
+        if (!pinned) HIP_TRY(hipMemcpy(buf, d_side, sizeof buf, hipMemcpyDeviceToHost));
+        for (int b = 0; b < gact::kBuckets; b++) st->handed_off += c[8 + b];
+        int64_t sc = 0;
+        memcpy(&sc, &c[2], sizeof(int64_t));
+        st->seed_cells += sc;
+    }
+    return 0;
+}
+
 int gact_hip_last_run_stats(gact_hip_engine *e, int slot, gact_hip_run_stats *st)
 {
     int rc = check_slot(e, slot);
@@ -2203,71 +1730,21 @@ int gact_hip_last_run_stats(gact_hip_engine *e, int slot, gact_hip_run_stats *st
     if (!e->slots[slot].timed) return fail(GACT_HIP_EINVAL, "no kernel has been launched on slot %d", slot);
     if ((rc = set_device(e))) return rc;
     memset(st, 0, sizeof *st);
-    if (e->slots[slot].merged_into >= 0) {
+    Slot &sl = e->slots[slot];
+    if (sl.merged_into >= 0) {
         // a run that was merged with other callers' runs: the figures of THAT launch, from its own immutable record -- the
         // merge slot's events and counters are re-recorded as soon as another leader takes the slot
-        const std::shared_ptr<LaunchStats> rec = e->slots[slot].merged_stats;
+        const std::shared_ptr<LaunchStats> rec = sl.merged_stats;
         if (!rec) return fail(GACT_HIP_EINVAL, "slot %d: no statistics of its merged run", slot);
-        st->merged_callers = e->slots[slot].merged_callers;
-        st->overlapped_seeding = rec->overlapped ? 1 : 0;
-        st->critical_lane = rec->lane ? 1 : 0;
-        st->role_waves = rec->roles;
+        st->merged_callers = sl.merged_callers;
         HIP_TRY(hipEventSynchronize(rec->ev_done));
-        HIP_TRY(hipEventElapsedTime(&st->total_ms, rec->ev0, rec->ev1));
-        st->main_ms = st->total_ms;
-        st->packed16 = rec->two_phase ? (rec->wide ? 3 : e->split ? 2 : 1) : 0;
-        st->seed_packed16 = (rec->two_phase && e->seed16) ? 1 : 0;
-        st->tagged_pointers = (rec->two_phase && e->tagged) ? 1 : 0;
-        st->linear_gap = (rec->two_phase && rec->lin) ? ((e->lin_row && !rec->wide) ? 3 : 1) : (rec->two_phase && rec->aff) ? 2 : 0;
-        st->raw_candidates = rec->routed_raw;
-        if (rec->two_phase) {
-            HIP_TRY(hipEventElapsedTime(&st->seed_ms, rec->ev0, rec->ev_mid));
-            HIP_TRY(hipEventElapsedTime(&st->main_ms, rec->ev_mid, rec->ev1));
-            const int *c = rec->h_counter;
-            for (int b = 0; b < gact::kBuckets; b++) st->handed_off += c[8 + b] + c[kMoreCount + b];
-            memcpy(&st->seed_cells, &c[2], sizeof(int64_t));
-            st->band_redos = c[6];
-            if (rec->side_used) {
-                const int *cs = rec->h_counter + kCounterInts;
-                for (int b = 0; b < gact::kBuckets; b++) st->handed_off += cs[8 + b];
-                int64_t sc = 0;
-                memcpy(&sc, &cs[2], sizeof(int64_t));
-                st->seed_cells += sc;
-            }
-        }
-        keep_times(e->slots[slot], st);
-        return 0;
+        rc = fill_run_stats(e, rec->shape, rec->ev0, rec->ev_mid, rec->ev1, rec->h_counter, nullptr, nullptr, st);
+    } else {
+        st->merged_callers = 1;
+        HIP_TRY(hipEventSynchronize(sl.ev1));
+        rc = fill_run_stats(e, sl.shape, sl.ev0, sl.ev_mid, sl.ev1, nullptr, sl.d_counter, sl.side_counter, st);
     }
-    Slot &sl = e->slots[slot];
-    st->merged_callers = 1;
-    st->overlapped_seeding = sl.overlapped ? 1 : 0;
-    st->critical_lane = sl.lane ? 1 : 0;
-    st->role_waves = sl.roles;
-    HIP_TRY(hipEventSynchronize(sl.ev1));
-    HIP_TRY(hipEventElapsedTime(&st->total_ms, sl.ev0, sl.ev1));
-    st->main_ms = st->total_ms;
-    st->packed16 = sl.two_phase ? (sl.wide ? 3 : e->split ? 2 : 1) : 0;
-    st->seed_packed16 = (sl.two_phase && e->seed16) ? 1 : 0;
-    st->tagged_pointers = (sl.two_phase && e->tagged) ? 1 : 0;
-    st->linear_gap = (sl.two_phase && sl.lin) ? ((e->lin_row && !sl.wide) ? 3 : 1) : (sl.two_phase && sl.aff) ? 2 : 0;
-    st->raw_candidates = sl.routed_raw;
-    if (sl.two_phase) {
-        HIP_TRY(hipEventElapsedTime(&st->seed_ms, sl.ev0, sl.ev_mid));
-        HIP_TRY(hipEventElapsedTime(&st->main_ms, sl.ev_mid, sl.ev1));
-        int c[kCounterInts];
-        HIP_TRY(hipMemcpy(c, sl.d_counter, sizeof c, hipMemcpyDeviceToHost));
-        st->handed_off = 0;
-        for (int b = 0; b < gact::kBuckets; b++) st->handed_off += c[8 + b] + c[kMoreCount + b];
-        memcpy(&st->seed_cells, &c[2], sizeof(int64_t));
-        st->band_redos = c[6];
-        if (sl.side_used) {                 // launches beside: their share of both figures
-            HIP_TRY(hipMemcpy(c, sl.side_counter, sizeof c, hipMemcpyDeviceToHost));
-            for (int b = 0; b < gact::kBuckets; b++) st->handed_off += c[8 + b];
-            int64_t sc = 0;
-            memcpy(&sc, &c[2], sizeof(int64_t));
-            st->seed_cells += sc;
-        }
-    }
+    if (rc) return rc;
     keep_times(sl, st);
     return 0;
 }
@@ -2300,36 +1777,18 @@ int gact_hip_prepare(gact_hip_engine *e, int32_t expected_candidates)
             HIP_TRY(hipStreamSynchronize(sl.stream));
             const Lane own = main_lane(e, sl);
             gact::ChainQueues q = queues(own, sl);
-            q.list = sl.order.p; q.list_n = 0;
-            gact::ChainQueues q2 = q;                                  // the two-set variant: both sets empty, the flag set
-            {
-                const gact::ChainQueues s2 = second_queues(own, sl);
-                q2.more_flag = sl.d_counter + 7;
-                q2.more_count = s2.bucket_count; q2.more_pop = s2.bucket_pop; q2.more_live = s2.live;
-            }
+            gact::ChainQueues q2 = both_queues(own, sl);              // the two-set forms: both sets empty, the flag set
+            q.list = q2.list = sl.order.p; q.list_n = q2.list_n = 0;
+            // a run of no candidates: one block of the seed kernel and of the main kernels of the pass this engine's scoring takes
+            // (gact_lin.hpp 12.), for one set of queues and for two
+            const RunCtx c{e, sl, 0, 0, 0, 0, e->kp, false, false};
+            const Pass ps{own, false, d, d, d, 0, false};
+            using M = gact_policy::MainK;
             for (hipStream_t st : {sl.stream, sl.aux_stream}) {
-                hipLaunchKernelGGL((gact::seed_p16_kernel<20, false, 1>), dim3(1), dim3(gact::kBlockThreads), 0, st, e->kp, e->kc, d, d, d,
-                                   sl.cands.p, 0, 0, 0, 0, sl.overlaps.p, q, sl.d_ws);
-                // the kernels of the pass this engine's scoring takes (gact_lin.hpp 12.)
-                auto warm = [&](auto layout) {
-                    using WL = decltype(layout);
-                    hipLaunchKernelGGL((gact::extend_p16_kernel<WL, false>), dim3(1), dim3(gact::kBlockThreads), 0, st, e->kp,
-                                       e->kc, d, d, d, 0, sl.overlaps.p, q, sl.d_ws);
-                    hipLaunchKernelGGL((gact::extend_p16_kernel<WL, false, true>), dim3(1), dim3(gact::kBlockThreads), 0, st,
-                                       e->kp, e->kc, d, d, d, 0, sl.overlaps.p, q2, sl.d_ws);
-                    hipLaunchKernelGGL((gact::extend_coop_kernel<WL, false>), dim3(1), dim3(gact::kBlockThreads), 0, st,
-                                       e->kp, e->kc, d, d, d, 0, sl.overlaps.p, q, sl.d_ws);
-                    hipLaunchKernelGGL((gact::extend_coop_kernel<WL, true>), dim3(1), dim3(gact::kBlockThreads), 0, st,
-                                       e->kp, e->kc, d, d, d, 0, sl.overlaps.p, q2, sl.d_ws);
-                    if (e->role_grid_blocks > 0) {
-                        hipLaunchKernelGGL((gact::extend_roles_kernel<WL, false>), dim3(1), dim3(gact::kRoleThreads), 0, st,
-                                           e->kp, e->kc, d, d, d, 0, sl.overlaps.p, q, sl.d_ws);
-                        hipLaunchKernelGGL((gact::extend_roles_kernel<WL, true>), dim3(1), dim3(gact::kRoleThreads), 0, st,
-                                           e->kp, e->kc, d, d, d, 0, sl.overlaps.p, q2, sl.d_ws);
-                    }
-                };
-                if (e->lin_row) warm(gact::SplitLayoutLinRow<7, 13>{}); else warm(gact::SplitLayoutLin<7, 13>{});
-                HIP_TRY(hipGetLastError());
+                if ((rc = launch_seed(c, ps, gact_policy::SeedK::P16Lin, 1, st, q, sl.d_ws))) return rc;
+                for (M k : {M::SplitLin, M::CoopLin, M::RolesLin})
+                    for (bool two_sets : {false, true})
+                        if ((k != M::RolesLin || e->role_grid_blocks > 0) && (rc = launch_main(c, ps, k, two_sets, 1, st, two_sets ? q2 : q, sl.d_ws))) return rc;
             }
             HIP_TRY(hipStreamSynchronize(sl.stream));
             HIP_TRY(hipStreamSynchronize(sl.aux_stream));

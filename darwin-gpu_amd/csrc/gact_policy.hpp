@@ -1,8 +1,8 @@
 // gact_policy.hpp -- WHAT a pass over `count` candidates runs as: which seed kernel, which main kernel, on how many blocks,
 // in which sequence.  A pure function of counts and of the engine's capabilities -- no HIP call, no engine, no device --
 // so that it can be read, swept and unit-tested on the CPU (tests/test_host_logic.py, gact_hip_plan_describe), apart from
-// the code that launches (gact_engine.hip launch_extend).  VERDICT r04 #8: until round 4 the decisions were spread over
-// 364 lines of launch_extend between the launches themselves.
+// the code that launches (gact_launch.hpp run_pass; which kernel a MainK / SeedK names: gact_launch_table.hpp).  VERDICT r04 #8:
+// until round 4 the decisions were spread over 364 lines of launch_extend between the launches themselves.
 //
 // The operating points, in candidates per resident tile slot of the narrow layouts (S = lin_grid_blocks x 32; 24,576 on
 // an MI355X), each from a measurement:
