@@ -59,6 +59,8 @@
 //    v_pk_maximum3_f16 and are kept and moved by the scalar unit, off the VALU and out of the VGPR file.
 #pragma once
 
+#include <type_traits>
+
 #include "gact_p16s.hpp"
 
 namespace gact {
@@ -395,27 +397,28 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         if (r1) { rb1 = row(lut_plain, sb1); rb1b = row(lut_plain, sb1b); }
         if (r2) { rb2 = row(tag2 ? lut_tagged : lut_plain, sb2); rb2b = row(tag2 ? lut_tagged : lut_plain, sb2b); }
     };
-    auto upper_all = [&](uint32_t (&U)[CT], const bool tag2, const uint32_t Zr2) {
+    auto upper_all = [&](auto first, uint32_t (&U)[CT], const bool tag2, const uint32_t Zr2) {
+        constexpr int C0 = decltype(first)::value;
         uint32_t P[CT];
 #pragma unroll
-        for (int c = 0; c < CT; c++) P[c] = __builtin_amdgcn_perm(c < C1 ? rb1b : rb2b, c < C1 ? rb1 : rb2, qb[c]);
+        for (int c = C0; c < CT; c++) P[c] = __builtin_amdgcn_perm(c < C1 ? rb1b : rb2b, c < C1 ? rb1 : rb2, qb[c]);
         GACT_SB();
 #pragma unroll
-        for (int c = 0; c < CT; c++) U[c] = (c == 0 ? Hdiag1 : c == C1 ? Hdiag2 : G[c - 1]) + P[c];   // align.cpp:134-144
+        for (int c = C0; c < CT; c++) U[c] = (c == 0 ? Hdiag1 : c == C1 ? Hdiag2 : G[c - 1]) + P[c];   // align.cpp:134-144
         // (pointer phase: region 2's G is kept tagged 2, so it IS H_up'' as it stands; the look-up words of that phase
         //  carry a +1, so M'' = G_diag'' + 4 (sub - g) + 1 comes out tagged 3 with no instruction of its own)
-        ask_rows(true, true, tag2);
+        ask_rows(C0 == 0, true, tag2);
         GACT_SB();
         if (GACT_LIN_MAX3) {
 #pragma unroll
-            for (int c = 0; c < CT; c++)                                         // :145-147 and the insertion, :149-154
+            for (int c = C0; c < CT; c++)                                         // :145-147 and the insertion, :149-154
                 U[c] = pk_max3f(U[c], c < C1 ? Z1 : Zr2, G[c]);
         } else {
 #pragma unroll
-            for (int c = 0; c < CT; c++) U[c] = lin_max(U[c], c < C1 ? Z1 : Zr2);     // :145-147
+            for (int c = C0; c < CT; c++) U[c] = lin_max(U[c], c < C1 ? Z1 : Zr2);     // :145-147
             GACT_SB();
 #pragma unroll
-            for (int c = 0; c < CT; c++) U[c] = lin_max(U[c], G[c]);              // the insertion, :149-154
+            for (int c = C0; c < CT; c++) U[c] = lin_max(U[c], G[c]);              // the insertion, :149-154
         }
         GACT_SB();
     };
@@ -428,7 +431,7 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         // lane 0 of region 2 continues lane 15's region 1 (one step ago = same row, same zero level)
         const uint32_t Hl2 = (uint32_t)dpp_row_shr1((int)H2, dpp_row_ror1((int)H1));
         uint32_t U[CT];
-        upper_all(U, false, Z2);
+        upper_all(LinPos<0>{}, U, false, Z2);
         Hdiag1 = Hl1; Hdiag2 = Hl2;
         uint32_t Ha = Hl1, Hb = Hl2;
         static_assert(C2 >= C1, "region 2 is the longer chain");
@@ -480,73 +483,33 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         uint32_t &r = grp[c - 2 + (S >> 2)];
         r = (S & 3) ? pk_shl_add4(r, x) : x;
     };
-    auto step_tagged = [&](auto pos) {
+    auto step_ptr = [&](auto pos, auto with_r1) {
         constexpr int S = decltype(pos)::value;
         constexpr bool blk = S != kLinTail;
-        ask_bytes(true, true);
-        Z1 += gv; Z24 += g4v;
-        const uint32_t Hl1 = (uint32_t)dpp_row_shr1((int)H1, (int)Z1);
-        // lane 15's region-1 column enters region 2 scaled and tagged 2
+        constexpr bool R1 = decltype(with_r1)::value;
+        ask_bytes(R1, true);
+        if (R1) Z1 += gv;
+        Z24 += g4v;
+        uint32_t Hl1 = 0;
+        if (R1) Hl1 = (uint32_t)dpp_row_shr1((int)H1, (int)Z1);
         const uint32_t Hl2 = (uint32_t)dpp_row_shr1((int)H2, dpp_row_ror1((int)pk_mad4v(H1, c2v)));
         uint32_t U[CT];
-        upper_all(U, true, Z24);
-        Hdiag1 = Hl1; Hdiag2 = Hl2;
+        upper_all(LinPos<R1 ? 0 : C1>{}, U, true, Z24);
+        if (R1) Hdiag1 = Hl1;
+        Hdiag2 = Hl2;
         uint32_t Ha = Hl1, Hb = Hl2;
         uint32_t tprev = 0, Hq = 0, x = 0;
 #pragma unroll
         for (int c = 0; c < C2; c++) {
-            const bool both = c < C1;
-            const bool filed = blk && c >= 2 && !(c & 1);                        // the pair (c - 2, c - 1) is filed in this slot
+            const bool both = R1 && c < C1;
+            const bool filed = blk && c >= 2 && !(c & 1);
             uint32_t Da = 0;
-            const uint32_t Db = Hb - dtv;                                        // G'' tagged 2 -> D'' tagged 1
+            const uint32_t Db = Hb - dtv;
             if (both) Da = Ha - gv;
             if (filed) x &= kLinPairMask;
             GACT_SB();
-            const uint32_t Hp = lin_max(U[C1 + c], Db);                           // the low bits: the op (:162-164)
+            const uint32_t Hp = lin_max(U[C1 + c], Db);
             if (both) { G[c] = lin_max(U[c], Da); Ha = G[c]; }
-            if (!blk && c > 0) acc[c - 1] = pk_shl_add4(acc[c - 1], tprev);
-            if (filed) file_group(S, c, x);
-            GACT_SB();
-            G[C1 + c] = andn_or(Hp, c3v, c2v);                                   // low bits := 2
-            if (!blk || c == C2 - 1) tprev = Hp & c3v;
-            else if (c & 1) x = __builtin_amdgcn_perm(Hp, Hq, psel);
-            else Hq = Hp;
-            GACT_SB();
-            Hb = G[C1 + c];
-        }
-        if (!blk) acc[C2 - 1] = pk_shl_add4(acc[C2 - 1], tprev);
-        else odd = S ? pk_shl_add4(odd, tprev) : tprev;
-        H1 = Ha; H2 = Hb;
-    };
-    // a step of the pointer phase in which region 1 is past its last row in every lane (see 7. below): region 2 alone; H1
-    // stays what lane 15 left at step T_end - LAG
-    auto step_tagged_r2 = [&](auto pos) {
-        constexpr int S = decltype(pos)::value;
-        constexpr bool blk = S != kLinTail;
-        ask_bytes(false, true);
-        Z24 += g4v;
-        const uint32_t Hl2 = (uint32_t)dpp_row_shr1((int)H2, dpp_row_ror1((int)pk_mad4v(H1, c2v)));
-        uint32_t P[C2], U[C2];
-#pragma unroll
-        for (int c = 0; c < C2; c++) P[c] = __builtin_amdgcn_perm(rb2b, rb2, qb[C1 + c]);
-        GACT_SB();
-#pragma unroll
-        for (int c = 0; c < C2; c++) U[c] = (c == 0 ? Hdiag2 : G[C1 + c - 1]) + P[c];
-        ask_rows(false, true, true);
-        GACT_SB();
-#pragma unroll
-        for (int c = 0; c < C2; c++) U[c] = GACT_LIN_MAX3 ? pk_max3f(U[c], Z24, G[C1 + c]) : lin_max(lin_max(U[c], Z24), G[C1 + c]);
-        GACT_SB();
-        Hdiag2 = Hl2;
-        uint32_t Hb = Hl2;
-        uint32_t tprev = 0, Hq = 0, x = 0;
-#pragma unroll
-        for (int c = 0; c < C2; c++) {
-            const bool filed = blk && c >= 2 && !(c & 1);
-            const uint32_t Db = Hb - dtv;
-            if (filed) x &= kLinPairMask;
-            GACT_SB();
-            const uint32_t Hp = lin_max(U[c], Db);
             if (!blk && c > 0) acc[c - 1] = pk_shl_add4(acc[c - 1], tprev);
             if (filed) file_group(S, c, x);
             GACT_SB();
@@ -559,12 +522,14 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         }
         if (!blk) acc[C2 - 1] = pk_shl_add4(acc[C2 - 1], tprev);
         else odd = S ? pk_shl_add4(odd, tprev) : tprev;
+        if (R1) H1 = Ha;
         H2 = Hb;
     };
+    auto step_tagged = [&](auto pos) { step_ptr(pos, std::true_type{}); };
+    auto step_tagged_r2 = [&](auto pos) { step_ptr(pos, std::false_type{}); };
     // the eight steps of a whole block, each with its place
 #define GACT_LIN_BLOCK8(f) do { f(LinPos<0>{}); f(LinPos<1>{}); f(LinPos<2>{}); f(LinPos<3>{}); \
                                 f(LinPos<4>{}); f(LinPos<5>{}); f(LinPos<6>{}); f(LinPos<7>{}); } while (0)
-#undef GACT_SB
     auto enter_tagged = [&]() {
 #pragma unroll
         for (int c = C1; c < CT; c++) G[c] = pk_mad4v(G[c], c2v);
@@ -630,7 +595,6 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split(const P16Consts &kc, const
         qA += QD * kWsRow;
         qB += QD * kWsRow;
     }
-#undef GACT_LIN_BLOCK8
     // (what is left are the last seven steps at most: region 2 alone, unless the pointer phase began inside them)
     for (; t <= T_end - LAG; t++, k++) step_tagged(LinPos<kLinTail>{});
     for (; t <= T_end; t++, k++) step_tagged_r2(LinPos<kLinTail>{});
@@ -750,10 +714,7 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
     uint32_t H1 = W[C1], H2 = W[C2];
     uint32_t Hdiag1 = W[0], Hdiag2 = W[0];          // last step's hand-over value: one gap below the zero level of slot 0 then
 
-    // Look-up words (LinLut above): a row's byte in the ref stream IS the byte offset of its word in the table, so a row
-    // costs two LDS reads per tile and no VALU instruction.  rp: this lane's stream bytes of region 2's row at the step
-    // to come (tile A, tile B); region 1's are LAG entries further on.  Before step t: rb1 / rb1b = row t of region 1,
-    // rb2 / rb2b = row t - LAG of region 2.
+    // look-up words and the ref stream: as in dp_pass_lin_split
     typedef __attribute__((address_space(3))) const uint8_t LdsByte;
     typedef __attribute__((address_space(3))) const uint32_t LdsWord;
     LdsByte *const lut_plain = (LdsByte *)lut_lds, *const lut_tagged = (LdsByte *)(lut_lds + 1);
@@ -763,14 +724,7 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
     uint32_t rb2 = row(lut_plain, rp[0]), rb2b = row(lut_plain, rp[1]);
     rp += 2;
 
-    // Instruction order.  With three waves on a SIMD a v_add / v_sub / v_and / v_or issues in 1.9 cycles when it does
-    // not wait for the instruction in front of it, in 3.0 when it does (issue_rate_probe.json, dependent streams).
-    // So the step is written in stages -- one kind of instruction for all column slots, then the next kind -- and the
-    // two regions' column chains (H_left -> D -> H, two dependent instructions per slot) run side by side; the
-    // scheduling barriers keep the compiler from folding the stages back into per-slot sequences.
-#define GACT_SB() __builtin_amdgcn_sched_barrier(0)
-    // the next step's rows: the stream bytes are asked for when the step begins, their look-up words once the v_perm stage
-    // has read the current ones (the bytes have had that stage's time to arrive, the words have the rest of the step)
+    // (instruction order, and when the next step's rows are asked for: see dp_pass_lin_split)
     uint32_t sb1 = 0, sb1b = 0, sb2 = 0, sb2b = 0;
     auto ask_bytes = [&](const bool r1, const bool r2) {
         if (r2) { sb2 = rp[0]; sb2b = rp[1]; }
@@ -781,117 +735,105 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
         if (r1) { rb1 = row(lut_plain, sb1); rb1b = row(lut_plain, sb1b); }
         if (r2) { rb2 = row(tag2 ? lut_tagged : lut_plain, sb2); rb2b = row(tag2 ? lut_tagged : lut_plain, sb2b); }
     };
-    // o: the step's place in a block's strips (lin_strip_at), 0 for a step of the per-step form
-    auto upper_all = [&](uint32_t (&U)[CT], const bool tag2, const int o) {
+    // slots first .. last - 1: both regions, or the one a step computes.  o: the step's place in a block's strips
+    // (lin_strip_at), 0 for a step of the per-step form
+    auto upper_all = [&](auto first, auto last, uint32_t (&U)[CT], const bool tag2, const int o) {
+        constexpr int C0 = decltype(first)::value, Cn = decltype(last)::value;
         uint32_t P[CT];
 #pragma unroll
-        for (int c = 0; c < CT; c++) P[c] = __builtin_amdgcn_perm(c < C1 ? rb1b : rb2b, c < C1 ? rb1 : rb2, qb[c]);
+        for (int c = C0; c < Cn; c++) P[c] = __builtin_amdgcn_perm(c < C1 ? rb1b : rb2b, c < C1 ? rb1 : rb2, qb[c]);
         GACT_SB();
 #pragma unroll
-        for (int c = 0; c < CT; c++) U[c] = (c == 0 ? Hdiag1 : c == C1 ? Hdiag2 : G[c - 1]) + P[c];   // align.cpp:134-144
-        // (pointer phase: region 2's G is kept tagged 2, so it IS H_up'' as it stands; the look-up words of that phase
-        //  carry a +1, so M'' = G_diag'' + 4 (sub - g) + 1 comes out tagged 3 with no instruction of its own)
-        ask_rows(true, true, tag2);
+        for (int c = C0; c < Cn; c++) U[c] = (c == 0 ? Hdiag1 : c == C1 ? Hdiag2 : G[c - 1]) + P[c];   // align.cpp:134-144
+        ask_rows(C0 < C1, Cn > C1, tag2);
         GACT_SB();
         if (GACT_LIN_MAX3) {
 #pragma unroll
-            for (int c = 0; c < CT; c++)                                         // :145-147 and the insertion, :149-154
+            for (int c = C0; c < Cn; c++)                                        // :145-147 and the insertion, :149-154
                 U[c] = pk_max3f_s(U[c], c < C1 ? W[o + c + 1] : tag2 ? T[o + c - C1] : W[o + c - C1 + 1], G[c]);
         } else {
 #pragma unroll
-            for (int c = 0; c < CT; c++) U[c] = pk_max_sgpr(U[c], c < C1 ? W[o + c + 1] : tag2 ? T[o + c - C1] : W[o + c - C1 + 1]);     // :145-147
+            for (int c = C0; c < Cn; c++) U[c] = pk_max_sgpr(U[c], c < C1 ? W[o + c + 1] : tag2 ? T[o + c - C1] : W[o + c - C1 + 1]);     // :145-147
             GACT_SB();
 #pragma unroll
-            for (int c = 0; c < CT; c++) U[c] = lin_max<kLinSplitBuiltins>(U[c], G[c]);              // the insertion, :149-154
+            for (int c = C0; c < Cn; c++) U[c] = lin_max<kLinSplitBuiltins>(U[c], G[c]);             // the insertion, :149-154
         }
         GACT_SB();
     };
 
-    auto step = [&](auto pos) {
+    // a step on plain scores.  Without region 2: it is in front of its row 1 in every lane (see 7. below) and stays at its
+    // zero level
+    auto step_plain = [&](auto pos, auto with_r2) {
         constexpr int S = decltype(pos)::value, o = lin_strip_at(S, 0);
-        ask_bytes(true, true);
-        if (!GACT_LIN_SLIDE || S == kLinTail) advance(NWIN, false);
+        constexpr bool R2 = decltype(with_r2)::value;
+        ask_bytes(true, R2);
+        if (!GACT_LIN_SLIDE || S == kLinTail) advance(R2 ? NWIN : C1 + 1, false);
         // lane 0 of region 1 sits on the j = 0 border: one gap below its zero level
         const uint32_t Hl1 = lin_hand_shr1(H1, k1v, W[o]);
         // lane 0 of region 2 continues lane 15's region 1 (one step ago = same row)
-        const uint32_t Hl2 = lin_hand_ror1_shr1(H1, k1v, H2, k2v);
+        uint32_t Hl2 = 0;
+        if (R2) Hl2 = lin_hand_ror1_shr1(H1, k1v, H2, k2v);
         uint32_t U[CT];
-        upper_all(U, false, o);
-        Hdiag1 = Hl1; Hdiag2 = Hl2;
+        upper_all(LinPos<0>{}, LinPos<R2 ? CT : C1>{}, U, false, o);
+        Hdiag1 = Hl1;
+        if (R2) Hdiag2 = Hl2;
         uint32_t Ha = Hl1, Hb = Hl2;
         static_assert(C2 >= C1, "region 2 is the longer chain");
 #pragma unroll
         for (int c = 0; c < C1; c++) {                                           // :151-160: H_left + g is H_left as it stands
-            G[c] = lin_max<kLinSplitBuiltins>(U[c], Ha); G[C1 + c] = lin_max<kLinSplitBuiltins>(U[C1 + c], Hb);
-            GACT_SB();
-            Ha = G[c]; Hb = G[C1 + c];
+            G[c] = lin_max<kLinSplitBuiltins>(U[c], Ha);
+            if (R2) { G[C1 + c] = lin_max<kLinSplitBuiltins>(U[C1 + c], Hb); GACT_SB(); Hb = G[C1 + c]; }
+            Ha = G[c];
         }
-#pragma unroll
-        for (int c = 2 * C1; c < CT; c++) { G[c] = lin_max<kLinSplitBuiltins>(U[c], Hb); Hb = G[c]; }
-        H1 = Ha; H2 = Hb;
-    };
-    // a step in which region 2 is in front of its row 1 in every lane (see 7. below): region 1 alone, region 2's zero level
-    auto step_r1 = [&]() {
-        ask_bytes(true, false);
-        advance(C1 + 1, false);
-        const uint32_t Hl1 = lin_hand_shr1(H1, k1v, W[0]);
-        uint32_t P[C1], U[C1];
-#pragma unroll
-        for (int c = 0; c < C1; c++) P[c] = __builtin_amdgcn_perm(rb1b, rb1, qb[c]);
-        GACT_SB();
-#pragma unroll
-        for (int c = 0; c < C1; c++) U[c] = (c == 0 ? Hdiag1 : G[c - 1]) + P[c];
-        ask_rows(true, false, false);
-        GACT_SB();
-#pragma unroll
-        for (int c = 0; c < C1; c++) U[c] = GACT_LIN_MAX3 ? pk_max3f_s(U[c], W[c + 1], G[c]) : lin_max<kLinSplitBuiltins>(pk_max_sgpr(U[c], W[c + 1]), G[c]);
-        GACT_SB();
-        Hdiag1 = Hl1;
-        uint32_t Ha = Hl1;
-#pragma unroll
-        for (int c = 0; c < C1; c++) { G[c] = lin_max<kLinSplitBuiltins>(U[c], Ha); Ha = G[c]; }
         H1 = Ha;
+        if (R2) {
+#pragma unroll
+            for (int c = 2 * C1; c < CT; c++) { G[c] = lin_max<kLinSplitBuiltins>(U[c], Hb); Hb = G[c]; }
+            H2 = Hb;
+        }
     };
+    auto step = [&](auto pos) { step_plain(pos, std::true_type{}); };
+    auto step_r1 = [&]() { step_plain(LinPos<kLinTail>{}, std::false_type{}); };
 
-    // ---- pointer phase: region 2 on tagged scores; G = 4H + 2 there: H_up'' without an instruction, the diagonal gets
-    //      its tag 3 from the look-up word (+1), the left neighbour its tag 1 from the gap subtraction (4|g| + 1), and
-    //      "low bits := 2" is one fast-class v_bitop3_b32
-    // filing the codes.  A step of the remainder (kLinTail): slot c's code goes into acc[c], a v_and_b32 beside the v_bitop3 and a
-    // v_pk_mad_u16 beside the next slot's maximum.  Step S of a whole block: the pair's v_perm_b32 stands where the odd column's
-    // v_and_b32 stood, its v_and_b32 beside the next slot's subtraction, its v_pk_mad_u16 (none at S = 0 and S = 4) beside
-    // that slot's maximum; Hq: the even column's H'' until its partner's exists
+    // ---- pointer phase and the filing of the codes: as in dp_pass_lin_split; what is left of the left neighbour's gap
+    //      subtraction is the re-tag 2 -> 1, a - 1
     static_assert(C2 >= 3 && (C2 & 1), "the last pair is filed while the unpaired slot is computed");
     auto file_group = [&](const int S, const int c, const uint32_t x) {
         uint32_t &r = grp[c - 2 + (S >> 2)];
         r = (S & 3) ? pk_shl_add4(r, x) : x;
     };
-    auto step_tagged = [&](auto pos) {
+    // a step of the pointer phase.  Without region 1: it is past its last row in every lane (see 7. below); H1 stays what
+    // lane 15 left at step T_end - LAG
+    auto step_ptr = [&](auto pos, auto with_r1) {
         constexpr int S = decltype(pos)::value;
         constexpr bool blk = S != kLinTail;
+        constexpr bool R1 = decltype(with_r1)::value;
         constexpr int o = lin_strip_at(S, 0);
-        ask_bytes(true, true);
-        if (!GACT_LIN_SLIDE || !blk) advance(C1 + 1, true);
-        const uint32_t Hl1 = lin_hand_shr1(H1, k1v, W[o]);
+        ask_bytes(R1, true);
+        if (!GACT_LIN_SLIDE || !blk) advance(R1 ? C1 + 1 : 0, true);
+        uint32_t Hl1 = 0;
+        if (R1) Hl1 = lin_hand_shr1(H1, k1v, W[o]);
         // lane 15's region-1 column enters region 2 scaled and tagged 2
         const uint32_t Hl2 = lin_hand_shr1_over(lin_hand_scaled_ror1(H1, k12v), H2, k24v);
         uint32_t U[CT];
-        upper_all(U, true, o);
-        Hdiag1 = Hl1; Hdiag2 = Hl2;
+        upper_all(LinPos<R1 ? 0 : C1>{}, LinPos<CT>{}, U, true, o);
+        if (R1) Hdiag1 = Hl1;
+        Hdiag2 = Hl2;
         uint32_t Ha = Hl1, Hb = Hl2;
         uint32_t tprev = 0, Hq = 0, x = 0;
 #pragma unroll
         for (int c = 0; c < C2; c++) {
-            const bool both = c < C1;
+            const bool both = R1 && c < C1;
             const bool filed = blk && c >= 2 && !(c & 1);                        // the pair (c - 2, c - 1) is filed in this slot
             const uint32_t Db = Hb - onev;                                       // G'' tagged 2 -> D'' tagged 1
             if (filed) x &= kLinPairMask;
             GACT_SB();
-            const uint32_t Hp = lin_max<kLinSplitBuiltins>(U[C1 + c], Db);                           // the low bits: the op (:162-164)
+            const uint32_t Hp = lin_max<kLinSplitBuiltins>(U[C1 + c], Db);       // the low bits: the op (:162-164)
             if (both) { G[c] = lin_max<kLinSplitBuiltins>(U[c], Ha); Ha = G[c]; }
             if (!blk && c > 0) acc[c - 1] = pk_shl_add4(acc[c - 1], tprev);
             if (filed) file_group(S, c, x);
             GACT_SB();
-            G[C1 + c] = andn_or<kLinSplitBuiltins>(Hp, c3v, c2v);                                   // low bits := 2
+            G[C1 + c] = andn_or<kLinSplitBuiltins>(Hp, c3v, c2v);                // low bits := 2
             if (!blk || c == C2 - 1) tprev = Hp & c3v;
             else if (c & 1) x = __builtin_amdgcn_perm(Hp, Hq, psel);
             else Hq = Hp;
@@ -900,55 +842,12 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
         }
         if (!blk) acc[C2 - 1] = pk_shl_add4(acc[C2 - 1], tprev);
         else odd = S ? pk_shl_add4(odd, tprev) : tprev;
-        H1 = Ha; H2 = Hb;
-    };
-    // a step of the pointer phase in which region 1 is past its last row in every lane (see 7. below): region 2 alone; H1
-    // stays what lane 15 left at step T_end - LAG
-    auto step_tagged_r2 = [&](auto pos) {
-        constexpr int S = decltype(pos)::value;
-        constexpr bool blk = S != kLinTail;
-        constexpr int o = lin_strip_at(S, 0);
-        ask_bytes(false, true);
-        if (!GACT_LIN_SLIDE || !blk) advance(0, true);
-        const uint32_t Hl2 = lin_hand_shr1_over(lin_hand_scaled_ror1(H1, k12v), H2, k24v);
-        uint32_t P[C2], U[C2];
-#pragma unroll
-        for (int c = 0; c < C2; c++) P[c] = __builtin_amdgcn_perm(rb2b, rb2, qb[C1 + c]);
-        GACT_SB();
-#pragma unroll
-        for (int c = 0; c < C2; c++) U[c] = (c == 0 ? Hdiag2 : G[C1 + c - 1]) + P[c];
-        ask_rows(false, true, true);
-        GACT_SB();
-#pragma unroll
-        for (int c = 0; c < C2; c++) U[c] = GACT_LIN_MAX3 ? pk_max3f_s(U[c], T[o + c], G[C1 + c]) : lin_max<kLinSplitBuiltins>(pk_max_sgpr(U[c], T[o + c]), G[C1 + c]);
-        GACT_SB();
-        Hdiag2 = Hl2;
-        uint32_t Hb = Hl2;
-        uint32_t tprev = 0, Hq = 0, x = 0;
-#pragma unroll
-        for (int c = 0; c < C2; c++) {
-            const bool filed = blk && c >= 2 && !(c & 1);
-            const uint32_t Db = Hb - onev;
-            if (filed) x &= kLinPairMask;
-            GACT_SB();
-            const uint32_t Hp = lin_max<kLinSplitBuiltins>(U[c], Db);
-            if (!blk && c > 0) acc[c - 1] = pk_shl_add4(acc[c - 1], tprev);
-            if (filed) file_group(S, c, x);
-            GACT_SB();
-            G[C1 + c] = andn_or<kLinSplitBuiltins>(Hp, c3v, c2v);
-            if (!blk || c == C2 - 1) tprev = Hp & c3v;
-            else if (c & 1) x = __builtin_amdgcn_perm(Hp, Hq, psel);
-            else Hq = Hp;
-            GACT_SB();
-            Hb = G[C1 + c];
-        }
-        if (!blk) acc[C2 - 1] = pk_shl_add4(acc[C2 - 1], tprev);
-        else odd = S ? pk_shl_add4(odd, tprev) : tprev;
+        if (R1) H1 = Ha;
         H2 = Hb;
     };
+    auto step_tagged = [&](auto pos) { step_ptr(pos, std::true_type{}); };
+    auto step_tagged_r2 = [&](auto pos) { step_ptr(pos, std::false_type{}); };
     // the eight steps of a whole block, each with its place
-#define GACT_LIN_BLOCK8(f) do { f(LinPos<0>{}); f(LinPos<1>{}); f(LinPos<2>{}); f(LinPos<3>{}); \
-                                f(LinPos<4>{}); f(LinPos<5>{}); f(LinPos<6>{}); f(LinPos<7>{}); } while (0)
 #undef GACT_SB
     auto enter_tagged = [&]() {
         c3v = vconst(kc.c3); onev = vconst(kc.one); c2v = vconst(kc.tag2);
@@ -965,11 +864,7 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
     };
 
     int t = 1;
-    // 7. Region 2 runs LAG steps behind region 1 and every tile ends on the wave's last step: for the first LAG steps region 2
-    //    is in front of its row 1 in EVERY lane (its values are the zero level, whatever the reads hold), for the last LAG
-    //    steps region 1 is past its last row in every lane (nothing reads what it would compute: lane 0 of region 2 takes
-    //    lane 15's H of step T_end - LAG at step T_end - LAG + 1 and rows past R after that).  Those steps run without the
-    //    idle region's column slots: 16 x 65 + up to 16 x 37 of a pass's ~53 k instructions.
+    // (7. in dp_pass_lin_split: the first and the last LAG steps run without the idle region's column slots)
     for (const int tP = imin(LAG, imin(tB - 1, T_end)); t <= tP; t++) step_r1();
     if (t > 1) {
         // region 2 starts at its zero level: what its slots "computed" at step t - 1, in that step's frame
@@ -1011,17 +906,13 @@ __device__ __forceinline__ uint32_t dp_pass_lin_split_col(const P16Consts &kc, c
         bd.lo[0] = bd.lo[1] = lo_.lo[0]; bd.hi[0] = bd.hi[1] = hi_.hi[0];
         bd.full[0] = fullA | (b <= 0); bd.full[1] = fullB | (b <= 0);
     }
-    // whole blocks of eight steps, each followed by its flush (an `if ((k & 7) == 7)` inside one loop is
-    // if-converted by the compiler: the re-pairing v_perm of the flush would then run at every step)
+    // whole blocks of eight steps, each followed by its flush
     int k = 0;
 #if GACT_LIN_SLIDE
     // (13. above: region 1's and the border's C1 + 1 levels and region 2's C2 scaled ones become strips for the whole blocks)
     if (tagged) { lin_strip_enter<C1 + 1>(W, gs); lin_strip_enter<C2>(T, g4s); }
 #endif
-    // (two loops one behind the other, not one loop with a branch inside: the two kinds of step keep their registers
-    //  differently, and a loop that holds both moves ~90 registers per block to reconcile them)
-    // (the eight steps are straight-line code: the stream offsets are immediates, the diagonal's registers are renamed)
-    // (a whole block keeps its codes in the byte groups and leaves acc[] alone: zero, as the remainder's partial flush needs it)
+    // (two loops, straight-line steps, acc[] left alone: the notes at the same place in dp_pass_lin_split)
     while (t + 7 <= T_end && t <= T_end - LAG) {
         GACT_LIN_BLOCK8(step_tagged);
         t += 8; k += 8;

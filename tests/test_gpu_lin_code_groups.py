@@ -39,11 +39,11 @@ def _max_linear_scoring():
     return best
 
 
-def pass_shape(x):
+def pass_shape(x, tile=TILE, overlap=OVERLAP):
     """a pass over one non-first tile of x rows and x columns (split_last_step, split_first_pointer_step in csrc/gact_p16s.hpp,
-    the loops of dp_pass_lin_split): pointer steps, first pointer step minus (T_end - LAG), whole blocks of step_tagged, whole
-    blocks of step_tagged_r2, steps behind the last whole block"""
-    early = TILE - OVERLAP
+    the loops of dp_pass_lin_split, the same in dp_pass_lin_split_col): pointer steps, first pointer step minus (T_end - LAG), whole
+    blocks of step_tagged, whole blocks of step_tagged_r2, steps behind the last whole block"""
+    early = tile - overlap
     first = max(1, x - early + 1)
     jj = first + (C2 * K_GROUP - x)
     t = tB = first + (jj - 1) // C2 + K_GROUP

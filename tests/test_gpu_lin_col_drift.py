@@ -12,12 +12,18 @@ pass.  Its look-up byte needs match + 2|g| <= 63 where the guard admits match + 
 kernels on the row-drifted pass.  That happens at small tiles only, so the last scoring on either side of the rule runs at
 tile 64 on the adversarial reads of tests/scoring_edges.py.
 
+The row-drifted frame is reachable at such tiles only, so every shape of the pointer phase that tile 64 / overlap 8 can give it
+(pass_shape of tests/test_gpu_lin_code_groups.py: whole blocks of both regions, of region 2 alone, none, every remainder, a
+first pointer step on either side of T_end - LAG) runs there too, under (62, -1, -1, -1), on last tiles of every size 1..64
+of exact copies and on copies with errors.
+
 Every record field is compared with the oracle (oracle.gact_many), as tests/test_gpu_lin_code_groups.py does; its helpers
 build and run the lists."""
 import numpy as np
 import pytest
 
-from test_gpu_lin_code_groups import LEN, OVERLAP, PLAIN, TILE, _check_launch, _max_linear_scoring, _run, _same, _sized_reads
+from test_gpu_lin_code_groups import (LEN, OVERLAP, PLAIN, TILE, _check_launch, _max_linear_scoring, _run, _same, _sized_reads,
+                                      pass_shape)
 
 pytestmark = pytest.mark.gpu
 
@@ -134,5 +140,99 @@ def test_either_side_of_the_byte_rule_at_tile_64(monkeypatch, oracle, scoring, l
             assert st["linear_gap"] and st["layout"] == "packed16-split" and st["coop_walks"] == (launch == "coop"), (tag, st)
             assert st["lin_row_drift"] == (scoring[0] - 2 * scoring[3] > 63), (tag, st)        # the pass meant is the one that ran
             _compare(got, _want(oracle, edge, scoring, er, name, comp, cands, qcat, qoffs, True), tag)
+    finally:
+        eng.close()
+
+
+ROW_TILE, ROW_OVERLAP, ROW_LEN, ROW_SCORING = 64, 8, 200, (62, -1, -1, -1)
+ROW_SIZES = tuple(range(1, ROW_TILE + 1))
+
+
+@pytest.fixture(scope="module")
+def row_lists(oracle):
+    """exact copies of one 200-base segment, whole and cut at either end, with candidates that leave a last tile of every size
+    1..64 in each direction, and two copies with 4 % and 10 % errors seeded at the same positions; the oracle's records of
+    both strands under (62, -1, -1, -1); and the check that the exact copies' tiles give the pass every shape of its pointer
+    phase that this tile size can"""
+    from gact_amd import synth
+    from scoring_edges import EDGES, threshold
+    edge = next(e for e in EDGES if e.name == "lin-match-64")
+    assert (edge.tile, edge.overlap) == (ROW_TILE, ROW_OVERLAP)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    g = acgt[np.random.default_rng(911).integers(0, 4, size=ROW_LEN)]
+    cuts = ((0, ROW_LEN), (0, ROW_LEN - 30), (25, ROW_LEN))
+    rs = synth.ReadSet()
+    rs.reads = [g.copy()] + [g[a:b].copy() for a, b in cuts] + [synth.revcomp(g[a:b]) for a, b in cuts]
+    rs.names = ["sized_ref"] + ["sized_q%d" % k for k in range(3)] + ["sized_qrc%d" % k for k in range(3)]
+    # two copies with errors, so that the same last tiles also leave the diagonal: the left neighbour's and the upper
+    # neighbour's terms and the hand-overs decide values here, not only shapes (exact copies never take them)
+    rng = np.random.default_rng(912)
+    noisy = []
+    for rate in (0.04, 0.10):
+        out = []
+        for base in g:
+            r = rng.random()
+            if r < rate / 3:
+                continue                                                 # deletion
+            if r < 2 * rate / 3:
+                out.append(acgt[rng.integers(0, 4)])                     # insertion in front of the base
+            out.append(acgt[rng.integers(0, 4)] if r > 1 - rate / 3 else base)   # substitution (a quarter of them silent)
+        noisy.append(np.array(out, dtype=np.uint8))
+    first_noisy = len(rs.reads)
+    rs.reads += noisy + [synth.revcomp(q) for q in noisy]
+    rs.names += ["noisy_q%d" % k for k in range(2)] + ["noisy_qrc%d" % k for k in range(2)]
+    adv = ROW_TILE - ROW_OVERLAP
+    positions = sorted({ROW_LEN - x for x in ROW_SIZES} | {ROW_LEN - adv - x for x in ROW_SIZES} |
+                       {adv + x for x in ROW_SIZES} | set(ROW_SIZES))
+    sf = [(0, 1 + k, p, p - a) for k, (a, b) in enumerate(cuts) for p in positions if a <= p < b]
+    sr = [(0, 4 + k, p, p - a) for k, (a, b) in enumerate(cuts) for p in positions if a <= p < b]
+    for k, q in enumerate(noisy):
+        pos = [p for p in positions if 20 <= p < min(ROW_LEN, len(q)) - 20][::3]
+        sf += [(0, first_noisy + k, p, p) for p in pos]
+        sr += [(0, first_noisy + 2 + k, p, p) for p in pos]
+    sf = np.array(sf, dtype=synth.CAND_DTYPE); sr = np.array(sr, dtype=synth.CAND_DTYPE)
+    seen = set()
+    for c in sf[sf["query_id"] == 1]:
+        _, traces = oracle.gact(rs.reads[0].tobytes(), rs.reads[1].tobytes(), int(c["ref_pos"]), int(c["query_pos"]),
+                                tile_size=ROW_TILE, tile_overlap=ROW_OVERLAP, ref_id=0, query_id=1, trace_cap=16)
+        seen |= {(t.reverse, t.ref_len) for t in traces if not t.first and t.ref_len == t.query_len}
+    missing = [(d, x) for d in (0, 1) for x in ROW_SIZES if (d, x) not in seen]
+    assert not missing, "no non-first tile of these (direction, size): %s" % missing
+    for d in (0, 1):
+        shapes = [pass_shape(x, ROW_TILE, ROW_OVERLAP) for dd, x in seen if dd == d and x in ROW_SIZES]
+        assert {rem for _, _, _, _, rem in shapes} == set(range(8))                  # the remainders 0..7
+        assert any(off <= 0 for _, off, _, _, _ in shapes) and any(off > 0 for _, off, _, _, _ in shapes)
+        assert any(both > 1 and r2 > 0 for _, _, both, r2, _ in shapes)              # whole blocks of both kinds
+        assert any(both == 0 and r2 > 0 for _, _, both, r2, _ in shapes)             # only region-2 blocks
+        assert any(both == 0 and r2 == 0 and n > 0 for n, _, both, r2, _ in shapes)  # no whole block at all
+    assert len(sf) + len(sr) <= 1500, len(sf) + len(sr)
+    cat, offs = rs.concat(); rcat, roffs = rs.concat(rc=True)
+    th = threshold(edge, ROW_SCORING)
+    kw = dict(same_file=True, tile_size=ROW_TILE, tile_overlap=ROW_OVERLAP, threshold=th, scoring=ROW_SCORING, n_threads=8)
+    want = (oracle.gact_many(cat, offs, cat, offs, sf, complement=False, **kw)[0],
+            oracle.gact_many(cat, offs, rcat, roffs, sr, complement=True, **kw)[0])
+    for w in want:
+        w.setflags(write=False)
+    return (cat, offs, rcat, roffs), (sf, sr), want, th
+
+
+@pytest.mark.parametrize("launch", LAUNCHES)
+def test_row_drift_at_every_shape_of_the_pointer_phase(monkeypatch, row_lists, launch):
+    from gact_amd import engine
+    from test_gpu_int16_edges import LAYOUTS
+    (cat, offs, rcat, roffs), cands, want, th = row_lists
+    for var, val in LAYOUTS[launch].items():
+        monkeypatch.setenv(var, val)
+    if launch != "coop":
+        monkeypatch.setenv("GACT_HIP_COOP", "0")
+    eng = engine.Engine(tile_size=ROW_TILE, tile_overlap=ROW_OVERLAP, scoring=ROW_SCORING, threshold=th)
+    try:
+        eng.upload(engine.SET_REF, cat, offs); eng.upload(engine.SET_QUERY, cat, offs); eng.upload(engine.SET_QUERY_RC, rcat, roffs)
+        for comp in (False, True):
+            got = eng.extend(cands[comp], complement=comp, same_file=True)
+            st = eng.last_run_stats()
+            _check_launch(st, launch)
+            assert st["lin_row_drift"], st                       # the row-drifted pass is the one that ran
+            _same(got, want[comp], "tile 64 %s, row drift, %s" % (launch, "rc" if comp else "fwd"))
     finally:
         eng.close()
