@@ -868,4 +868,91 @@ __device__ __forceinline__ int chain_bucket(const ChainState &s, const KParams &
     return kBuckets - 1 - length_class(tiles);
 }
 
+// ---------------------------------------------------------------------------
+// The control phase of a persistent main launch, shared by its three kernels (extend_p16_kernel, extend_roles_kernel,
+// extend_coop_kernel).  State goes in and out as separate scalars by reference: the DP loop owns the register file, and a
+// struct of state moves its allocation (profiles/r15, profiles/r16).
+
+// Where a launch starts popping: longest chains first (ChainQueues) -- except that a launch with a critical lane beside it
+// (cq.leave_longest) starts behind the classes that hold the longest `leave_longest` chains of its own set and comes back
+// to them last.
+__device__ __forceinline__ int main_first_bucket(const ChainQueues &cq)
+{
+    int bucket_first = 0;
+    if (cq.leave_longest > 0) {
+        int acc = 0;
+        while (bucket_first < kBuckets && (acc += cq.bucket_count[bucket_first]) <= cq.leave_longest) bucket_first++;
+        if (bucket_first >= kBuckets) bucket_first = 0;
+    }
+    return bucket_first;
+}
+
+// Pops the group's next chain from the length-class queues: the candidate's index, or -1 when there is none (now).  The
+// group pops class (bucket_first + my_bucket) mod kBuckets; `lead` = the group's lane 0 does the atomic.  TWO_SETS
+// (overlapped seeding): once the launch's own set is empty and the second one is open, the group goes on with that one.
+template <bool TWO_SETS, int LANES>
+__device__ __forceinline__ int main_pop(const ChainQueues &cq, bool lead, int bucket_first, int &my_bucket, bool &second_set)
+{
+    int cand = -1;
+    for (;;) {
+        const int *q_count = (TWO_SETS && second_set) ? cq.more_count : cq.bucket_count;
+        int *q_pop = (TWO_SETS && second_set) ? cq.more_pop : cq.bucket_pop;
+        const int *q_live = (TWO_SETS && second_set) ? cq.more_live : cq.live;
+        while (my_bucket < kBuckets) {
+            // look before popping: an atomic on a class that is empty or drained is one of ~12,000
+            // (every group comes by) serialised on one address -- 4 ms of a 55 ms launch with 32 empty classes
+            const int bkt = bucket_first + my_bucket - (bucket_first + my_bucket >= kBuckets ? kBuckets : 0);
+            const int cnt = q_count[bkt];
+            int idx = cnt;
+            if (lead && __hip_atomic_load(&q_pop[bkt], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < cnt)
+                idx = atomicAdd(&q_pop[bkt], 1);
+            idx = __shfl(idx, 0, LANES);
+            if (idx < cnt) {
+                cand = q_live[(size_t)bkt * cq.live_stride + idx];
+                break;
+            }
+            my_bucket++;
+        }
+        if (cand >= 0 || second_set || !TWO_SETS) break;
+        // this launch's own queues are empty.  Overlapped seeding: a second set is being filled by a seed
+        // launch on another stream; *more_flag is written in stream order BEHIND that launch, so once it
+        // reads non-zero the launch has ended and its writes are in memory -- an acquire at agent scope
+        // (this XCD's caches drop what they hold of them) and the wave goes on with that set
+        if (__hip_atomic_load(cq.more_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) break;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        second_set = true;
+        my_bucket = 0;
+    }
+    return cand;
+}
+
+// Consume (gact.cpp:111-133 / :172-194; non-first tiles only), the case that the walk of slot's R x Q tile counts: the
+// tile is counted and the chain advances by the walk's result, which lane `src` of the group holds.  (The other case --
+// the walk left the band its pass stored, the tile comes again -- is two statements and stays with the callers, as do
+// the load and the store of the state: every form that took them along moved spills, profiles/r16.)
+template <int LANES>
+__device__ __forceinline__ void main_count_advance(ChainState &s, int R, int Q, int src, const ScoreWalk &wk, int ref_steps,
+                                                   int query_steps, int nst)
+{
+    s.full = 0;
+    s.n_tiles++;
+    s.cells += (int64_t)R * Q;
+    chain_advance<LANES>(s, false, wk, ref_steps, query_steps, nst, src);
+}
+
+// Issue priority of a wave's DP pass: among the passes, the waves that carry the longest chains go first -- when there are
+// fewer chains than tile slots the launch lasts as long as its longest chain.  (Everything around the pass runs at 3.)
+__device__ __forceinline__ void pass_prio(const ChainQueues &cq, const KParams &kp, int wave_longest, int &rank_turn, int &rank_cached)
+{
+    const int ref_longest = ranked_longest(cq, kp, wave_longest, rank_turn, rank_cached);
+    // ranking mode (prio_bases[0] == 0): prio_bases[1] = thresholds in sixteenths of the longest, hi << 8 | mid
+    const bool rank_hi = kp.prio_bases[0] == 0 ? 16 * wave_longest > (kp.prio_bases[1] >> 8) * ref_longest
+                                               : wave_longest > kp.prio_bases[1];
+    const bool rank_mid = kp.prio_bases[0] == 0 ? 16 * wave_longest > (kp.prio_bases[1] & 255) * ref_longest
+                                                : wave_longest > kp.prio_bases[0];
+    if (rank_hi) __builtin_amdgcn_s_setprio(2);
+    else if (rank_mid) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
+}
+
 }  // namespace gact

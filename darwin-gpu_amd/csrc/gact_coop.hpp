@@ -20,15 +20,15 @@
 //     positions carried from move to move (gact_walk_pos.hpp).  The bases of a cell come out of the loader's
 //     staging words, which stay in LDS until their bank is loaded again.
 //
-// Hand-over: LDS words only.  A job's fields are written before its state word (posted), a lane claims a job with a
-// compare-and-swap on the state word, a result is written before the state word says done; the pointer words a walk reads
-// were stored by the posting wave and waited for (s_waitcnt vmcnt(0)) before it posted, and are read past the L1 (sc1).
+// Hand-over (gact_two_bank.hpp: the two-bank DP wave, its job record and bank words, shared with the role launch): a job's
+// fields are written before its state word (posted), a lane claims a job with a compare-and-swap on the state word, a
+// result is written before the state word says done.
 // Progress: a wave that needs a result either finds it, or finds the job unclaimed and walks it itself (after the lock), or
 // finds it claimed -- then the lock holder is walking it and finishes in bounded time.  A watchdog turns a hang into a
 // reported error (bit 30 of the band_redos counter).
 #pragma once
 
-#include "gact_lin.hpp"
+#include "gact_two_bank.hpp"
 #include "gact_walk_pos.hpp"
 
 namespace gact {
@@ -38,21 +38,12 @@ constexpr int kCoopJobs = (kBlockThreads / 64) * 8 * kCoopBanks;       // tile s
 static_assert(kCoopJobs == 64, "a walking wave serves every job of its block, one per lane");
 constexpr int kCoopCacheStride = 36;                                   // dwords of region cache per walking lane (32 used)
 
-struct CoopJob {                 // posting wave -> walking lane
-    uint32_t ws_off;             // the tile's pointer words: byte offset of its (wsA | wsB) from ws_all
-    int R, Q;
-    int k0;                      // stored step of the start cell (L::walk_start)
-    int v0;                      // H[R][Q] from the pass
-    int band_lim;                // see walk_chain_lin; -1: every block is there
-    uint32_t where;              // bits 0-7: staged position of the ref slice's first base, 8-15: the query slice's,
-                                 // 16: AlignWithBT's `reverse`, 17-31: dword index of the tile's ref segment in the stage array
-    int pad_;
-};
-struct CoopDone { int ref_steps, query_steps, dv, redo; };
+// a job and its result (gact_two_bank.hpp)
+struct CoopJob : TileJob { int pad_; };      // posting wave -> walking lane
+using CoopDone = TileDone;
 // state word of a job: (sequence number << 2) | phase; phase 1 posted, 2 claimed by a walking lane, 3 done
 
-template <class L> constexpr size_t coop_bank_words() { return (size_t)L::G::kMaxFlush * L::kWalkQuads * kWsRow * 4; }
-template <class L> __host__ constexpr size_t coop_ws_words(int blocks) { return (size_t)blocks * (kBlockThreads / 64) * kCoopBanks * coop_bank_words<L>(); }
+template <class L> __host__ constexpr size_t coop_ws_words(int blocks) { return (size_t)blocks * (kBlockThreads / 64) * kCoopBanks * two_bank_words<L>(); }
 
 // One batch: lane j claims job j if it is posted, all claimed jobs are walked in lock step, results written.
 template <class L>
@@ -217,7 +208,7 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
     __shared__ CoopDone done[kCoopJobs];
     __shared__ uint32_t jstate[kCoopJobs];
     __shared__ __attribute__((aligned(16))) uint32_t cache_lds[kCoopJobs * kCoopCacheStride];
-    __shared__ int bank_lds[kGroupsPerBlock][kCoopBanks][6];   // {R_A, Q_A, R_B, Q_B, state word of the jobs in flight (0: none), -}
+    __shared__ int bank_lds[kGroupsPerBlock][kCoopBanks][kBankWords];   // (BankWord; in flight: the jobs' state word when done)
     __shared__ uint32_t walk_lock;
 
     uint32_t *const lin_lut = LinLutLds<L::kLutWords>::get();      // the pass's table of look-up words (gact_lin.hpp 8.)
@@ -240,25 +231,17 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
     uint8_t *q8 = ref8;                                                 // (never written: load_pair_packed<..., false>)
     const uint16_t *ref16_lane = reinterpret_cast<const uint16_t *>(ref8) + (L::kRow0 - 1 - w.gl);
     // a wave's pointer words: [bank][flush block][uint4 n][tile A | tile B][the wave's 64 lanes]
-    uint32_t *ws_wave = ws_all + (size_t)(blockIdx.x * (kBlockThreads / 64) + wave_in_block) * (kCoopBanks * coop_bank_words<L>());
+    uint32_t *ws_wave = ws_all + (size_t)(blockIdx.x * (kBlockThreads / 64) + wave_in_block) * (kCoopBanks * two_bank_words<L>());
     // this lane's job of bank b: ((group in block) * 2 + slot) * 2 + b   (lanes 0 and 1 of a group: slots A and B)
     const int job_base = (group_in_block * kSlots + (w.gl & 1)) * kCoopBanks;
 
     for (int b = 0; b < kCoopBanks; b++)
         if (w.gl < kSlots) { chain_lds[group_in_block][b][w.gl].phase = 2; chain_lds[group_in_block][b][w.gl].cand = -1; }
-    if (w.gl == 0) {
-        int *bt = &bank_lds[group_in_block][0][0];
-        for (int n = 0; n < kCoopBanks * 6; n++) bt[n] = 0;
-    }
+    bank_reset(&bank_lds[group_in_block][0][0], w.gl == 0);
     wave_sync();
     bool exhausted = false;
     int my_bucket = 0;
-    int bucket_first = 0;
-    if (cq.leave_longest > 0) {
-        int acc = 0;
-        while (bucket_first < kBuckets && (acc += cq.bucket_count[bucket_first]) <= cq.leave_longest) bucket_first++;
-        if (bucket_first >= kBuckets) bucket_first = 0;
-    }
+    const int bucket_first = main_first_bucket(cq);
     bool second_set = false;
     constexpr bool one_set = !TWO_SETS;
     int idle_polls = 0;
@@ -266,21 +249,16 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
     int rank_turn = 0, rank_cached = 0;
     int bank = 0;
     __builtin_amdgcn_s_setprio(3);
-#ifdef GACT_STAMPS
-    unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long tl_start = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long tl_cyc0 = __builtin_amdgcn_s_memtime();
-    unsigned long long tl_empty = 0;
-#endif
+    GACT_STAMPS_BEGIN;
 
     for (;;) {
         ChainState *st = chain_lds[group_in_block][bank];
         GACT_STAMP(t_w0);
         // ---- the results of this bank's walks (posted one pass of the other bank ago): gact.cpp:111-133 / :172-194
-        const int *bk = &bank_lds[group_in_block][bank][0];
-        const uint32_t want = (uint32_t)__builtin_amdgcn_readfirstlane(bk[4]);       // (the same for the wave's four groups)
+        int *bk = bank_lds[group_in_block][bank];
+        const uint32_t want = (uint32_t)__builtin_amdgcn_readfirstlane(bk[kBankWant]);       // (the same for the wave's four groups)
         if (want != 0) {
-            const int sv_R[kSlots] = {bk[0], bk[2]}, sv_Q[kSlots] = {bk[1], bk[3]};
+            const int sv_R[kSlots] = {bk[kBankRA], bk[kBankRB]}, sv_Q[kSlots] = {bk[kBankQA], bk[kBankQB]};
             const bool mine = w.gl < kSlots && ((w.gl & 1) ? sv_R[1] : sv_R[0]) > 0;
             const int my_job = job_base + bank;
             // somebody has to walk: whoever needs a result first walks every posted job of the block (see the header)
@@ -306,12 +284,13 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
                     break;
                 }
             }
+            // (from here to the end of the block: the same text in extend_roles_kernel (gact_roles.hpp) -- as one function it moved spills, profiles/r16)
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             int ref_steps = 0, query_steps = 0, nst = 0, redo = 0;
             ScoreWalk wk;
             wk.score = 0; wk.pend_gap = 0; wk.open_flag = 0; wk.have_left = 0; wk.left_first_gap = 0;
             if (mine) {
-                const CoopDone d = done[my_job];
+                const TileDone d = done[my_job];
                 wk.load(st[w.gl & 1]);
                 wk.score += d.dv;                                        // (open == extend: the gap bookkeeping decides nothing)
                 ref_steps = d.ref_steps; query_steps = d.query_steps; nst = d.ref_steps + d.query_steps; redo = d.redo;
@@ -324,10 +303,7 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
                         s.full = 1;
                         if (w.gl == 0) atomicAdd(cq.band_redos, 1);
                     } else {
-                        s.full = 0;
-                        s.n_tiles++;
-                        s.cells += (int64_t)sv_R[h] * sv_Q[h];
-                        chain_advance<LANES>(s, false, wk, ref_steps, query_steps, nst, h);
+                        main_count_advance<LANES>(s, sv_R[h], sv_Q[h], h, wk, ref_steps, query_steps, nst);
                     }
                     wave_sync();
                     if (w.gl == 0) st[h] = s;
@@ -335,7 +311,7 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
                 wave_sync();
             }
             wave_sync();
-            if (w.gl == 0) bank_lds[group_in_block][bank][4] = 0;
+            if (w.gl == 0) bk[kBankWant] = 0;
             wave_sync();
         }
         // ---- the queues are empty: chains move out of bank 1 into free slots of bank 0, so that what is left of the launch runs
@@ -362,6 +338,7 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
         bool have[kSlots];
         int Tend_h[kSlots], tB_h[kSlots];
         int longest = 0;
+        // (the pick below, to the end of the loop over h: one of three copies, the others in extend_p16_kernel (gact_p16.hpp) and extend_roles_kernel (gact_roles.hpp))
 #pragma unroll
         for (int h = 0; h < kSlots; h++) {
             ChainState s = st[h];
@@ -380,36 +357,11 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
                     //  left to finish in waves that are no longer full, profiles/r05/ab_coop_lean_waves.txt; closing bank 1 to the
                     //  classes of fewer than 8 ... 48 tiles for such a run: ecoli10x 38.0 -> 32.5-36.3 ms, still behind; pacbio50mb
                     //  alone has no tail to cut -- queues dry at 132.9 of 135.4 ms --, single_run_vs_in_flight_experiments.txt)
-                    int cand = -1;
-                    for (;;) {
-                        const int *q_count = (TWO_SETS && second_set) ? cq.more_count : cq.bucket_count;
-                        int *q_pop = (TWO_SETS && second_set) ? cq.more_pop : cq.bucket_pop;
-                        const int *q_live = (TWO_SETS && second_set) ? cq.more_live : cq.live;
-                        while (my_bucket < kBuckets) {
-                            const int bkt = bucket_first + my_bucket - (bucket_first + my_bucket >= kBuckets ? kBuckets : 0);
-                            const int cnt = q_count[bkt];
-                            int idx = cnt;
-                            if (w.gl == 0 && __hip_atomic_load(&q_pop[bkt], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < cnt)
-                                idx = atomicAdd(&q_pop[bkt], 1);
-                            idx = __shfl(idx, 0, LANES);
-                            if (idx < cnt) {
-                                cand = q_live[(size_t)bkt * cq.live_stride + idx];
-                                break;
-                            }
-                            my_bucket++;
-                        }
-                        if (cand >= 0 || second_set || one_set) break;
-                        if (__hip_atomic_load(cq.more_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) break;
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                        second_set = true;
-                        my_bucket = 0;
-                    }
+                    const int cand = main_pop<TWO_SETS, LANES>(cq, w.gl == 0, bucket_first, my_bucket, second_set);
                     if (cand < 0) {
                         if (second_set || one_set) {
                             exhausted = true;
-#ifdef GACT_STAMPS
-                            if (!tl_empty) tl_empty = __builtin_amdgcn_s_memrealtime();
-#endif
+                            GACT_STAMPS_DO(note_empty());
                         }
                         break;
                     }
@@ -429,18 +381,17 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
             wave_sync();
         }
         if (w.gl == 0) {
-            int *bw = &bank_lds[group_in_block][bank][0];
-            bw[0] = have[0] ? pt.R[0] : 0; bw[1] = pt.Q[0]; bw[2] = have[1] ? pt.R[1] : 0; bw[3] = pt.Q[1];
+            bk[kBankRA] = have[0] ? pt.R[0] : 0; bk[kBankQA] = pt.Q[0]; bk[kBankRB] = have[1] ? pt.R[1] : 0; bk[kBankQB] = pt.Q[1];
         }
         const bool any_here = have[0] | have[1];
         if (!__any(any_here)) {
             // nothing for this bank.  The other bank may have walks in flight or chains of its own: go there; with neither,
             // the wave is done once the queues are (or waits for the second set of overlapped seeding, as extend_p16_kernel)
-            const bool other_busy = __builtin_amdgcn_readfirstlane(bank_lds[group_in_block][bank ^ 1][4]) != 0;
+            const bool other_busy = __builtin_amdgcn_readfirstlane(bank_lds[group_in_block][bank ^ 1][kBankWant]) != 0;
             if (!other_busy) {
                 const ChainState *so = chain_lds[group_in_block][bank ^ 1];
                 if (__all(exhausted && st[0].phase == 2 && st[1].phase == 2 && so[0].phase == 2 && so[1].phase == 2)) break;
-                if (!second_set && !one_set) {
+                if (!second_set && !one_set) {                  // (the wait of extend_p16_kernel, where it is explained; a third copy in extend_roles_kernel)
                     __builtin_amdgcn_s_sleep(127);
                     if (++idle_polls > 512) { second_set = true; exhausted = true; my_bucket = kBuckets; }
                 }
@@ -448,15 +399,8 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
             bank ^= 1;
             continue;
         }
-        const int T_end = wave_max_groups<LANES>(imax(have[0] ? Tend_h[0] : 0, have[1] ? Tend_h[1] : 0));
-        const int reach0 = have[0] ? tB_h[0] + (T_end - Tend_h[0]) : 0x7fffffff;
-        const int reach1 = have[1] ? tB_h[1] + (T_end - Tend_h[1]) : 0x7fffffff;
-        const int tB = wave_min_groups<LANES>(imin(reach0, reach1));
-        pt.col_from = imax(imin(have[0] ? pt.Q[0] : 0x7fff, have[1] ? pt.Q[1] : 0x7fff) - kp.early, 0);
-        pt.band = kp.band;
-        pt.lut = lin_lut;
-        pt.shift[0] = have[0] ? T_end - Tend_h[0] : 0;
-        pt.shift[1] = have[1] ? T_end - Tend_h[1] : 0;
+        int T_end, tB;
+        pair_starts<L>(kp, have, Tend_h, tB_h, lin_lut, pt, T_end, tB);
 
         GACT_STAMP(t_b);
         uint32_t qb[L::kSlotsPerLane];
@@ -467,15 +411,8 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
         GACT_STAMP(t_c);
 
         const int wave_longest = wave_max_groups<LANES>(longest);
-        const int ref_longest = ranked_longest(cq, kp, wave_longest, rank_turn, rank_cached);
-        const bool rank_hi = kp.prio_bases[0] == 0 ? 16 * wave_longest > (kp.prio_bases[1] >> 8) * ref_longest
-                                                   : wave_longest > kp.prio_bases[1];
-        const bool rank_mid = kp.prio_bases[0] == 0 ? 16 * wave_longest > (kp.prio_bases[1] & 255) * ref_longest
-                                                    : wave_longest > kp.prio_bases[0];
-        if (rank_hi) __builtin_amdgcn_s_setprio(2);
-        else if (rank_mid) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-        uint32_t *wsA = ws_wave + (size_t)bank * coop_bank_words<L>() + (w.g * LANES) * 4;
+        pass_prio(cq, kp, wave_longest, rank_turn, rank_cached);
+        uint32_t *wsA = ws_wave + (size_t)bank * two_bank_words<L>() + (w.g * LANES) * 4;
         uint32_t *wsB = wsA + 64 * 4;
         const uint32_t fin = L::template pass<false>(kc, w.gl, ref16_lane, qb, T_end, tB, wsA, wsB, pt);
         __builtin_amdgcn_s_setprio(3);
@@ -487,29 +424,15 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
 
         // ---- post the walks of this bank: lane h of the group writes slot h's job, its state word last
         // (jobs of this wave are numbered 1, 2, ... over both banks; the counter sits in the first group's spare LDS word)
-        const uint32_t wave_seq = (uint32_t)__builtin_amdgcn_readfirstlane(bank_lds[wave_in_block * kGroupsOfWave][0][5]) + 1u;
-        if (w.gl < kSlots) {
-            const int h = w.gl;
-            if (h ? have[1] : have[0]) {
-                const int Rh = h ? pt.R[1] : pt.R[0], Qh = h ? pt.Q[1] : pt.Q[0], sh = h ? pt.shift[1] : pt.shift[0];
-                int l0, c0, k0;
-                L::walk_start(Rh, Qh, L::tile_tB(tB, sh), l0, c0, k0);
-                CoopJob *jb = &jobs[job_base + bank];
-                jb->ws_off = (uint32_t)((const char *)(h ? wsB : wsA) - (const char *)ws_all);
-                jb->R = Rh; jb->Q = Qh; jb->k0 = k0; jb->v0 = h ? v0B : v0A;
-                jb->band_lim = ((kp.band & 0xffff) > 0 && !(h ? pt.full[1] : pt.full[0])) ? (kp.band & 0xffff) - kLinWalkSpan : -1;
-                const uint32_t seg_index = (uint32_t)((group_in_block * kCoopBanks + bank) * kStageWords + (2 * h) * kSeg);
-                constexpr uint32_t kFrontBits = 16u * StageGeom<L::kSlotsPerLane, LANES>::kFront;
-                jb->where = (kFrontBits + (uint32_t)((h ? pt.rp0[1] : pt.rp0[0]) & 15)) |
-                            ((kFrontBits + (uint32_t)((h ? pt.qp0[1] : pt.qp0[0]) & 15)) << 8) |
-                            ((h ? pt.reverse[1] : pt.reverse[0]) ? 1u << 16 : 0u) | (seg_index << 17);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __hip_atomic_store(&jstate[job_base + bank], (wave_seq << 2) | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
+        const uint32_t wave_seq = (uint32_t)__builtin_amdgcn_readfirstlane(bank_lds[wave_in_block * kGroupsOfWave][0][kBankSeq]) + 1u;
+        if (w.gl < kSlots && (w.gl ? have[1] : have[0])) {
+            post_job<L>(&jobs[job_base + bank], w.gl, kp, pt, tB, w.gl ? wsB : wsA, ws_all, w.gl ? v0B : v0A,
+                        (group_in_block * kCoopBanks + bank) * kStageWords);
+            __hip_atomic_store(&jstate[job_base + bank], (wave_seq << 2) | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         wave_sync();
-        if (w.gl == 0) bank_lds[group_in_block][bank][4] = (int)((wave_seq << 2) | 3u);      // what the bank's jobs read when done
-        if ((threadIdx.x & 63) == 0) bank_lds[wave_in_block * kGroupsOfWave][0][5] = (int)wave_seq;
+        if (w.gl == 0) bk[kBankWant] = (int)((wave_seq << 2) | 3u);      // what the bank's jobs read when done
+        if ((threadIdx.x & 63) == 0) bank_lds[wave_in_block * kGroupsOfWave][0][kBankSeq] = (int)wave_seq;
         wave_sync();
         // (walking eagerly -- a wave that has just posted walks at once when 16 / 24 / 32 / 48 jobs of the block are pending, so that
         //  nobody waits for a result later -- takes the waiting out of the stamps, 24 % -> 9 % of a wave's time, and changes
@@ -518,22 +441,10 @@ __global__ __launch_bounds__(kBlockThreads, 3) void extend_coop_kernel(
         GACT_STAMP(t_f);
         GACT_ACC(0, t_a, t_b); GACT_ACC(1, t_b, t_c); GACT_ACC(2, t_c, t_d); GACT_ACC(3, t_d, t_e);
         GACT_ACC(4, t_w0, t_a); GACT_ACC(5, t_e, t_f);
-#ifdef GACT_STAMPS
-        stamp_acc[6] += 1; stamp_acc[7] += (unsigned long long)(T_end - tB + 1);
-#endif
+        GACT_STAMPS_DO(pass_done(T_end - tB + 1));
         bank ^= 1;
     }
-#ifdef GACT_STAMPS
-    if ((threadIdx.x & 63) == 0) {
-        for (int k = 0; k < 8; k++) atomicAdd(&g_stamps[k], stamp_acc[k]);
-        const int wv = blockIdx.x * (kBlockThreads / 64) + wave_in_block;
-        if (wv < 4096) {
-            g_timeline[4 * wv] = tl_start; g_timeline[4 * wv + 1] = tl_empty;
-            g_timeline[4 * wv + 2] = __builtin_amdgcn_s_memrealtime(); g_timeline[4 * wv + 3] = stamp_acc[6];
-            g_wave_cycles[wv] = __builtin_amdgcn_s_memtime() - tl_cyc0;
-        }
-    }
-#endif
+    GACT_STAMPS_DO(finish(blockIdx.x * (kBlockThreads / 64) + wave_in_block));
 }
 
 }  // namespace gact

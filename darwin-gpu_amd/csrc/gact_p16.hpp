@@ -35,10 +35,33 @@ __device__ unsigned long long g_wave_cycles[4096];
 // cooperative launch (gact_coop.hpp): walk batches, their loop trips, lane-trips (a trip with n walking lanes counts n), jobs walked
 __device__ unsigned long long g_coop_counts[4];
 #define GACT_STAMP(var) unsigned long long var = __builtin_amdgcn_s_memtime()
-#define GACT_ACC(slot, t0, t1) stamp_acc[slot] += (t1) - (t0)
+#define GACT_ACC(slot, t0, t1) stamps.acc[slot] += (t1) - (t0)
+#define GACT_STAMPS_BEGIN MainStamps stamps; stamps.begin()
+#define GACT_STAMPS_DO(call) stamps.call
+// what a wave of a main launch (its `stamps`) keeps for the above.  The record and every statement that names it exist in
+// this build only: an empty record with empty members moved the register allocation of the default build (profiles/r16)
+struct MainStamps {
+    unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // [0..5] clocks per phase, [6] passes, [7] their DP steps
+    unsigned long long tl_start = 0, tl_cyc0 = 0, tl_empty = 0;
+    __device__ void begin() { tl_start = __builtin_amdgcn_s_memrealtime(); tl_cyc0 = __builtin_amdgcn_s_memtime(); }
+    __device__ void note_empty() { if (!tl_empty) tl_empty = __builtin_amdgcn_s_memrealtime(); }
+    __device__ void pass_done(int steps) { acc[6] += 1; acc[7] += (unsigned long long)steps; }
+    __device__ void finish(int wv)                             // wv: the wave's index in the launch
+    {
+        if ((threadIdx.x & 63) != 0) return;
+        for (int k = 0; k < 8; k++) atomicAdd(&g_stamps[k], acc[k]);
+        if (wv < 4096) {
+            g_timeline[4 * wv] = tl_start; g_timeline[4 * wv + 1] = tl_empty;
+            g_timeline[4 * wv + 2] = __builtin_amdgcn_s_memrealtime(); g_timeline[4 * wv + 3] = acc[6];
+            g_wave_cycles[wv] = __builtin_amdgcn_s_memtime() - tl_cyc0;
+        }
+    }
+};
 #else
 #define GACT_STAMP(var)
 #define GACT_ACC(slot, t0, t1)
+#define GACT_STAMPS_BEGIN
+#define GACT_STAMPS_DO(call)
 #endif
 
 // the seed launch's linear-gap walks by teams of eight lanes (1) or by one lane per tile (0)
@@ -827,6 +850,30 @@ template <class L, bool TEAM> constexpr int walk_scratch_words()
 }
 
 // ---------------------------------------------------------------------------
+// The control phase of the persistent main kernels, continued from gact_chain.hpp (main_pop, pass_prio): the pieces that
+// need PairTile.  extend_p16_kernel below, extend_roles_kernel and extend_coop_kernel call them.
+
+// Common end and common pointer start over the wave's tiles (align_starts), from each slot's own last step and first
+// pointer step; and what of the pass's PairTile is the same for both slots.
+template <class L>
+__device__ __forceinline__ void pair_starts(const KParams &kp, const bool (&have)[kSlots], const int (&Tend_h)[kSlots],
+                                            const int (&tB_h)[kSlots], uint32_t *lut, PairTile &pt, int &T_end, int &tB)
+{
+    constexpr int LANES = L::kLanes;
+    T_end = wave_max_groups<LANES>(imax(have[0] ? Tend_h[0] : 0, have[1] ? Tend_h[1] : 0));
+    const int reach0 = have[0] ? tB_h[0] + (T_end - Tend_h[0]) : 0x7fffffff;
+    const int reach1 = have[1] ? tB_h[1] + (T_end - Tend_h[1]) : 0x7fffffff;
+    tB = wave_min_groups<LANES>(imin(reach0, reach1));
+    // the walk starts in column Q and stops after `early` query steps (align.cpp:205)
+    pt.col_from = imax(imin(have[0] ? pt.Q[0] : 0x7fff, have[1] ? pt.Q[1] : 0x7fff) - kp.early, 0);
+    pt.band = kp.band;
+    pt.lut = lut;
+    // (a layout whose walker wants H[R][Q] from the pass delays every tile all the way: last row = last step)
+    pt.shift[0] = have[0] ? (L::kEndAligned ? T_end - Tend_h[0] : imax(0, tB - tB_h[0])) : 0;
+    pt.shift[1] = have[1] ? (L::kEndAligned ? T_end - Tend_h[1] : imax(0, tB - tB_h[1])) : 0;
+}
+
+// ---------------------------------------------------------------------------
 // Persistent main kernel: every group carries two candidates (slot A / slot B).
 // RAW: the sets hold bytes other than ACGT and are compared as raw bytes (see dp_pass_p16).
 // TWO_SETS: the launch may go on with a second set of queues (overlapped seeding, ChainQueues::more_flag); a variant of its
@@ -880,16 +927,9 @@ __global__ __launch_bounds__(kBlockThreads, L::kBlocksPerCu) void extend_p16_ker
     if (w.gl < kSlots) { st[w.gl].phase = 2; st[w.gl].cand = -1; }
     wave_sync();
     bool exhausted = false;
-    // longest chains first (ChainQueues) -- except that a launch with a critical lane beside it (cq.leave_longest, gact_chain.hpp)
-    // starts behind the classes that hold the longest `leave_longest` chains of its own set and comes back to them last:
-    // bucket = (bucket_first + my_bucket) mod kBuckets
+    // the group pops class (bucket_first + my_bucket) mod kBuckets (main_pop)
     int my_bucket = 0;
-    int bucket_first = 0;
-    if (cq.leave_longest > 0) {
-        int acc = 0;
-        while (bucket_first < kBuckets && (acc += cq.bucket_count[bucket_first]) <= cq.leave_longest) bucket_first++;
-        if (bucket_first >= kBuckets) bucket_first = 0;
-    }
+    const int bucket_first = main_first_bucket(cq);
     // the set of queues this group pops from: the launch's own, later (overlapped seeding) the second one.  (One flag per
     // lane, the pointers are picked where they are used: the DP loop owns the register file)
     bool second_set = false;
@@ -898,12 +938,7 @@ __global__ __launch_bounds__(kBlockThreads, L::kBlocksPerCu) void extend_p16_ker
     // (the ranking against the longest chain running: every kRankEvery-th tile, the waves of a launch taking turns; the first tile always)
     int rank_turn = 0, rank_cached = 0;
     __builtin_amdgcn_s_setprio(3);
-#ifdef GACT_STAMPS
-    unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long tl_start = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long tl_cyc0 = __builtin_amdgcn_s_memtime();
-    unsigned long long tl_empty = 0;
-#endif
+    GACT_STAMPS_BEGIN;
 
     for (;;) {
         GACT_STAMP(t_a);
@@ -913,6 +948,7 @@ __global__ __launch_bounds__(kBlockThreads, L::kBlocksPerCu) void extend_p16_ker
         bool have[kSlots];
         int Tend_h[kSlots], tB_h[kSlots];
         int longest = 0;             // bases the longest chain of this group still has to cover
+        // (the pick below, to the end of the loop over h: one of three copies, the others in extend_roles_kernel (gact_roles.hpp) and extend_coop_kernel (gact_coop.hpp))
 #pragma unroll
         for (int h = 0; h < kSlots; h++) {
             ChainState s = st[h];
@@ -921,43 +957,12 @@ __global__ __launch_bounds__(kBlockThreads, L::kBlocksPerCu) void extend_p16_ker
             for (int guard = 0; guard < 3 && !pk.have; guard++) {
                 if (s.phase == 2) {
                     if (exhausted) break;
-                    int cand = -1;
-                    for (;;) {
-                        const int *q_count = (TWO_SETS && second_set) ? cq.more_count : cq.bucket_count;
-                        int *q_pop = (TWO_SETS && second_set) ? cq.more_pop : cq.bucket_pop;
-                        const int *q_live = (TWO_SETS && second_set) ? cq.more_live : cq.live;
-                        while (my_bucket < kBuckets) {
-                            // look before popping: an atomic on a class that is empty or drained is one of ~12,000
-                            // (every group comes by) serialised on one address -- 4 ms of a 55 ms launch with 32 empty classes
-                            const int bkt = bucket_first + my_bucket - (bucket_first + my_bucket >= kBuckets ? kBuckets : 0);
-                            const int cnt = q_count[bkt];
-                            int idx = cnt;
-                            if (w.gl == 0 && __hip_atomic_load(&q_pop[bkt], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < cnt)
-                                idx = atomicAdd(&q_pop[bkt], 1);
-                            idx = __shfl(idx, 0, LANES);
-                            if (idx < cnt) {
-                                cand = q_live[(size_t)bkt * cq.live_stride + idx];
-                                break;
-                            }
-                            my_bucket++;
-                        }
-                        if (cand >= 0 || second_set || one_set) break;
-                        // this launch's own queues are empty.  Overlapped seeding: a second set is being filled by a seed
-                        // launch on another stream; *more_flag is written in stream order BEHIND that launch, so once it
-                        // reads non-zero the launch has ended and its writes are in memory -- an acquire at agent scope
-                        // (this XCD's caches drop what they hold of them) and the wave goes on with that set
-                        if (__hip_atomic_load(cq.more_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) break;
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                        second_set = true;
-                        my_bucket = 0;
-                    }
+                    const int cand = main_pop<TWO_SETS, LANES>(cq, w.gl == 0, bucket_first, my_bucket, second_set);
                     if (cand < 0) {
                         // (no second set yet: not exhausted, the slot stays empty for this pass)
                         if (second_set || one_set) {
                             exhausted = true;
-#ifdef GACT_STAMPS
-                            if (!tl_empty) tl_empty = __builtin_amdgcn_s_memrealtime();
-#endif
+                            GACT_STAMPS_DO(note_empty());
                         }
                         break;
                     }
@@ -980,6 +985,7 @@ __global__ __launch_bounds__(kBlockThreads, L::kBlocksPerCu) void extend_p16_ker
         if (!__any(any_here)) {
             if (__all(exhausted && st[0].phase == 2 && st[1].phase == 2)) break;
             if (!second_set && !one_set) {
+                // (one of three copies, the others in extend_roles_kernel (gact_roles.hpp) and extend_coop_kernel (gact_coop.hpp))
                 // a wave with nothing to do while the second set of queues is not open yet: wait a little, but never
                 // for ever -- the launch that opens it may be waiting for this wave's registers (several engine slots
                 // at work); what is left over is taken by the main launch queued behind that seed launch
@@ -988,18 +994,8 @@ __global__ __launch_bounds__(kBlockThreads, L::kBlocksPerCu) void extend_p16_ker
             }
             continue;
         }
-        // common end / common pointer start over the wave's 8 tiles (align_starts)
-        const int T_end = wave_max_groups<LANES>(imax(have[0] ? Tend_h[0] : 0, have[1] ? Tend_h[1] : 0));
-        const int reach0 = have[0] ? tB_h[0] + (T_end - Tend_h[0]) : 0x7fffffff;
-        const int reach1 = have[1] ? tB_h[1] + (T_end - Tend_h[1]) : 0x7fffffff;
-        const int tB = wave_min_groups<LANES>(imin(reach0, reach1));
-        // (a layout whose walker wants H[R][Q] from the pass delays every tile all the way: last row = last step)
-        // the walk starts in column Q and stops after `early` query steps (align.cpp:205)
-        pt.col_from = imax(imin(have[0] ? pt.Q[0] : 0x7fff, have[1] ? pt.Q[1] : 0x7fff) - kp.early, 0);
-        pt.band = kp.band;
-        pt.lut = lin_lut;
-        pt.shift[0] = have[0] ? (L::kEndAligned ? T_end - Tend_h[0] : imax(0, tB - tB_h[0])) : 0;
-        pt.shift[1] = have[1] ? (L::kEndAligned ? T_end - Tend_h[1] : imax(0, tB - tB_h[1])) : 0;
+        int T_end, tB;
+        pair_starts<L>(kp, have, Tend_h, tB_h, lin_lut, pt, T_end, tB);
 
         GACT_STAMP(t_b);
         uint32_t qb[L::kSlotsPerLane];
@@ -1009,19 +1005,9 @@ __global__ __launch_bounds__(kBlockThreads, L::kBlocksPerCu) void extend_p16_ker
 
         // the DP pass is throughput work; everything else in this loop is a short serial
         // chain (traceback, chain bookkeeping, loads) that must not queue behind other
-        // waves' DP instructions: run it at raised issue priority
-        // ... and among the DP passes, the waves that carry the longest chains go first: when there are
-        // fewer chains than tile slots the launch lasts as long as its longest chain
+        // waves' DP instructions: run it at raised issue priority (pass_prio: the pass's own)
         const int wave_longest = wave_max_groups<LANES>(longest);
-        const int ref_longest = ranked_longest(cq, kp, wave_longest, rank_turn, rank_cached);
-        // ranking mode (prio_bases[0] == 0): prio_bases[1] = thresholds in sixteenths of the longest, hi << 8 | mid
-        const bool rank_hi = kp.prio_bases[0] == 0 ? 16 * wave_longest > (kp.prio_bases[1] >> 8) * ref_longest
-                                                   : wave_longest > kp.prio_bases[1];
-        const bool rank_mid = kp.prio_bases[0] == 0 ? 16 * wave_longest > (kp.prio_bases[1] & 255) * ref_longest
-                                                    : wave_longest > kp.prio_bases[0];
-        if (rank_hi) __builtin_amdgcn_s_setprio(2);
-        else if (rank_mid) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
+        pass_prio(cq, kp, wave_longest, rank_turn, rank_cached);
         const uint32_t fin = L::template pass<RAW>(kc, w.gl, ref16_lane, qb, T_end, tB, wsA, wsB, pt);
         __builtin_amdgcn_s_setprio(3);
         // FMT 3 walkers start from H[R][Q]: held by the lane of column Q when the pass ends
@@ -1075,7 +1061,7 @@ __global__ __launch_bounds__(kBlockThreads, L::kBlocksPerCu) void extend_p16_ker
             }
         }
         GACT_STAMP(t_f);
-        // ---- consume (gact.cpp:111-133 / :172-194); non-first tiles only
+        // ---- consume (gact.cpp:111-133 / :172-194); non-first tiles only.  (The bank form of this loop: extend_roles_kernel (gact_roles.hpp) and extend_coop_kernel (gact_coop.hpp))
 #pragma unroll
         for (int h = 0; h < kSlots; h++) {
             if (have[h]) {
@@ -1086,10 +1072,7 @@ __global__ __launch_bounds__(kBlockThreads, L::kBlocksPerCu) void extend_p16_ker
                     s.full = 1;
                     if (w.gl == 0) atomicAdd(cq.band_redos, 1);
                 } else {
-                    s.full = 0;
-                    s.n_tiles++;
-                    s.cells += (int64_t)pt.R[h] * pt.Q[h];
-                    chain_advance<LANES>(s, false, wk, ref_steps, query_steps, nst, h * kWalkLanes);
+                    main_count_advance<LANES>(s, pt.R[h], pt.Q[h], h * kWalkLanes, wk, ref_steps, query_steps, nst);
                 }
                 wave_sync();
                 if (w.gl == 0) st[h] = s;
@@ -1099,21 +1082,9 @@ __global__ __launch_bounds__(kBlockThreads, L::kBlocksPerCu) void extend_p16_ker
         GACT_STAMP(t_g);
         GACT_ACC(0, t_a, t_b); GACT_ACC(1, t_b, t_c); GACT_ACC(2, t_c, t_d); GACT_ACC(3, t_d, t_e);
         GACT_ACC(4, t_e, t_f); GACT_ACC(5, t_f, t_g);
-#ifdef GACT_STAMPS
-        stamp_acc[6] += 1; stamp_acc[7] += (unsigned long long)(T_end - tB + 1);
-#endif
+        GACT_STAMPS_DO(pass_done(T_end - tB + 1));
     }
-#ifdef GACT_STAMPS
-    if ((threadIdx.x & 63) == 0) {
-        for (int k = 0; k < 8; k++) atomicAdd(&g_stamps[k], stamp_acc[k]);
-        const int wv = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-        if (wv < 4096) {
-            g_timeline[4 * wv] = tl_start; g_timeline[4 * wv + 1] = tl_empty;
-            g_timeline[4 * wv + 2] = __builtin_amdgcn_s_memrealtime(); g_timeline[4 * wv + 3] = stamp_acc[6];
-            g_wave_cycles[wv] = __builtin_amdgcn_s_memtime() - tl_cyc0;
-        }
-    }
-#endif
+    GACT_STAMPS_DO(finish((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
 }
 
 // the linear-gap pass (gact_lin.hpp), uniform layout; LIN seed launch below
