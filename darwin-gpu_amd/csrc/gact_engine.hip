@@ -362,15 +362,25 @@ struct Slot {
 
 // gact_hip_pileup_* (gact_pileup.hpp): the open window of GACT_SET_REF and its counts, one allocation of the engine's
 struct Pileup {
-    PassScratch<gact_pileup_stats> scratch;       // p: counts (32 per position) | consensus (1 per position) | read table | alignments per read | state;
-                                                  // the events around finish's own work; stats under mu: adds come from several threads
+    PassScratch<gact_pileup_stats> scratch;       // p: counts (32 per position) | slots (16 ins_slots per position) | consensus (1 per position) |
+                                                  // read table | alignments per read | state | corrected reads' table | read_at;
+                                                  // the events around finish's and corrected's own work; stats under mu: adds come from several threads
     std::mutex mu;
     bool open = false;
-    int32_t read_first = 0, n_reads = 0;
+    int32_t read_first = 0, n_reads = 0, ins_slots = 0;
     int64_t base = 0, positions = 0;      // the window's first base in the set's concatenation, its bases
-    size_t at_cons = 0, at_reads = 0, at_aln = 0, at_state = 0;       // where the parts of p begin
+    size_t at_ins = 0, at_cons = 0, at_reads = 0, at_aln = 0, at_state = 0, at_corrected = 0, at_read_at = 0;      // where the parts of p begin
     int64_t ref_epoch = -1;               // gact_hip_engine::ref_epoch at begin: the window describes that upload of GACT_SET_REF
-    void release() { scratch.release(); open = false; }
+    gact_pileup_ins_stats ins_stats{};    // (under mu)
+    uint8_t *seq = nullptr;               // the corrected reads' bytes of the last gact_hip_pileup_corrected that had room for them
+    size_t seq_cap = 0;
+    void release()
+    {
+        scratch.release();
+        if (seq) (void)hipFree(seq);
+        seq = nullptr; seq_cap = 0;
+        open = false;
+    }
 };
 
 // device-side D-SOFT filter (dsoft_device.hpp)

@@ -1,5 +1,5 @@
 // gact_pileup.hpp -- per-base pileup and consensus of the reads of GACT_SET_REF from the overlaps' alignments
-// (gact_hip_pileup_begin / _add / _finish).
+// (gact_hip_pileup_begin / _add / _finish), the inserted bases and the corrected reads (gact_hip_pileup_begin_ins / _corrected).
 //
 // What a consumer of an overlapper's alignments does with them: stack every overlap's alignment on its target read, count at
 // every position what the other reads say, take the majority (daccord, the polishing rounds behind miniasm).  The path run
@@ -18,27 +18,43 @@
 //                            A candidate whose record was not emitted, or that has no columns, adds nothing.  Every index is
 //                            checked before it is used: a read outside the window or a span outside its reads sets the flag word
 //                            and adds nothing.
+//                            pileup_kernel<true> (a window with ins_slots = K > 0) also keeps the inserted bases: an 'I' lane has
+//                            r and q already, and its index j inside its run is the length of the stretch of set bits directly
+//                            below it in the ballot of 'I' lanes, plus a wave-uniform carry (the open run's length at the end of
+//                            the step before) when that stretch reaches lane 0; j < K, r < len, a base of kind A C G T: one
+//                            more add, to ins[r][j].n[kind].  The lanes with j == K are the runs longer than K, counted per wave.
+//                            pileup_kernel<false> is the kernel as it was: a window without slots runs that.
 //   pileup_consensus_kernel  one thread per position: the consensus byte
 //   pileup_reads_kernel      one wave per read, grid-stride, 64 positions per step: called / changed / deleted / ins_flagged from
 //                            the popcounts of four ballots, the highest depth from a per-lane running max reduced once
-// No LDS, no look-back, no spinning.  All results are integers and the same on every call.
+//   pileup_spell_kernel      the corrected reads, one wave per read, grid-stride, 64 positions per step.  A lane calls its
+//                            position's slots (pileup_slots) and reads its consensus byte; what a position gives is at most
+//                            K + 1 bytes.  <false>: the read's length, inserted bases, sites, deleted and changed positions from
+//                            the popcounts of the ballots "slot j emitted" and "byte kept".  <true>, behind the scan: a position's
+//                            offset is the read's start, the carry of the steps before and the same ballots' popcounts under
+//                            the lane mask; it writes its bytes there.
+//   pileup_scan_kernel       one block: the reads' lengths -> their exclusive 64-bit scan (the shape of select_scan_kernel: two
+//                            levels, no block waits for another)
+// No LDS but the scan's, no look-back, no spinning.  All results are integers and the same on every call.
 //
-// The counts belong to the engine (Pileup in gact_engine.hip): 32 bytes per position of the open window, 13.4 GB for 418 Mb of
-// reads -- hence the window.
+// The counts belong to the engine (Pileup in gact_engine.hip): 32 + 16 K bytes per position of the open window, 13.4 GB for
+// 418 Mb of reads at K = 0 -- hence the window.
 //
 // Included by gact_engine.hip behind every other kernel and behind the engine's definitions, inside its extern "C" block, as
 // gact_cover.hpp is.
 #pragma once
 
+extern "C++" {                  // (templates: not in gact_engine.hip's extern "C")
 namespace gact {
 
 constexpr int kPileupBlock = 256;                 // four waves
 constexpr int kPileupBadRead = 1, kPileupBadSpan = 2;       // bits of the flag word
 
-struct PileupState {                              // 32 bytes behind the counts, zeroed by begin, copied back by every add
+struct PileupState {                              // 48 bytes behind the counts, zeroed by begin, copied back by every add
     int flag, pad;
     unsigned long long alignments, columns;       // counted since begin
-    unsigned long long reserved;
+    unsigned long long runs_truncated;            // runs of 'I' longer than the window's ins_slots
+    unsigned long long slot_adds, reserved;       // adds to the slots
 };
 
 struct PileupWin {
@@ -47,6 +63,8 @@ struct PileupWin {
     PileupState *state;
     int read_first, n_reads;
     long long base;                               // the window's first base in the ref set's concatenation
+    uint32_t *ins;                                // [positions][ins_slots][4]; pileup_kernel<true> only
+    int ins_slots;
 };
 
 // A C G T -> 0 1 2 3 in either case, anything else -> 4
@@ -61,6 +79,7 @@ __device__ __forceinline__ int pileup_kind(uint32_t b)
     }
 }
 
+template <bool kSlots>
 __global__ void __launch_bounds__(kPileupBlock)
 pileup_kernel(const uint8_t *__restrict__ cols, const int64_t *__restrict__ col_off, const int32_t *__restrict__ n_cols,
               const gact_candidate *__restrict__ cands, const gact_overlap *__restrict__ records, int n, SeqSetDev refs,
@@ -104,6 +123,9 @@ pileup_kernel(const uint8_t *__restrict__ cols, const int64_t *__restrict__ col_
         const uint8_t *qraw = qs.raw + q_off;
         // ---- the columns
         uint32_t last = 0;                                      // the code of the step before's last column (none: no 'I')
+        uint32_t *slots = kSlots ? win.ins + (size_t)(r_off - win.base) * win.ins_slots * 4 : nullptr;
+        int open_run = 0, n_slot = 0, n_long = 0;               // (kSlots: the open run's length so far; this alignment's adds
+                                                                //  to slots and runs longer than ins_slots; wave-uniform)
         for (int c0 = 0; c0 < len; c0 += 64) {
             const int t = c0 + lane;
             const bool in = t < len;
@@ -122,6 +144,17 @@ pileup_kernel(const uint8_t *__restrict__ cols, const int64_t *__restrict__ col_
                 const long long rr = r < r_len - 1 ? r : r_len - 1;
                 atomicAdd(mine + (size_t)rr * 8 + GACT_PILEUP_INS, 1u);
             }
+            if constexpr (kSlots) {                             // the inserted base: column j of its run, in front of r
+                const bool is_i = in && !on_r;
+                const uint64_t m_i = __ballot(is_i);
+                const uint64_t gaps = ~m_i & below_me;          // the lanes below mine that are no 'I'
+                const int j = gaps ? lane - (64 - __clzll(gaps)) : lane + open_run;
+                const int kind = is_i && j < win.ins_slots && r < r_len ? pileup_kind(qraw[q]) : GACT_PILEUP_OTHER;
+                if (kind < GACT_PILEUP_OTHER) atomicAdd(slots + ((size_t)r * win.ins_slots + j) * 4 + kind, 1u);
+                n_slot += __popcll(__ballot(kind < GACT_PILEUP_OTHER));
+                n_long += __popcll(__ballot(is_i && j == win.ins_slots));
+                open_run = ~m_i ? __clzll(~m_i) : open_run + 64;                // the 'I' lanes at the step's top
+            }
             r_base += __popcll(m_r);
             q_base += __popcll(m_q);
             last = __shfl(code, 63);
@@ -130,6 +163,8 @@ pileup_kernel(const uint8_t *__restrict__ cols, const int64_t *__restrict__ col_
             atomicAdd(&win.n_aln[rid - win.read_first], 1);
             atomicAdd(&win.state->alignments, 1ull);
             atomicAdd(&win.state->columns, (unsigned long long)len);
+            if (kSlots && n_slot) atomicAdd(&win.state->slot_adds, (unsigned long long)n_slot);
+            if (kSlots && n_long) atomicAdd(&win.state->runs_truncated, (unsigned long long)n_long);
         }
     }
 }
@@ -202,22 +237,133 @@ pileup_reads_kernel(const uint32_t *__restrict__ counts, const uint8_t *__restri
     }
 }
 
+// The slot call of position p with K slots: how many are emitted -- the leading ones whose four counts together are more than
+// half the depth, at a called position -- and their bytes, slot j's in bits [8 j, 8 j + 8)
+__device__ __forceinline__ int pileup_slots(const uint32_t *__restrict__ ins, size_t p, int K, uint32_t depth, uint32_t min_depth,
+                                            uint32_t &bytes)
+{
+    bytes = 0;
+    if (depth < min_depth) return 0;
+    int e = 0;
+    for (; e < K; e++) {
+        const uint4 n = ((const uint4 *)ins)[p * (size_t)K + e];
+        if (2ull * ((unsigned long long)n.x + n.y + n.z + n.w) <= depth) break;
+        uint32_t best = n.x, b = 'A';                           // the first of equal ones in the order A C G T
+        if (n.y > best) { best = n.y; b = 'C'; }
+        if (n.z > best) { best = n.z; b = 'G'; }
+        if (n.w > best) { best = n.w; b = 'T'; }
+        bytes |= b << (8 * e);
+    }
+    return e;
+}
+
+// kWrite false: read_at[read] = the corrected read's length, reads[read] its record.  kWrite true, behind pileup_scan_kernel:
+// the read's bytes at seq + read_at[read]; a position that would write at or beyond seq_cap writes nothing.
+template <bool kWrite>
+__global__ void __launch_bounds__(kPileupBlock)
+pileup_spell_kernel(const uint32_t *__restrict__ counts, const uint32_t *__restrict__ ins, int K, const uint8_t *__restrict__ own,
+                    const uint8_t *__restrict__ cons, const int64_t *__restrict__ offsets, long long base, int n_reads,
+                    uint32_t min_depth, long long *__restrict__ read_at, gact_read_corrected *__restrict__ reads,
+                    uint8_t *__restrict__ seq, long long seq_cap)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * (kPileupBlock / 64) + (threadIdx.x >> 6), n_waves = gridDim.x * (kPileupBlock / 64);
+    const uint64_t below_me = (1ull << lane) - 1;
+    for (int read = wave; read < n_reads; read += n_waves) {    // (offsets: the window's first read's onwards)
+        const long long first = offsets[read] - base, len = offsets[read + 1] - offsets[read];
+        long long at = kWrite ? read_at[read] : 0;              // where the step's first byte goes (kWrite false: from 0)
+        int inserted = 0, sites = 0, deleted = 0, changed = 0;
+        for (long long c0 = 0; c0 < len; c0 += 64) {
+            const long long p = first + c0 + lane;
+            const bool valid = c0 + lane < len;
+            uint32_t depth = 0, mine = 0, made = '-', bytes = 0;
+            int e = 0;                                          // emitted slots of my position
+            if (valid) {
+                depth = counts[(size_t)p * 8 + GACT_PILEUP_DEPTH];
+                mine = own[p];
+                made = cons[p];
+                e = pileup_slots(ins, (size_t)p, K, depth, min_depth, bytes);
+            }
+            const bool keep = valid && made != '-';
+            const uint64_t m_keep = __ballot(keep);
+            int step = __popcll(m_keep), before = __popcll(m_keep & below_me);  // bytes of the step, of the lanes below mine
+            for (int j = 0; j < K; j++) {                       // (wave-uniform)
+                const uint64_t m = __ballot(e > j);
+                step += __popcll(m);
+                before += __popcll(m & below_me);
+                if (j == 0) sites += __popcll(m);
+            }
+            if (kWrite) {
+                const long long o = at + before;
+                if (valid && o >= 0 && o + e + (keep ? 1 : 0) <= seq_cap) {
+                    for (int j = 0; j < e; j++) seq[o + j] = (uint8_t)(bytes >> (8 * j));
+                    if (keep) seq[o + e] = (uint8_t)made;
+                }
+            } else {
+                inserted += step - __popcll(m_keep);
+                deleted += __popcll(__ballot(valid && made == '-'));
+                changed += __popcll(__ballot(keep && depth >= min_depth && (made | 0x20u) != (mine | 0x20u)));
+            }
+            at += step;
+        }
+        if (!kWrite && lane == 0) {
+            read_at[read] = at;
+            int4 *r = (int4 *)&reads[read];
+            r[0] = make_int4((int)at, inserted, sites, deleted);
+            r[1] = make_int4(changed, 0, 0, 0);
+        }
+    }
+}
+
+// one block: read_at[0, n_reads) (the lengths) -> their exclusive scan, in place; read_at[n_reads] = all bases,
+// read_at[n_reads + 1] = the inserted ones
+__global__ void __launch_bounds__(kPileupBlock)
+pileup_scan_kernel(int n_reads, long long *__restrict__ read_at, const gact_read_corrected *__restrict__ reads)
+{
+    __shared__ long long s_len[kPileupBlock], s_ins[kPileupBlock];
+    long long carry = 0, carry_ins = 0;
+    for (int base = 0; base < n_reads; base += kPileupBlock) {
+        const int k = base + (int)threadIdx.x;
+        const long long own = k < n_reads ? read_at[k] : 0;
+        s_len[threadIdx.x] = own;
+        s_ins[threadIdx.x] = k < n_reads ? reads[k].inserted : 0;
+        __syncthreads();
+        for (int d = 1; d < kPileupBlock; d <<= 1) {
+            const long long a = (int)threadIdx.x >= d ? s_len[threadIdx.x - d] : 0;
+            const long long b = (int)threadIdx.x >= d ? s_ins[threadIdx.x - d] : 0;
+            __syncthreads();
+            s_len[threadIdx.x] += a;
+            s_ins[threadIdx.x] += b;
+            __syncthreads();
+        }
+        if (k < n_reads) read_at[k] = carry + s_len[threadIdx.x] - own;
+        carry += s_len[kPileupBlock - 1];
+        carry_ins += s_ins[kPileupBlock - 1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { read_at[n_reads] = carry; read_at[n_reads + 1] = carry_ins; }
+}
+
 }  // namespace gact
+}  // extern "C++"
 
 static int pileup_refuse_big_tiles(gact_hip_engine *e, const char *who)
 {
     return refuse_big_tiles(e, who, "the pileup counts the path run's columns, which come from");
 }
 
-// One allocation: counts (32 positions) | consensus (positions) | read table (32 n_reads) | alignments per read (4 n_reads) |
-// state (32).  Everything but the consensus is zeroed here.
-int gact_hip_pileup_begin(gact_hip_engine *e, int32_t read_first, int32_t n_reads)
+// One allocation: counts (32 positions) | slots (16 ins_slots positions) | consensus (positions) | read table (32 n_reads) |
+// alignments per read (4 n_reads) | state (48) | corrected reads' table (32 n_reads) | read_at (8 (n_reads + 2)).  Everything but
+// the consensus is zeroed here.
+int gact_hip_pileup_begin_ins(gact_hip_engine *e, int32_t read_first, int32_t n_reads, int32_t ins_slots)
 {
     if (!e) return fail(GACT_HIP_EINVAL, "engine is NULL");
     Pileup &pl = e->pileup;
     pl.open = false;                          // (a begin that is refused leaves no window open, an earlier one's neither)
     int rc = pileup_refuse_big_tiles(e, "pileup_begin");
     if (rc) return rc;
+    if (ins_slots < 0 || ins_slots > GACT_PILEUP_MAX_INS_SLOTS)
+        return fail(GACT_HIP_EINVAL, "pileup_begin: ins_slots = %d outside [0, %d]", ins_slots, GACT_PILEUP_MAX_INS_SLOTS);
     const SeqSet &rs = e->sets[GACT_SET_REF];
     if (rs.n == 0 || !rs.d_raw) return fail(GACT_HIP_EINVAL, "pileup_begin: GACT_SET_REF not uploaded");
     if (read_first < 0 || n_reads < 0 || (int64_t)read_first + n_reads > rs.n)
@@ -228,11 +374,14 @@ int gact_hip_pileup_begin(gact_hip_engine *e, int32_t read_first, int32_t n_read
     if ((rc = ps.timer.create("pileup_begin"))) return rc;
     const int64_t base = rs.h_offsets[(size_t)read_first];
     const int64_t positions = rs.h_offsets[(size_t)read_first + (size_t)n_reads] - base;
-    const size_t at_cons = (size_t)positions * sizeof(gact_pileup_col);
+    const size_t at_ins = (size_t)positions * sizeof(gact_pileup_col);
+    const size_t at_cons = at_ins + (size_t)positions * (size_t)ins_slots * sizeof(gact_pileup_ins);
     const size_t at_reads = up16(at_cons + (size_t)positions);
     const size_t at_aln = at_reads + (size_t)n_reads * sizeof(gact_read_pileup);
     const size_t at_state = up16(at_aln + (size_t)n_reads * sizeof(int32_t));
-    const size_t bytes = at_state + sizeof(gact::PileupState);
+    const size_t at_corrected = at_state + sizeof(gact::PileupState);
+    const size_t at_read_at = at_corrected + (size_t)n_reads * sizeof(gact_read_corrected);
+    const size_t bytes = at_read_at + ((size_t)n_reads + 2) * sizeof(int64_t);
     if (ps.reserve(bytes))
         return fail(GACT_HIP_ENOMEM, "pileup_begin: device allocation failed (%d reads, %lld positions, %zu bytes)", n_reads,
                     (long long)positions, bytes);
@@ -240,8 +389,9 @@ int gact_hip_pileup_begin(gact_hip_engine *e, int32_t read_first, int32_t n_read
     if (at_cons) HIP_TRY(hipMemsetAsync(ps.p, 0, at_cons, stream));
     HIP_TRY(hipMemsetAsync(ps.p + at_reads, 0, bytes - at_reads, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    pl.at_cons = at_cons; pl.at_reads = at_reads; pl.at_aln = at_aln; pl.at_state = at_state;
-    pl.read_first = read_first; pl.n_reads = n_reads;
+    pl.at_ins = at_ins; pl.at_cons = at_cons; pl.at_reads = at_reads; pl.at_aln = at_aln; pl.at_state = at_state;
+    pl.at_corrected = at_corrected; pl.at_read_at = at_read_at;
+    pl.read_first = read_first; pl.n_reads = n_reads; pl.ins_slots = ins_slots;
     pl.base = base; pl.positions = positions;
     pl.ref_epoch = e->ref_epoch;
     {
@@ -249,9 +399,17 @@ int gact_hip_pileup_begin(gact_hip_engine *e, int32_t read_first, int32_t n_read
         ps.stats = gact_pileup_stats{};
         ps.stats.positions = positions;
         ps.stats.scratch_bytes = (int64_t)ps.bytes;
+        pl.ins_stats = gact_pileup_ins_stats{};
+        pl.ins_stats.ins_slots = ins_slots;
+        pl.ins_stats.table_bytes = (int64_t)(at_cons - at_ins);
     }
     pl.open = true;
     return 0;
+}
+
+int gact_hip_pileup_begin(gact_hip_engine *e, int32_t read_first, int32_t n_reads)
+{
+    return gact_hip_pileup_begin_ins(e, read_first, n_reads, 0);
 }
 
 static int pileup_window(gact_hip_engine *e, const char *who)
@@ -295,6 +453,9 @@ int gact_hip_pileup_add(gact_hip_engine *e, int slot, int32_t n_sel, const int32
     win.state = (gact::PileupState *)(pl.scratch.p + pl.at_state);
     win.read_first = pl.read_first; win.n_reads = pl.n_reads;
     win.base = pl.base;
+    win.ins = (uint32_t *)(pl.scratch.p + pl.at_ins);
+    win.ins_slots = pl.ins_slots;
+    const auto kernel = pl.ins_slots ? gact::pileup_kernel<true> : gact::pileup_kernel<false>;
     // Every chunk's arrays at their largest before the first launch: a DevBuf that grows frees its old memory, and chunk i's
     // kernels, which the host does not wait for, still read it while chunk i + 1 is being queued.
     {
@@ -327,7 +488,7 @@ int gact_hip_pileup_add(gact_hip_engine *e, int slot, int32_t n_sel, const int32
             if (crc) return crc;
             const int32_t n = end - first;
             const int blocks = std::max(1, std::min((n + 3) / 4, 4096));
-            hipLaunchKernelGGL(gact::pileup_kernel, dim3(blocks), dim3(gact::kPileupBlock), 0, sl.stream, pb.cols.p, pb.col_off.p,
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(gact::kPileupBlock), 0, sl.stream, pb.cols.p, pb.col_off.p,
                                pb.n_cols.p, pb.cands.p, pb.records.p, n, sn.d_rs, sn.d_qf, sn.d_qr, win);
             HIP_TRY(hipGetLastError());
             first = end;
@@ -351,6 +512,8 @@ int gact_hip_pileup_add(gact_hip_engine *e, int slot, int32_t n_sel, const int32
         ts.chunks += chunks;
         ts.alignments = std::max(ts.alignments, (int64_t)st.alignments);       // (counted since begin, by every slot's adds)
         ts.columns = std::max(ts.columns, (int64_t)st.columns);
+        pl.ins_stats.slot_adds = std::max(pl.ins_stats.slot_adds, (int64_t)st.slot_adds);
+        pl.ins_stats.runs_truncated = std::max(pl.ins_stats.runs_truncated, (int64_t)st.runs_truncated);
     }
     if (st.flag) {
         // reported once: the flag word is cleared, so that later adds (of other slots too) answer for themselves.  The other
@@ -360,6 +523,19 @@ int gact_hip_pileup_add(gact_hip_engine *e, int slot, int32_t n_sel, const int32
         return fail(GACT_HIP_ERANGE, "pileup_add: an alignment lies outside the window or outside its two reads (flag %d); it was "
                                      "left out, the add's other alignments are counted", st.flag);
     }
+    return 0;
+}
+
+// the consensus bytes of the open window for min_depth, on `stream`; full: the blocks that fill the device
+static int pileup_launch_consensus(gact_hip_engine *e, hipStream_t stream, int32_t min_depth, size_t full)
+{
+    Pileup &pl = e->pileup;
+    if (pl.positions <= 0) return 0;
+    const size_t want = ((size_t)pl.positions + gact::kPileupBlock - 1) / gact::kPileupBlock;
+    hipLaunchKernelGGL(gact::pileup_consensus_kernel, dim3((unsigned)std::min(want, full * 4)), dim3(gact::kPileupBlock), 0, stream,
+                       (const uint32_t *)pl.scratch.p, e->sets[GACT_SET_REF].d_raw + pl.base, (long long)pl.positions,
+                       (uint32_t)min_depth, pl.scratch.p + pl.at_cons);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -380,12 +556,7 @@ int gact_hip_pileup_finish(gact_hip_engine *e, int32_t min_depth, gact_pileup_co
     const uint8_t *own = rs.d_raw + pl.base;
     const size_t full = (size_t)std::max(1, e->prop.multiProcessorCount) * 8;              // eight waves on every SIMD
     if ((rc = ps.timer.start(stream, "pileup_finish"))) return rc;
-    if (pl.positions > 0) {
-        const size_t want = ((size_t)pl.positions + gact::kPileupBlock - 1) / gact::kPileupBlock;
-        hipLaunchKernelGGL(gact::pileup_consensus_kernel, dim3((unsigned)std::min(want, full * 4)), dim3(gact::kPileupBlock), 0, stream,
-                           d_counts, own, (long long)pl.positions, (uint32_t)min_depth, d_cons);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = pileup_launch_consensus(e, stream, min_depth, full))) return rc;
     if (pl.n_reads > 0) {
         const size_t want = ((size_t)pl.n_reads + gact::kPileupBlock / 64 - 1) / (gact::kPileupBlock / 64);
         hipLaunchKernelGGL(gact::pileup_reads_kernel, dim3((unsigned)std::min(want, full)), dim3(gact::kPileupBlock), 0, stream, d_counts,
@@ -402,6 +573,95 @@ int gact_hip_pileup_finish(gact_hip_engine *e, int32_t min_depth, gact_pileup_co
     if ((rc = ps.timer.stop(stream, &ms))) return rc;
     std::lock_guard<std::mutex> lk(pl.mu);
     ps.stats.device_ms += ms;
+    return 0;
+}
+
+// The consensus, then pileup_spell_kernel<false> (lengths and the table), pileup_scan_kernel (read_at and the two totals, which
+// the host waits for: they size the bytes), then, where the caller has room, pileup_spell_kernel<true> into pl.seq.
+int gact_hip_pileup_corrected(gact_hip_engine *e, int32_t min_depth, gact_pileup_ins *ins, gact_read_corrected *reads,
+                              int64_t *read_at, uint8_t *seq, int64_t seq_cap, int64_t *seq_len)
+{
+    if (!e) return fail(GACT_HIP_EINVAL, "engine is NULL");
+    if (seq_len) *seq_len = 0;
+    if (min_depth < 1) return fail(GACT_HIP_EINVAL, "pileup_corrected: min_depth = %d, at least 1", min_depth);
+    if (seq_cap < 0) return fail(GACT_HIP_EINVAL, "pileup_corrected: seq_cap = %lld", (long long)seq_cap);
+    int rc = pileup_window(e, "pileup_corrected");
+    if (rc) return rc;
+    Pileup &pl = e->pileup;
+    if (ins && pl.ins_slots == 0)
+        return fail(GACT_HIP_EINVAL, "pileup_corrected: the window was opened without slots (gact_hip_pileup_begin_ins), there is no table");
+    if ((rc = set_device(e))) return rc;
+    const SeqSet &rs = e->sets[GACT_SET_REF];
+    hipStream_t stream = e->slots[0].stream;
+    PassScratch<gact_pileup_stats> &ps = pl.scratch;
+    const uint32_t *d_counts = (const uint32_t *)ps.p;
+    const uint32_t *d_ins = pl.ins_slots ? (const uint32_t *)(ps.p + pl.at_ins) : nullptr;
+    const uint8_t *d_cons = ps.p + pl.at_cons;
+    gact_read_corrected *d_reads = (gact_read_corrected *)(ps.p + pl.at_corrected);
+    long long *d_read_at = (long long *)(ps.p + pl.at_read_at);
+    const uint8_t *own = rs.d_raw + pl.base;
+    const int K = pl.ins_slots;
+    const size_t full = (size_t)std::max(1, e->prop.multiProcessorCount) * 8;              // eight waves on every SIMD
+    const size_t want = ((size_t)pl.n_reads + gact::kPileupBlock / 64 - 1) / (gact::kPileupBlock / 64);
+    const dim3 grid((unsigned)std::max((size_t)1, std::min(want, full))), block(gact::kPileupBlock);
+    if ((rc = ps.timer.start(stream, "pileup_corrected"))) return rc;
+    if ((rc = pileup_launch_consensus(e, stream, min_depth, full))) return rc;
+    if (pl.n_reads > 0) {
+        hipLaunchKernelGGL(gact::pileup_spell_kernel<false>, grid, block, 0, stream, d_counts, d_ins, K, own, d_cons,
+                           rs.d_offsets + pl.read_first, (long long)pl.base, pl.n_reads, (uint32_t)min_depth, d_read_at, d_reads,
+                           (uint8_t *)nullptr, 0ll);
+        hipLaunchKernelGGL(gact::pileup_scan_kernel, dim3(1), block, 0, stream, pl.n_reads, d_read_at, d_reads);
+        HIP_TRY(hipGetLastError());
+    }
+    long long totals[2] = {0, 0};                                 // all bases, the inserted ones (n_reads == 0: zeroed by begin)
+    HIP_TRY(hipMemcpyAsync(totals, d_read_at + pl.n_reads, sizeof totals, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (totals[0] < 0 || totals[0] > pl.positions * (K + 1) || totals[1] < 0 || totals[1] > totals[0])
+        return fail(GACT_HIP_EDEVICE, "pileup_corrected: the device counted %lld bases, %lld of them inserted, at %lld positions",
+                    totals[0], totals[1], (long long)pl.positions);
+    if (seq_len) *seq_len = totals[0];
+    const bool room = !seq || seq_cap >= totals[0];
+    if (seq && room && totals[0] > 0) {
+        if ((size_t)totals[0] > pl.seq_cap) {
+            if (pl.seq) (void)hipFree(pl.seq);
+            pl.seq = nullptr; pl.seq_cap = 0;
+            if (hipMalloc((void **)&pl.seq, (size_t)totals[0]) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(GACT_HIP_ENOMEM, "pileup_corrected: device allocation failed (%lld bases)", totals[0]);
+            }
+            pl.seq_cap = (size_t)totals[0];
+        }
+        hipLaunchKernelGGL(gact::pileup_spell_kernel<true>, grid, block, 0, stream, d_counts, d_ins, K, own, d_cons,
+                           rs.d_offsets + pl.read_first, (long long)pl.base, pl.n_reads, (uint32_t)min_depth, d_read_at, d_reads,
+                           pl.seq, totals[0]);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(seq, pl.seq, (size_t)totals[0], hipMemcpyDeviceToHost, stream));
+    }
+    if (ins && pl.positions > 0)
+        HIP_TRY(hipMemcpyAsync(ins, d_ins, (size_t)pl.positions * (size_t)K * sizeof(gact_pileup_ins), hipMemcpyDeviceToHost, stream));
+    if (read_at) HIP_TRY(hipMemcpyAsync(read_at, d_read_at, ((size_t)pl.n_reads + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    if (reads && pl.n_reads > 0)
+        HIP_TRY(hipMemcpyAsync(reads, d_reads, (size_t)pl.n_reads * sizeof(gact_read_corrected), hipMemcpyDeviceToHost, stream));
+    float ms = 0;
+    if ((rc = ps.timer.stop(stream, &ms))) return rc;
+    {
+        std::lock_guard<std::mutex> lk(pl.mu);
+        pl.ins_stats.device_ms += ms;
+        pl.ins_stats.emitted = totals[1];
+    }
+    if (!room)
+        return fail(GACT_HIP_EINVAL, "pileup_corrected: %lld bases, room for %lld: call again with room for *seq_len", totals[0],
+                    (long long)seq_cap);
+    return 0;
+}
+
+int gact_hip_last_pileup_ins_stats(gact_hip_engine *e, gact_pileup_ins_stats *stats)
+{
+    if (!e || !stats) return fail(GACT_HIP_EINVAL, "last_pileup_ins_stats: NULL argument");
+    Pileup &pl = e->pileup;
+    if (!pl.open) return fail(GACT_HIP_EINVAL, "last_pileup_ins_stats: no window is open (gact_hip_pileup_begin first)");
+    std::lock_guard<std::mutex> lk(pl.mu);
+    *stats = pl.ins_stats;
     return 0;
 }
 

@@ -57,6 +57,12 @@ PILEUP_COL_DTYPE = np.dtype([("n", "<u4", (8,))])
 READ_PILEUP_DTYPE = np.dtype([(n, "<i4") for n in ("n_alignments", "max_depth", "called", "changed", "deleted", "ins_flagged")] +
                              [("reserved", "<i4", (2,))])
 assert PILEUP_COL_DTYPE.itemsize == 32 and READ_PILEUP_DTYPE.itemsize == 32
+# the inserted bases in front of a position, per slot (gact_pileup_ins), and the per-read table of pileup_corrected
+PILEUP_MAX_INS_SLOTS = 4
+PILEUP_INS_DTYPE = np.dtype([("n", "<u4", (4,))])
+READ_CORRECTED_DTYPE = np.dtype([(n, "<i4") for n in ("length", "inserted", "ins_sites", "deleted", "changed")] +
+                                [("reserved", "<i4", (3,))])
+assert PILEUP_INS_DTYPE.itemsize == 16 and READ_CORRECTED_DTYPE.itemsize == 32
 
 # alignment ops (include/gact_hip.h GACT_PATH_OP_*): BAM's CIGAR numbering; an op word is len << 4 | op
 OP_I, OP_D, OP_EQ, OP_X = 1, 2, 7, 8
@@ -171,6 +177,11 @@ class UnitigStats(C.Structure):
 class PileupStats(C.Structure):
     _fields_ = [("device_ms", C.c_float), ("adds", C.c_int32), ("chunks", C.c_int32), ("alignments", C.c_int64),
                 ("columns", C.c_int64), ("positions", C.c_int64), ("scratch_bytes", C.c_int64)]
+
+
+class PileupInsStats(C.Structure):
+    _fields_ = [("device_ms", C.c_float), ("ins_slots", C.c_int32), ("slot_adds", C.c_int64), ("runs_truncated", C.c_int64),
+                ("emitted", C.c_int64), ("table_bytes", C.c_int64)]
 
 
 COVER_REF, COVER_QUERY, COVER_BOTH = 1, 2, 3
@@ -365,6 +376,14 @@ def load():
             getattr(L, "gact_hip_" + name).restype = C.c_int
     except AttributeError:
         pass
+    try:
+        L.gact_hip_pileup_begin_ins.argtypes = [vp, i32, i32, i32]
+        L.gact_hip_pileup_corrected.argtypes = [vp, i32, vp, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+        L.gact_hip_last_pileup_ins_stats.argtypes = [vp, C.POINTER(PileupInsStats)]
+        for name in ("pileup_begin_ins", "pileup_corrected", "last_pileup_ins_stats"):
+            getattr(L, "gact_hip_" + name).restype = C.c_int
+    except AttributeError:
+        pass
     try:                                    # (an older build loaded through GACT_HIP_LIB_PATH for an A/B run has none)
         L.gact_hip_comm_create.argtypes = [vp, i32, i32, C.c_char_p, i32, C.POINTER(vp)]
         L.gact_hip_comm_gather_lines.argtypes = [vp, C.c_int, i32, vp, vp, C.c_int64]
@@ -399,7 +418,8 @@ EXPORTS = ("gact_hip_create", "gact_hip_destroy", "gact_hip_last_error", "gact_h
            "gact_hip_last_summaries_stats", "gact_hip_format_paf", "gact_hip_select_overlaps", "gact_hip_last_select_stats",
            "gact_hip_read_coverage", "gact_hip_last_cover_stats", "gact_hip_overlap_graph", "gact_hip_last_graph_stats",
            "gact_hip_unitigs", "gact_hip_last_unitig_stats", "gact_hip_pileup_begin", "gact_hip_pileup_add",
-           "gact_hip_pileup_finish", "gact_hip_last_pileup_stats")
+           "gact_hip_pileup_finish", "gact_hip_last_pileup_stats", "gact_hip_pileup_begin_ins", "gact_hip_pileup_corrected",
+           "gact_hip_last_pileup_ins_stats")
 
 
 def plan(count, flags=0, compute_units=256, tile_size=320, tile_overlap=120, scoring=(1, -1, -1, -1), threshold=35):
@@ -758,17 +778,21 @@ class Engine:
         left after the tip cut, joins and links among them, device bytes the call holds"""
         return self._stats(self.L.gact_hip_last_unitig_stats, UnitigStats, slot)
 
-    def pileup_begin(self, read_first=0, n_reads=None):
+    def pileup_begin(self, read_first=0, n_reads=None, ins_slots=0):
         """opens the pileup window: reads [read_first, read_first + n_reads) of SET_REF (n_reads None: to the set's end), counts
-        zeroed; a second call starts over, and one that is refused leaves no window open, an earlier one's neither
-        (include/gact_hip.h gact_hip_pileup_begin)"""
+        zeroed; a second call starts over, and one that is refused leaves no window open, an earlier one's neither.
+        ins_slots (0 .. PILEUP_MAX_INS_SLOTS): the inserted bases kept in front of every position, for pileup_corrected
+        (include/gact_hip.h gact_hip_pileup_begin, gact_hip_pileup_begin_ins)"""
         n_all = len(self._ref_offsets) - 1
         if n_reads is None:
             n_reads = max(n_all - int(read_first), 0)
         self._pileup = None
-        self._check(self.L.gact_hip_pileup_begin(self.h, int(read_first), int(n_reads)))
+        if int(ins_slots) == 0:
+            self._check(self.L.gact_hip_pileup_begin(self.h, int(read_first), int(n_reads)))
+        else:
+            self._check(self.L.gact_hip_pileup_begin_ins(self.h, int(read_first), int(n_reads), int(ins_slots)))
         offs = self._ref_offsets
-        self._pileup = (int(n_reads), int(offs[int(read_first) + int(n_reads)] - offs[int(read_first)]))
+        self._pileup = (int(n_reads), int(offs[int(read_first) + int(n_reads)] - offs[int(read_first)]), int(ins_slots))
 
     def pileup_add(self, sel=None, n=None, rc_from=0x7fffffff, same_file=True, slot=0):
         """stacks the alignments of candidates `sel` of the slot's candidate array (sel None: the first n; index >= rc_from =>
@@ -786,7 +810,7 @@ class Engine:
         calls and another pileup_finish may follow (gact_hip_pileup_finish)"""
         if self._pileup is None:                      # (the sizes of the three arrays are the window's)
             raise GactHipError("gact_hip error -1: pileup_finish: no window is open (gact_hip_pileup_begin first)")
-        n_reads, n_pos = self._pileup
+        n_reads, n_pos, _ = self._pileup
         reads = np.zeros(n_reads, dtype=READ_PILEUP_DTYPE)
         cnt = np.zeros((n_pos, 8), dtype=np.uint32) if counts else None
         cons = np.zeros(n_pos, dtype=np.uint8) if consensus else None
@@ -797,6 +821,36 @@ class Engine:
         """the pileup since pileup_begin: device ms of its adds and finishes (HIP events), adds, path-run chunks, alignments
         counted, their columns, the window's positions, device bytes the window holds"""
         return self._stats(self.L.gact_hip_last_pileup_stats, PileupStats)
+
+    def pileup_corrected(self, min_depth=3, ins=False):
+        """the corrected reads of the open window, spelled on the device: (reads READ_CORRECTED_DTYPE, read_at int64
+        [n_reads + 1], seq bytes) -- read i is seq[read_at[i]:read_at[i + 1]]: for every position its emitted slots' bases,
+        then its consensus byte unless that is '-' -- or, with `ins`, (reads, read_at, seq, ins uint32 [positions, ins_slots,
+        4]), the slots' counts of A C G T; the counts stay (include/gact_hip.h gact_hip_pileup_corrected)"""
+        if self._pileup is None:                      # (the sizes of the arrays are the window's)
+            raise GactHipError("gact_hip error -1: pileup_corrected: no window is open (gact_hip_pileup_begin first)")
+        n_reads, n_pos, slots = self._pileup
+        reads = np.zeros(n_reads, dtype=READ_CORRECTED_DTYPE)
+        read_at = np.zeros(n_reads + 1, dtype=np.int64)
+        # (at least one word: a table asked of a window without slots is the library's to refuse, and it sees a pointer)
+        table = np.zeros(max(n_pos * slots * 4, 1), dtype=np.uint32) if ins else None
+        seq_len = C.c_int64()
+        cap = n_pos + n_pos // 16                   # (positions * (ins_slots + 1) always suffices; few reads grow at all)
+        for attempt in range(2):
+            seq = np.zeros(max(cap, 1), dtype=np.uint8)
+            rc = self.L.gact_hip_pileup_corrected(self.h, int(min_depth), table.ctypes.data if ins else None, _ptr(reads),
+                                                  _ptr(read_at), seq.ctypes.data, cap, C.byref(seq_len))
+            if rc == 0 or attempt or seq_len.value <= cap:
+                break
+            cap = seq_len.value                     # (EINVAL with *seq_len filled: once more with room for the bytes)
+        self._check(rc)
+        seq = seq[:seq_len.value].tobytes()
+        return (reads, read_at, seq, table[:n_pos * slots * 4].reshape(n_pos, slots, 4)) if ins else (reads, read_at, seq)
+
+    def last_pileup_ins_stats(self):
+        """the slots since pileup_begin: device ms of the pileup_corrected calls (HIP events), ins_slots, adds to slots, runs
+        longer than ins_slots, bases the last pileup_corrected put in, the table's bytes"""
+        return self._stats(self.L.gact_hip_last_pileup_ins_stats, PileupInsStats)
 
     def register_output(self, out, slot=0):
         """page-locks a caller-owned record array that will be fetched into repeatedly (opt-in; it must outlive the

@@ -3,7 +3,7 @@
 //   darwin_hip <REF.fasta> <READS.fasta> CPU_THREADS [--params params.cfg]
 //              [--candidates FILE | --dump-candidates FILE [--dsoft-only]] [--device-dsoft]
 //              [--device D] [--shard R/W] [--recode] [--cigar] [--paf] [--unique exact|pair] [--coverage K]
-//              [--pileup K] [--gfa [--unitigs K]]
+//              [--pileup K [--ins-slots S]] [--gfa [--unitigs K]]
 //
 // Plays the part of reference darwin.cpp:451-646 for the GACT stage: owns the
 // globals gact.cpp reads, loads params.cfg and the two FASTA files, builds the
@@ -39,6 +39,10 @@
 // them before the feeders start, one gact_hip_pileup_add per feeder behind its run, gact_hip_pileup_finish(K) after the join --
 // and darwin.cons.fa gets one record per reference sequence in id order: `>name called=<n> changed=<n> deleted=<n>
 // ins_flagged=<n>`, then the consensus bytes with every '-' left out, on one line.  Every other output byte is as without the flag.
+// --ins-slots S (with --pileup; 1 <= S <= 4): the window is opened with S slots (gact_hip_pileup_begin_ins), so the adds keep the
+// first S bases of every insertion run, and darwin.cons.fa gets the corrected reads of gact_hip_pileup_corrected(K) -- the bases
+// the other reads agree the sequence lacks put in, the header line with ` inserted=<n>` at its end.  Every other file is as
+// without the flag, and without it darwin.cons.fa is too.
 // --gfa (with --device-dsoft and one input file used for both sides, not with --shard): after the feeders have finished, the
 // records they wrote (the emitted ones; with --unique the selected ones; with --paf together with their summaries) go through
 // one gact_hip_overlap_graph call with the default parameters -- with --coverage K clipped to that table's spans, else against
@@ -91,6 +95,7 @@ static bool want_paf = false;                    // --paf
 static int unique_mode = -1;                     // --unique: GACT_SELECT_EXACT / GACT_SELECT_PAIR, -1: every emitted record
 static int coverage_depth = 0;                   // --coverage K: min_depth of darwin.cover.tsv, 0: no table
 static int pileup_depth = 0;                     // --pileup K: min_depth of darwin.cons.fa, 0: no consensus
+static int pileup_ins_slots = 0;                 // --ins-slots S: the inserted bases kept per position, 0: none
 static bool want_gfa = false;                    // --gfa: darwin.gfa, the overlap graph of the records written
 static int unitig_tips = -1;                     // --unitigs K: tip_reads of darwin.utg.gfa, -1: no unitigs
 // --coverage, --gfa: the records every feeder wrote a line for, in its file's order, and with --paf their summaries
@@ -472,12 +477,34 @@ static int write_consensus(gact_hip_engine *e)
         printf("\ngact_hip_pileup_finish failed: %s\n\n", gact_hip_last_error());
         return 1;
     }
+    // --ins-slots: the corrected reads come spelled from the device, back to back
+    std::vector<gact_read_corrected> corrected;
+    std::vector<int64_t> read_at;
+    std::vector<uint8_t> spelled;
+    if (pileup_ins_slots) {
+        corrected.resize(reference_seqs.size());
+        read_at.resize(reference_seqs.size() + 1);
+        spelled.resize(positions * (size_t)(pileup_ins_slots + 1));         // (always suffices)
+        int64_t n_spelled = 0;
+        if (gact_hip_pileup_corrected(e, pileup_depth, nullptr, corrected.data(), read_at.data(), spelled.data(), (int64_t)spelled.size(),
+                                      &n_spelled) != 0) {
+            printf("\ngact_hip_pileup_corrected failed: %s\n\n", gact_hip_last_error());
+            return 1;
+        }
+    }
     FILE *f = fopen("darwin.cons.fa", "w");
     if (!f) { fprintf(stderr, "--pileup: cannot write darwin.cons.fa\n"); return 1; }
     size_t at = 0;
     std::string seq;
     for (size_t i = 0; i < reference_seqs.size(); i++) {
         const gact_read_pileup &t = table[i];
+        if (pileup_ins_slots) {
+            fprintf(f, ">%s called=%d changed=%d deleted=%d ins_flagged=%d inserted=%d\n", reference_descrips[i][0].c_str(), t.called,
+                    t.changed, t.deleted, t.ins_flagged, corrected[i].inserted);
+            fwrite(spelled.data() + read_at[i], 1, (size_t)(read_at[i + 1] - read_at[i]), f);
+            fputc('\n', f);
+            continue;
+        }
         fprintf(f, ">%s called=%d changed=%d deleted=%d ins_flagged=%d\n", reference_descrips[i][0].c_str(), t.called, t.changed,
                 t.deleted, t.ins_flagged);
         seq.clear();
@@ -655,7 +682,7 @@ int main(int argc, char *argv[])
     if (argc >= 3 && strcmp(argv[1], "--selftest") == 0) return selftest(argv[2]);
     if (argc < 4) {
         fprintf(stderr, "Usage: darwin_hip <REFERENCE>.fasta <READS>.fasta CPU_THREADS --candidates FILE "
-                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K] [--gfa [--unitigs K]]]\n");
+                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K [--ins-slots S]] [--gfa [--unitigs K]]]\n");
         return 1;
     }
     std::string cand_path, dump_path, cfg_path = "params.cfg", gather_id;
@@ -688,6 +715,16 @@ int main(int argc, char *argv[])
             const long k = strtol(v, &end, 10);
             if (!*v || *end || k < 1 || k > 0x7fffffffL) { fprintf(stderr, "--pileup wants an integer >= 1, not '%s'\n", v); return 1; }
             pileup_depth = (int)k;
+        }
+        else if (!strcmp(argv[a], "--ins-slots")) {
+            const char *v = a + 1 < argc ? argv[++a] : "";
+            char *end = nullptr;
+            const long k = strtol(v, &end, 10);
+            if (!*v || *end || k < 1 || k > GACT_PILEUP_MAX_INS_SLOTS) {
+                fprintf(stderr, "--ins-slots wants an integer from 1 to %d, not '%s'\n", GACT_PILEUP_MAX_INS_SLOTS, v);
+                return 1;
+            }
+            pileup_ins_slots = (int)k;
         }
         else if (!strcmp(argv[a], "--gfa")) want_gfa = true;
         else if (!strcmp(argv[a], "--unitigs")) {
@@ -733,6 +770,10 @@ int main(int argc, char *argv[])
         // the counts come from the alignments of one engine's candidate arrays, and a rank of a sharded job holds part of every
         // sequence's overlaps: combining the ranks' counts is left to the caller
         fprintf(stderr, "--pileup: only with --device-dsoft, and not with --shard\n");
+        return 1;
+    }
+    if (pileup_ins_slots && !pileup_depth) {
+        fprintf(stderr, "--ins-slots: only with --pileup\n");
         return 1;
     }
     if (want_gfa && (!device_dsoft || shard_given || strcmp(argv[1], argv[2]) != 0)) {
@@ -802,8 +843,8 @@ int main(int argc, char *argv[])
         const bool dumping = !dump_path.empty() && dsoft_only;
         cover_records.resize((size_t)num_threads);
         cover_sums.resize((size_t)num_threads);
-        if (pileup_depth && !dumping && gact_hip_pileup_begin(e, 0, (int32_t)reference_seqs.size()) != 0) {
-            printf("\ngact_hip_pileup_begin failed: %s\n\n", gact_hip_last_error());
+        if (pileup_depth && !dumping && gact_hip_pileup_begin_ins(e, 0, (int32_t)reference_seqs.size(), pileup_ins_slots) != 0) {
+            printf("\ngact_hip_pileup_begin_ins failed: %s\n\n", gact_hip_last_error());
             return 1;
         }
         std::vector<std::thread> threads;

@@ -561,7 +561,7 @@ int gact_hip_last_unitig_stats(gact_hip_engine *e, int slot, gact_unitig_stats *
  *                           candidates).  Candidates whose ref_id lies outside the window are dropped on the host; the rest run
  *                           through the path run's chunks on the slot's stream (column buffers within GACT_HIP_PATH_BUDGET_MB),
  *                           and in each chunk the pileup kernel consumes the columns behind the chain kernel.  No ops are made
- *                           and nothing but 32 bytes of error state and counters comes back.  Synchronous on the slot's stream;
+ *                           and nothing but 48 bytes of error state and counters comes back.  Synchronous on the slot's stream;
  *                           any number of calls, also from several threads on different slots at once: the counts are integer
  *                           atomic adds, so the result does not depend on order or interleaving.  A candidate whose record has
  *                           emitted == 0, or that has no columns, adds nothing.  Without an open window, or after GACT_SET_REF
@@ -583,8 +583,8 @@ int gact_hip_last_unitig_stats(gact_hip_engine *e, int slot, gact_unitig_stats *
  *   '=' / 'X'   n[kind of query byte q] += 1 (case folded; anything but acgtACGT is OTHER), n[DEPTH] += 1 at r; r++, q++
  *   'D'         n[DEL] += 1, n[DEPTH] += 1 at r; r++
  *   'I'         q++; the FIRST column of a run of 'I' adds 1 to n[INS] at min(r, len - 1): a run counts once whatever its length
- *               (also across a tile boundary or the junction of the left and the right extension).  The inserted bases are not
- *               kept: a caller who wants them takes the CIGAR
+ *               (also across a tile boundary or the junction of the left and the right extension).  The inserted bases are kept
+ *               by a window opened with gact_hip_pileup_begin_ins (below), and by that one only
  * Consensus byte of a position: its depth < min_depth: the read's own raw byte, unchanged.  Else the largest of A, C, G, T, DEL
  * (OTHER never wins); ties go to the read's own base (case folded) if it is among the tied kinds, else in the order A, C, G, T,
  * DEL; the byte is 'A' 'C' 'G' 'T' or '-'.  All five zero (every aligned query byte was OTHER): the read's own byte, which does
@@ -616,6 +616,54 @@ int gact_hip_pileup_finish(gact_hip_engine *e, int32_t min_depth, gact_pileup_co
  * least one column), their columns, the window's positions, and the device memory the window holds. */
 typedef struct { float device_ms; int32_t adds, chunks; int64_t alignments, columns, positions, scratch_bytes; } gact_pileup_stats;
 int gact_hip_last_pileup_stats(gact_hip_engine *e, gact_pileup_stats *stats);
+
+/* The inserted bases, and the corrected reads spelled on the device.  A base the target read lacks shows in the pileup as a run
+ * of 'I' in front of a position; a window opened with ins_slots = K keeps the first K bases of every such run, so that the
+ * consensus can put them back.
+ *   gact_hip_pileup_begin_ins   gact_hip_pileup_begin with 0 <= ins_slots <= GACT_PILEUP_MAX_INS_SLOTS slots in front of every
+ *                               position: one gact_pileup_ins (16 bytes) per (position, slot), laid out [positions][K] behind the
+ *                               counts in the window's allocation and zeroed here, so a position takes 32 + 16 K bytes.
+ *                               gact_hip_pileup_begin is ins_slots = 0: no table, and its adds run the kernel they always ran.
+ *                               ins_slots outside [0, 4]: GACT_HIP_EINVAL, and no window is open
+ *   gact_hip_pileup_add         counts as above, and for an 'I' column that is the j-th of its run (j from 0; a run goes on across
+ *                               tile boundaries and the junction of the two extensions, as for n[INS]), with the target cursor
+ *                               at r: if j < K, r < len and the query byte is one of acgtACGT, ins[r][j].n[kind] += 1.  A run
+ *                               behind the read's last base (r == len) and bytes of kind OTHER add nothing to the slots; n[INS]
+ *                               is counted as ever.  A run longer than K is counted once in runs_truncated
+ *   gact_hip_pileup_corrected   the consensus for min_depth (>= 1) as gact_hip_pileup_finish makes it, then the slot call, then
+ *                               the corrected reads.  Slot j of position p is EMITTED iff p is called (n[DEPTH] >= min_depth),
+ *                               every slot below j at p is emitted, and 2 * (the slot's nA + nC + nG + nT) > n[DEPTH] of p; its
+ *                               byte is 'A' 'C' 'G' 'T' by the largest of the four counts, the first of equal ones in that
+ *                               order.  A corrected read is, for every position in order, its emitted slots' bytes, then its
+ *                               consensus byte unless that is '-' (an uncalled position gives the read's own raw byte).  With
+ *                               K = 0 that is the consensus with every '-' left out.
+ *                               Outputs, any of which may be NULL: ins, the table, positions * K records; read_at[n_reads + 1],
+ *                               the reads lie back to back in seq and read_at[n_reads] == *seq_len; seq, the bytes; reads
+ *                               [n_reads].  seq_cap < *seq_len (with seq not NULL): GACT_HIP_EINVAL with everything else filled
+ *                               in, call again with room for *seq_len; positions * (K + 1) always suffices.  Synchronous on
+ *                               slot 0's stream, as finish is, and as little to be called while an add is running; the counts
+ *                               stay.  All integer: the same bytes on every call, whichever slots added in whichever order.
+ *                               GACT_HIP_EINVAL: no open window, GACT_SET_REF uploaded again since, min_depth < 1, seq_cap < 0,
+ *                               ins not NULL on a window without slots.  The spelled bytes lie in a second allocation of the
+ *                               engine's, *seq_len bytes, grown on demand. */
+#define GACT_PILEUP_MAX_INS_SLOTS 4
+typedef struct { uint32_t n[4]; } gact_pileup_ins;          /* A C G T (GACT_PILEUP_A ..): 16 bytes per position and slot */
+typedef struct {
+    int32_t length;         /* bases of the corrected read = the read's length + inserted - deleted */
+    int32_t inserted;       /* emitted slots: bases put in */
+    int32_t ins_sites;      /* positions with at least one emitted slot */
+    int32_t deleted;        /* positions whose consensus byte is '-': left out */
+    int32_t changed;        /* as gact_read_pileup's */
+    int32_t reserved[3];
+} gact_read_corrected;      /* 32 bytes */
+int gact_hip_pileup_begin_ins(gact_hip_engine *e, int32_t read_first, int32_t n_reads, int32_t ins_slots);
+int gact_hip_pileup_corrected(gact_hip_engine *e, int32_t min_depth, gact_pileup_ins *ins, gact_read_corrected *reads,
+                              int64_t *read_at, uint8_t *seq, int64_t seq_cap, int64_t *seq_len);
+/* The slots since the last begin: HIP-event time of the gact_hip_pileup_corrected calls (copies and kernels), the window's
+ * ins_slots, the adds to slots and the runs longer than ins_slots its gact_hip_pileup_add calls made, the bases the last
+ * gact_hip_pileup_corrected put in (emitted slots), and the table's bytes. */
+typedef struct { float device_ms; int32_t ins_slots; int64_t slot_adds, runs_truncated, emitted, table_bytes; } gact_pileup_ins_stats;
+int gact_hip_last_pileup_ins_stats(gact_hip_engine *e, gact_pileup_ins_stats *stats);
 
 /* ------------------------------------------------------------------------
  * D-SOFT seed filter on the device (the stage in front of the path; optional:
