@@ -40,7 +40,6 @@
 
 namespace gact {
 
-constexpr int kCoverBlock = 256;                  // four waves
 constexpr int32_t kCoverMaxRecords = 1 << 30;
 constexpr int32_t kCoverMaxLength = 0x7fffffff - 64;    // (the sweep's chunk begin stays an int32 one step past the end)
 constexpr int kCoverBadIndex = 1, kCoverBadRead = 2;    // bits of the flag word
@@ -61,36 +60,31 @@ __device__ inline bool cover_mark(long long b, long long e, int id, bool mirror,
     return true;
 }
 
-__global__ void __launch_bounds__(kCoverBlock)
+__global__ void __launch_bounds__(kPassBlock)
 cover_mark_kernel(const gact_overlap *__restrict__ rec, int n, const int *__restrict__ sel, int n_chosen,
                   const gact_path_summary *__restrict__ sums, int sides, int n_reads, const long long *__restrict__ off,
                   int *diff, gact_read_cover *cover, int *flag)
 {
-    const int k = blockIdx.x * kCoverBlock + threadIdx.x;
+    const int k = blockIdx.x * kPassBlock + threadIdx.x;
     if (k >= n_chosen) return;
     const int i = sel ? sel[k] : k;
     if (i < 0 || i >= n) { atomicOr(flag, kCoverBadIndex); return; }
     const gact_overlap r = rec[i];
     if (!r.emitted) return;
     long long ab = r.ab, bb = r.bb;
-    if (sums) {
-        const gact_path_summary s = sums[k];
-        const long long m = (long long)s.n_eq + s.n_x;
-        ab = (long long)r.ae - (m + s.del_bases);
-        bb = (long long)r.be - (m + s.ins_bases);
-    }
+    if (sums) begins_from_summary(r, sums[k], ab, bb);
     bool ok = true;
     if (sides & GACT_COVER_REF) ok = cover_mark(ab, r.ae, r.ref_id, false, n_reads, off, diff, cover);
     if (sides & GACT_COVER_QUERY) ok = cover_mark(bb, r.be, r.query_id, r.comp != 0, n_reads, off, diff, cover) && ok;
     if (!ok) atomicOr(flag, kCoverBadRead);
 }
 
-__global__ void __launch_bounds__(kCoverBlock)
+__global__ void __launch_bounds__(kPassBlock)
 cover_sweep_kernel(int n_reads, const long long *__restrict__ off, const int *__restrict__ diff, int min_depth,
                    gact_read_cover *__restrict__ cover, int *__restrict__ depth_out)
 {
     const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * (kCoverBlock / 64) + (threadIdx.x >> 6), n_waves = gridDim.x * (kCoverBlock / 64);
+    const int wave = blockIdx.x * (kPassBlock / 64) + (threadIdx.x >> 6), n_waves = gridDim.x * (kPassBlock / 64);
     for (int read = wave; read < n_reads; read += n_waves) {
         const long long base = off[read];
         const int len = (int)(off[read + 1] - base - 1);
@@ -103,13 +97,9 @@ cover_sweep_kernel(int n_reads, const long long *__restrict__ off, const int *__
         for (int c0 = 0; c0 < len; c0 += 64) {
             const int p = c0 + lane;
             const bool valid = p < len;
-            int x = next;
+            const int x = next;
             next = p < len - 64 ? d[p + 64] : 0;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(x, o);
-                if (lane >= o) x += t;
-            }
-            const int depth = carry + x;                  // (an invalid lane adds 0: the depth of the read's last position)
+            const int depth = carry + wave_scan(x, lane); // (an invalid lane adds 0: the depth of the read's last position)
             carry = __shfl(depth, 63);
             if (valid) {
                 if (out) out[p] = depth;
@@ -207,13 +197,10 @@ int gact_hip_read_coverage(gact_hip_engine *e, int slot, int32_t n, const gact_o
     HIP_TRY(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(hipMemsetAsync(d_cover, 0, at_diff + n_diff * sizeof(int32_t) - at_cover, sl.stream));
     if (n_chosen > 0)
-        hipLaunchKernelGGL(gact::cover_mark_kernel, dim3((unsigned)(((size_t)n_chosen + gact::kCoverBlock - 1) / gact::kCoverBlock)),
-                           dim3(gact::kCoverBlock), 0, sl.stream, d_rec, n, d_sel, n_chosen, d_sums, sides, n_reads, d_off, d_diff,
-                           d_cover, d_flag);
-    const size_t want_blocks = ((size_t)n_reads + gact::kCoverBlock / 64 - 1) / (gact::kCoverBlock / 64);
-    const size_t full = (size_t)std::max(1, e->prop.multiProcessorCount) * 8;              // eight waves on every SIMD
-    hipLaunchKernelGGL(gact::cover_sweep_kernel, dim3((unsigned)std::min(want_blocks, full)), dim3(gact::kCoverBlock), 0, sl.stream,
-                       n_reads, d_off, d_diff, min_depth, d_cover, d_depth);
+        hipLaunchKernelGGL(gact::cover_mark_kernel, lane_blocks((size_t)n_chosen), dim3(gact::kPassBlock), 0, sl.stream, d_rec, n, d_sel,
+                           n_chosen, d_sums, sides, n_reads, d_off, d_diff, d_cover, d_flag);
+    hipLaunchKernelGGL(gact::cover_sweep_kernel, wave_blocks(e, (size_t)n_reads), dim3(gact::kPassBlock), 0, sl.stream, n_reads, d_off,
+                       d_diff, min_depth, d_cover, d_depth);
     HIP_TRY(hipGetLastError());
     int flag = 0;
     HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, sl.stream));

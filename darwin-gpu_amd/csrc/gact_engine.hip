@@ -1940,7 +1940,8 @@ int gact_hip_measure_valu_rate(gact_hip_engine *e, double *lane_ops_per_s)
 
 #include "dsoft_engine.hpp"      // gact_hip_dsoft_build / _query / candidates_download
 #include "gact_gather.hpp"       // gact_hip_comm_*: the RCCL gather of a sharded job
-#include "gact_pass.hpp"         // what the passes below share: their selection, records, refusals and last_*_stats
+#include "gact_pass_device.hpp"  // what the pass kernels below share: the block, the block scan, the best-holder table, the wave count
+#include "gact_pass.hpp"         // what the passes below share on the host: their selection, records, refusals and last_*_stats
 #include "gact_path_run.hpp"     // gact_hip_candidates_paths / _summaries: the alignments again, as CIGARs or as counts
 #include "gact_select.hpp"       // gact_hip_select_overlaps: one overlap per class, behind every other kernel
 #include "gact_cover.hpp"        // gact_hip_read_coverage: per-read coverage of an overlap set, behind those

@@ -8,18 +8,15 @@
 // Nine kernels on the slot's stream, nothing on the host between them:
 //   1 graph_class_kernel    one lane per chosen record: its class, and for a DOVETAIL record its two proposals (the arc and the
 //                           complement, as gact_graph_arc; u = -1 for every other record).  atomicMin of the record index into
-//                           contained_by (unsigned, 0xffffffff = none), atomicAdd into the read's counters, one ballot per class
-//                           and wave into the statistics, atomicOr into a flag word for a sel index outside [0, n) or a read
+//                           contained_by (unsigned, 0xffffffff = none), atomicAdd into the read's counters, one wave_count per
+//                           class into the statistics, atomicOr into a flag word for a sel index outside [0, n) or a read
 //                           id outside [0, n_reads) -- the host reads that word before it copies anything out.
 //   2 graph_insert_kernel   behind the kernel boundary (contained_by is final): one lane per proposal whose two reads are not
-//                           contained.  An open-addressing table of proposal indices (int32, -1 empty, a power of two >= twice
-//                           the proposals, linear probing) keyed (u, v): a proposal claims an empty slot with atomicCAS, passes
-//                           a slot of another key, and at a slot of its own key replaces the holder only while it is better --
-//                           higher score, lower record index, lower proposal index: a total order.  select_insert_kernel's
-//                           argument: a slot never becomes empty again and never changes its key, the holder only gets better,
-//                           so every loop ends, nothing waits for another wave, and the winner does not depend on arrival.
+//                           contained, into a best-holder table of proposal indices (table_insert_best, gact_pass_device.hpp,
+//                           which holds the argument) with >= twice the proposals slots, keyed (u, v); better is the higher
+//                           score, then the lower record index, then the lower proposal index: a total order.
 //   3 graph_degree_kernel   one lane per table slot: a holder adds 1 to the out-degree of its u.
-//   4 graph_scan_kernel     exclusive scan of the 2 n_reads degrees, one block, a carry from chunk to chunk (no look-back).
+//   4 graph_scan_kernel     exclusive scan of the 2 n_reads degrees, one block (block_scan_step; no look-back).
 //   5 graph_scatter_kernel  one lane per table slot: the holder goes to first[u] + atomicAdd(fill[u], 1) of the CSR list -- in
 //                           arrival order, which the next kernel removes.
 //   6 graph_order_kernel    one wave per vertex, grid-stride: lanes stride over the vertex's list (it may be longer than 64), each
@@ -42,19 +39,15 @@
 
 namespace gact {
 
-constexpr int kGraphBlock = 256;                  // four waves
 constexpr int32_t kGraphMaxRecords = 1 << 28;     // (a proposal index 2 k + 1 and a table of >= 4 n slots fit an int32 / uint32)
 constexpr int32_t kGraphMaxReads = 1 << 30;       // (a vertex 2 i + 1 fits an int32)
 constexpr int kGraphBadIndex = 1, kGraphBadRead = 2;    // bits of the flag word
-constexpr int kGraphEmpty = -1;
 // the statistics' counters: by_class[8], then
 constexpr int kGraphProposed = 8, kGraphKept = 9, kGraphContained = 10, kGraphCounters = 16;
 
 __device__ inline uint32_t graph_hash(int u, int v)
 {
-    uint32_t h = select_mix(select_mix(0x2545f491u, (uint32_t)u), (uint32_t)v);
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return h;
+    return hash_final(hash_mix(hash_mix(kHashSeed, (uint32_t)u), (uint32_t)v));
 }
 
 // is proposal a (index pa) better than proposal b (index pb) of its key?  pa != pb
@@ -65,13 +58,13 @@ __device__ inline bool graph_better(int pa, const gact_graph_arc &a, int pb, con
     return pa < pb;
 }
 
-__global__ void __launch_bounds__(kGraphBlock)
+__global__ void __launch_bounds__(kPassBlock)
 graph_class_kernel(const gact_overlap *__restrict__ rec, int n, const int *__restrict__ sel, int n_chosen,
                    const gact_path_summary *__restrict__ sums, int n_reads, const int *__restrict__ lens,
                    const int *__restrict__ clip, gact_graph_params p, gact_graph_read *reads, unsigned *contained_by,
                    uint8_t *__restrict__ classes, gact_graph_arc *__restrict__ props, unsigned long long *counters, int *flag)
 {
-    const int k = blockIdx.x * kGraphBlock + threadIdx.x;
+    const int k = blockIdx.x * kPassBlock + threadIdx.x;
     int cls = -1;                                  // (a lane behind the last chosen record)
     if (k < n_chosen) {
         cls = GACT_GRAPH_NONE;
@@ -91,12 +84,7 @@ graph_class_kernel(const gact_overlap *__restrict__ rec, int n, const int *__res
                 const int rev = r.comp != 0;
                 long long ab = r.ab, bb = r.bb;
                 const long long ae = r.ae, be = r.be;
-                if (sums) {
-                    const gact_path_summary s = sums[k];
-                    const long long m = (long long)s.n_eq + s.n_x;
-                    ab = ae - (m + s.del_bases);
-                    bb = be - (m + s.ins_bases);
-                }
+                if (sums) begins_from_summary(r, sums[k], ab, bb);
                 const long long len_t = lens[t], len_q = lens[q];
                 long long cbt = 0, cet = len_t, cbq = 0, ceq = len_q;
                 if (clip) { cbt = clip[2 * t]; cet = clip[2 * t + 1]; cbq = clip[2 * q]; ceq = clip[2 * q + 1]; }
@@ -148,110 +136,70 @@ graph_class_kernel(const gact_overlap *__restrict__ rec, int n, const int *__res
         props[2 * (size_t)k] = a0;
         props[2 * (size_t)k + 1] = a1;
     }
-    for (int c = 0; c < 8; c++) {
-        const unsigned long long m = __ballot(cls == c);
-        if (m && (threadIdx.x & 63) == 0) atomicAdd(&counters[c], (unsigned long long)__popcll(m));
-    }
+    for (int c = 0; c < 8; c++) wave_count(&counters[c], cls == c);
 }
 
-__global__ void __launch_bounds__(kGraphBlock)
+__global__ void __launch_bounds__(kPassBlock)
 graph_insert_kernel(const gact_graph_arc *__restrict__ props, int n_props, const unsigned *__restrict__ contained_by, int *table,
                     uint32_t mask, unsigned long long *counters)
 {
-    const int pi = blockIdx.x * kGraphBlock + threadIdx.x;
+    const int pi = blockIdx.x * kPassBlock + threadIdx.x;
     bool live = false;
     gact_graph_arc a;
     if (pi < n_props) {
         a = props[pi];
         live = a.u >= 0 && contained_by[a.u >> 1] == 0xffffffffu && contained_by[a.v >> 1] == 0xffffffffu;
     }
-    const unsigned long long m = __ballot(live);
-    if (m && (threadIdx.x & 63) == 0) atomicAdd(&counters[kGraphProposed], (unsigned long long)__popcll(m));
+    wave_count(&counters[kGraphProposed], live);
     if (!live) return;
-    uint32_t s = graph_hash(a.u, a.v) & mask;
-    // (at most n_props of the >= 2 n_props slots are ever taken: an empty slot, or the key's own, comes up before the probe is round)
-    for (;;) {
-        int j = __hip_atomic_load(&table[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (j == kGraphEmpty) {
-            j = atomicCAS(&table[s], kGraphEmpty, pi);
-            if (j == kGraphEmpty) break;                       // claimed
-        }
-        if (props[j].u == a.u && props[j].v == a.v) {
-            // the holder is of this key for good; it is replaced only by a better proposal, so this ends
-            while (graph_better(pi, a, j, props[j])) {
-                const int seen = atomicCAS(&table[s], j, pi);
-                if (seen == j) break;
-                j = seen;
-            }
-            break;
-        }
-        s = (s + 1) & mask;
-    }
+    table_insert_best(table, mask, graph_hash(a.u, a.v), pi,
+                      [&](int j) { return props[j].u == a.u && props[j].v == a.v; },
+                      [&](int j) { return graph_better(pi, a, j, props[j]); });
 }
 
-// the proposal that holds key (u, v), -1: none.  The table is complete: no kernel that looks up runs beside one that inserts
-__device__ inline int graph_find(const gact_graph_arc *__restrict__ props, const int *__restrict__ table, uint32_t mask, int u, int v)
-{
-    uint32_t s = graph_hash(u, v) & mask;
-    for (;;) {
-        const int j = table[s];
-        if (j == kGraphEmpty) return -1;
-        if (props[j].u == u && props[j].v == v) return j;
-        s = (s + 1) & mask;
-    }
-}
-
-__global__ void __launch_bounds__(kGraphBlock)
+__global__ void __launch_bounds__(kPassBlock)
 graph_degree_kernel(const gact_graph_arc *__restrict__ props, const int *__restrict__ table, size_t slots, int *deg)
 {
-    const size_t s = (size_t)blockIdx.x * kGraphBlock + threadIdx.x;
+    const size_t s = (size_t)blockIdx.x * kPassBlock + threadIdx.x;
     if (s >= slots) return;
     const int j = table[s];
-    if (j != kGraphEmpty) atomicAdd(&deg[props[j].u], 1);
+    if (j != kTableEmpty) atomicAdd(&deg[props[j].u], 1);
 }
 
 // one block: first[0, nv] = the exclusive scan of deg[0, nv), first[nv] = the number of arcs
-__global__ void __launch_bounds__(kGraphBlock)
+__global__ void __launch_bounds__(kPassBlock)
 graph_scan_kernel(int nv, const int *__restrict__ deg, int *__restrict__ first)
 {
-    __shared__ int s_scan[kGraphBlock];
-    int carry = 0;
-    for (int base = 0; base < nv; base += kGraphBlock) {
+    long long carry = 0;
+    for (int base = 0; base < nv; base += kPassBlock) {
         const int k = base + (int)threadIdx.x;
-        const int own = k < nv ? deg[k] : 0;
-        s_scan[threadIdx.x] = own;
-        __syncthreads();
-        for (int d = 1; d < kGraphBlock; d <<= 1) {
-            const int a = (int)threadIdx.x >= d ? s_scan[threadIdx.x - d] : 0;
-            __syncthreads();
-            s_scan[threadIdx.x] += a;
-            __syncthreads();
-        }
-        if (k < nv) first[k] = carry + s_scan[threadIdx.x] - own;
-        carry += s_scan[kGraphBlock - 1];
-        __syncthreads();
+        long long own[1] = {0}, before[1], total[1];
+        if (k < nv) own[0] = deg[k];
+        block_scan_step(own, before, total);
+        if (k < nv) first[k] = (int)(carry + before[0]);
+        carry += total[0];
     }
-    if (threadIdx.x == 0) first[nv] = carry;
+    if (threadIdx.x == 0) first[nv] = (int)carry;
 }
 
-__global__ void __launch_bounds__(kGraphBlock)
+__global__ void __launch_bounds__(kPassBlock)
 graph_scatter_kernel(const gact_graph_arc *__restrict__ props, const int *__restrict__ table, size_t slots,
                      const int *__restrict__ first, int *fill, int *__restrict__ csr)
 {
-    const size_t s = (size_t)blockIdx.x * kGraphBlock + threadIdx.x;
+    const size_t s = (size_t)blockIdx.x * kPassBlock + threadIdx.x;
     if (s >= slots) return;
     const int j = table[s];
-    if (j == kGraphEmpty) return;
+    if (j == kTableEmpty) return;
     const int u = props[j].u;
     csr[first[u] + atomicAdd(&fill[u], 1)] = j;
 }
 
-__global__ void __launch_bounds__(kGraphBlock)
+__global__ void __launch_bounds__(kPassBlock)
 graph_order_kernel(int nv, const gact_graph_arc *__restrict__ props, const int *__restrict__ first, const int *__restrict__ csr,
                    gact_graph_arc *__restrict__ arcs)
 {
     const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * (kGraphBlock / 64) + (threadIdx.x >> 6), n_waves = gridDim.x * (kGraphBlock / 64);
+    const int wave = blockIdx.x * (kPassBlock / 64) + (threadIdx.x >> 6), n_waves = gridDim.x * (kPassBlock / 64);
     for (int u = wave; u < nv; u += n_waves) {
         const int b = first[u], d = first[u + 1] - b;
         for (int e = lane; e < d; e += 64) {
@@ -266,12 +214,12 @@ graph_order_kernel(int nv, const gact_graph_arc *__restrict__ props, const int *
     }
 }
 
-__global__ void __launch_bounds__(kGraphBlock)
+__global__ void __launch_bounds__(kPassBlock)
 graph_reduce_kernel(int nv, const gact_graph_arc *__restrict__ props, const int *__restrict__ table, uint32_t mask,
                     const int *__restrict__ first, gact_graph_arc *arcs, int fuzz)
 {
     const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * (kGraphBlock / 64) + (threadIdx.x >> 6), n_waves = gridDim.x * (kGraphBlock / 64);
+    const int wave = blockIdx.x * (kPassBlock / 64) + (threadIdx.x >> 6), n_waves = gridDim.x * (kPassBlock / 64);
     for (int u = wave; u < nv; u += n_waves) {
         const int b = first[u], d = first[u + 1] - b;
         if (d < 2) continue;
@@ -282,16 +230,16 @@ graph_reduce_kernel(int nv, const gact_graph_arc *__restrict__ props, const int 
             const int x = arcs[b + ix].v, w = arcs[b + iw].v;
             const long long len_ux = arcs[b + ix].len, len_uw = arcs[b + iw].len;
             if (len_uw > len_ux + fuzz) continue;              // (every len is >= 1: no w -> x can make up for it)
-            const int j = graph_find(props, table, mask, w, x);
-            if (j >= 0 && len_uw + props[j].len <= len_ux + fuzz) atomicOr(&arcs[b + ix].flags, 1);
+            const int j = table_find(table, mask, graph_hash(w, x), [&](int h) { return props[h].u == w && props[h].v == x; });
+            if (j != kTableEmpty && len_uw + props[j].len <= len_ux + fuzz) atomicOr(&arcs[b + ix].flags, 1);
         }
     }
 }
 
-__global__ void __launch_bounds__(kGraphBlock)
+__global__ void __launch_bounds__(kPassBlock)
 graph_mirror_kernel(int n_arcs, const int *__restrict__ first, gact_graph_arc *arcs)
 {
-    const int k = blockIdx.x * kGraphBlock + threadIdx.x;
+    const int k = blockIdx.x * kPassBlock + threadIdx.x;
     if (k >= n_arcs) return;
     const int from = arcs[k].v ^ 1, to = arcs[k].u ^ 1;
     for (int e = first[from]; e < first[from + 1]; e++)
@@ -301,11 +249,11 @@ graph_mirror_kernel(int n_arcs, const int *__restrict__ first, gact_graph_arc *a
         }
 }
 
-__global__ void __launch_bounds__(kGraphBlock)
+__global__ void __launch_bounds__(kPassBlock)
 graph_reads_kernel(int n_reads, const unsigned *__restrict__ contained_by, const int *__restrict__ first,
                    const gact_graph_arc *__restrict__ arcs, gact_graph_read *reads, unsigned long long *counters)
 {
-    const int i = blockIdx.x * kGraphBlock + threadIdx.x;
+    const int i = blockIdx.x * kPassBlock + threadIdx.x;
     int kept_here = 0;
     bool inside = false;
     if (i < n_reads) {
@@ -321,11 +269,8 @@ graph_reads_kernel(int n_reads, const unsigned *__restrict__ contained_by, const
         }
     }
     for (int o = 32; o > 0; o >>= 1) kept_here += __shfl_xor(kept_here, o);
-    const unsigned long long m = __ballot(inside);
-    if ((threadIdx.x & 63) == 0) {
-        if (kept_here) atomicAdd(&counters[kGraphKept], (unsigned long long)kept_here);
-        if (m) atomicAdd(&counters[kGraphContained], (unsigned long long)__popcll(m));
-    }
+    if (kept_here && (threadIdx.x & 63) == 0) atomicAdd(&counters[kGraphKept], (unsigned long long)kept_here);
+    wave_count(&counters[kGraphContained], inside);
 }
 
 }  // namespace gact
@@ -353,12 +298,7 @@ int gact_hip_overlap_graph(gact_hip_engine *e, int slot, int32_t n, const gact_o
         return fail(GACT_HIP_EINVAL, "overlap_graph: bad arguments (n = %d, at most %d; n_reads = %d, at most %d; n_sel = %d; arcs_cap = %lld)",
                     n, gact::kGraphMaxRecords, n_reads, gact::kGraphMaxReads, n_sel, (long long)arcs_cap);
     if (n_reads > 0 && (!read_lens || !reads)) return fail(GACT_HIP_EINVAL, "overlap_graph: read_lens or reads is NULL");
-    for (int32_t i = 0; i < n_reads; i++) {
-        if (read_lens[i] < 0) return fail(GACT_HIP_EINVAL, "overlap_graph: read %d has the negative length %d", i, read_lens[i]);
-        if (clip && !(0 <= clip[2 * (size_t)i] && clip[2 * (size_t)i] <= clip[2 * (size_t)i + 1] && clip[2 * (size_t)i + 1] <= read_lens[i]))
-            return fail(GACT_HIP_EINVAL, "overlap_graph: the clip [%d, %d) of read %d is not inside [0, %d]", clip[2 * (size_t)i],
-                        clip[2 * (size_t)i + 1], i, read_lens[i]);
-    }
+    if (check_read_lens("overlap_graph", n_reads, read_lens, clip) < 0) return GACT_HIP_EINVAL;
     Slot &sl = e->slots[slot];
     if ((rc = slot_records_check(sl, slot, n, records, "overlap_graph"))) return rc;
     if (n_reads == 0) return 0;
@@ -405,22 +345,20 @@ int gact_hip_overlap_graph(gact_hip_engine *e, int slot, int32_t n, const gact_o
     HIP_TRY(hipMemcpyAsync(d_lens, read_lens, (size_t)n_reads * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
     if (clip) HIP_TRY(hipMemcpyAsync(gb.p + at_clip, clip, nv * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(hipMemsetAsync(d_reads, 0, at_first - at_reads, sl.stream));
-    HIP_TRY(hipMemsetAsync(d_cby, 0xff, at_table + slots * sizeof(int) - at_cby, sl.stream));        // no container, kGraphEmpty
-    const dim3 block(gact::kGraphBlock);
-    auto blocks = [](size_t lanes) { return dim3((unsigned)((lanes + gact::kGraphBlock - 1) / gact::kGraphBlock)); };
-    const size_t want_waves = (nv + gact::kGraphBlock / 64 - 1) / (gact::kGraphBlock / 64);
-    const dim3 wave_grid((unsigned)std::min(want_waves, (size_t)std::max(1, e->prop.multiProcessorCount) * 8));
+    HIP_TRY(hipMemsetAsync(d_cby, 0xff, at_table + slots * sizeof(int) - at_cby, sl.stream));        // no container, kTableEmpty everywhere
+    const dim3 block(gact::kPassBlock);
+    const dim3 wave_grid = wave_blocks(e, nv);
     const uint32_t mask = (uint32_t)(slots - 1);
     if (n_chosen > 0) {
-        hipLaunchKernelGGL(gact::graph_class_kernel, blocks((size_t)n_chosen), block, 0, sl.stream, d_rec, n, d_sel, n_chosen, d_sums,
+        hipLaunchKernelGGL(gact::graph_class_kernel, lane_blocks((size_t)n_chosen), block, 0, sl.stream, d_rec, n, d_sel, n_chosen, d_sums,
                            n_reads, d_lens, d_clip, p, d_reads, d_cby, d_classes, d_props, d_counters, d_flag);
-        hipLaunchKernelGGL(gact::graph_insert_kernel, blocks(n_props), block, 0, sl.stream, d_props, (int)n_props, d_cby, d_table, mask,
+        hipLaunchKernelGGL(gact::graph_insert_kernel, lane_blocks(n_props), block, 0, sl.stream, d_props, (int)n_props, d_cby, d_table, mask,
                            d_counters);
-        hipLaunchKernelGGL(gact::graph_degree_kernel, blocks(slots), block, 0, sl.stream, d_props, d_table, slots, d_deg);
+        hipLaunchKernelGGL(gact::graph_degree_kernel, lane_blocks(slots), block, 0, sl.stream, d_props, d_table, slots, d_deg);
     }
     hipLaunchKernelGGL(gact::graph_scan_kernel, dim3(1), block, 0, sl.stream, (int)nv, d_deg, d_first);
     if (n_chosen > 0) {
-        hipLaunchKernelGGL(gact::graph_scatter_kernel, blocks(slots), block, 0, sl.stream, d_props, d_table, slots, d_first, d_fill, d_csr);
+        hipLaunchKernelGGL(gact::graph_scatter_kernel, lane_blocks(slots), block, 0, sl.stream, d_props, d_table, slots, d_first, d_fill, d_csr);
         hipLaunchKernelGGL(gact::graph_order_kernel, wave_grid, block, 0, sl.stream, (int)nv, d_props, d_first, d_csr, d_arcs);
         hipLaunchKernelGGL(gact::graph_reduce_kernel, wave_grid, block, 0, sl.stream, (int)nv, d_props, d_table, mask, d_first, d_arcs,
                            p.fuzz);
@@ -438,8 +376,8 @@ int gact_hip_overlap_graph(gact_hip_engine *e, int slot, int32_t n, const gact_o
     if (total < 0 || (size_t)total > n_props)
         return fail(GACT_HIP_EDEVICE, "overlap_graph: the device counted %d arcs of %zu proposals", total, n_props);
     if (total > 0)
-        hipLaunchKernelGGL(gact::graph_mirror_kernel, blocks((size_t)total), block, 0, sl.stream, total, d_first, d_arcs);
-    hipLaunchKernelGGL(gact::graph_reads_kernel, blocks((size_t)n_reads), block, 0, sl.stream, n_reads, d_cby, d_first, d_arcs, d_reads,
+        hipLaunchKernelGGL(gact::graph_mirror_kernel, lane_blocks((size_t)total), block, 0, sl.stream, total, d_first, d_arcs);
+    hipLaunchKernelGGL(gact::graph_reads_kernel, lane_blocks((size_t)n_reads), block, 0, sl.stream, n_reads, d_cby, d_first, d_arcs, d_reads,
                        d_counters);
     HIP_TRY(hipGetLastError());
     unsigned long long counters[gact::kGraphCounters];

@@ -14,7 +14,9 @@
 //     if ((rc = ps.end(sl.stream))) return rc;               // ev1 recorded and waited for, stats.device_ms read once
 //     the other figures of ps.stats, then any "room" refusal
 //
-// and its gact_hip_last_*_stats is one call of last_pass_stats.
+// and its gact_hip_last_*_stats is one call of last_pass_stats.  Its kernels start from gact_pass_device.hpp: kPassBlock
+// threads a block (the grids: lane_blocks, wave_blocks, full_device_blocks below), offsets by block_scan_step, a best-of-key table by
+// table_insert_best / table_find, counters by wave_count.
 #pragma once
 
 extern "C++" {                  // (templates: not in gact_engine.hip's extern "C")
@@ -30,6 +32,36 @@ static int last_pass_stats(gact_hip_engine *e, int slot, Pass Slot::*pass, Stats
     if (!ps.timed) return fail(GACT_HIP_EINVAL, "%s: slot %d %s", who, slot, none_yet);
     *stats = ps.stats;
     return 0;
+}
+
+// The grids: of a kernel with one lane per item (at least one block); the blocks that fill the device for a grid-stride
+// kernel, eight waves on every SIMD; and of a grid-stride kernel with one wave per item, the blocks that hold the items, at
+// most the ones that fill the device
+static dim3 lane_blocks(size_t lanes)
+{
+    return dim3((unsigned)((std::max(lanes, (size_t)1) + gact::kPassBlock - 1) / gact::kPassBlock));
+}
+static size_t full_device_blocks(const gact_hip_engine *e)
+{
+    return (size_t)std::max(1, e->prop.multiProcessorCount) * 8;
+}
+static dim3 wave_blocks(const gact_hip_engine *e, size_t items)
+{
+    return dim3((unsigned)std::min((std::max(items, (size_t)1) + gact::kPassWaves - 1) / gact::kPassWaves, full_device_blocks(e)));
+}
+
+// the lengths and, where given, the clips of a pass's n_reads reads (graph, unitigs) -> the clipped total, or the refusal's code (< 0)
+static int64_t check_read_lens(const char *who, int32_t n_reads, const int32_t *read_lens, const int32_t *clip)
+{
+    int64_t clipped = 0;
+    for (int32_t i = 0; i < n_reads; i++) {
+        if (read_lens[i] < 0) return fail(GACT_HIP_EINVAL, "%s: read %d has the negative length %d", who, i, read_lens[i]);
+        if (clip && !(0 <= clip[2 * (size_t)i] && clip[2 * (size_t)i] <= clip[2 * (size_t)i + 1] && clip[2 * (size_t)i + 1] <= read_lens[i]))
+            return fail(GACT_HIP_EINVAL, "%s: the clip [%d, %d) of read %d is not inside [0, %d]", who, clip[2 * (size_t)i],
+                        clip[2 * (size_t)i + 1], i, read_lens[i]);
+        clipped += clip ? clip[2 * (size_t)i + 1] - clip[2 * (size_t)i] : read_lens[i];
+    }
+    return clipped;
 }
 
 // "Records of the slot or of the caller" (select, cover, graph).  records == NULL: records [0, n) of the slot's device array,

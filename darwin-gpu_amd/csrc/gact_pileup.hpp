@@ -33,8 +33,7 @@
 //                            the popcounts of the ballots "slot j emitted" and "byte kept".  <true>, behind the scan: a position's
 //                            offset is the read's start, the carry of the steps before and the same ballots' popcounts under
 //                            the lane mask; it writes its bytes there.
-//   pileup_scan_kernel       one block: the reads' lengths -> their exclusive 64-bit scan (the shape of select_scan_kernel: two
-//                            levels, no block waits for another)
+//   pileup_scan_kernel       one block: the reads' lengths -> their exclusive scan (block_scan_step; no block waits for another)
 // No LDS but the scan's, no look-back, no spinning.  All results are integers and the same on every call.
 //
 // The counts belong to the engine (Pileup in gact_engine.hip): 32 + 16 K bytes per position of the open window, 13.4 GB for
@@ -47,7 +46,6 @@
 extern "C++" {                  // (templates: not in gact_engine.hip's extern "C")
 namespace gact {
 
-constexpr int kPileupBlock = 256;                 // four waves
 constexpr int kPileupBadRead = 1, kPileupBadSpan = 2;       // bits of the flag word
 
 struct PileupState {                              // 48 bytes behind the counts, zeroed by begin, copied back by every add
@@ -80,7 +78,7 @@ __device__ __forceinline__ int pileup_kind(uint32_t b)
 }
 
 template <bool kSlots>
-__global__ void __launch_bounds__(kPileupBlock)
+__global__ void __launch_bounds__(kPassBlock)
 pileup_kernel(const uint8_t *__restrict__ cols, const int64_t *__restrict__ col_off, const int32_t *__restrict__ n_cols,
               const gact_candidate *__restrict__ cands, const gact_overlap *__restrict__ records, int n, SeqSetDev refs,
               SeqSetDev qfwd, SeqSetDev qrc, PileupWin win)
@@ -184,12 +182,12 @@ __device__ __forceinline__ uint8_t pileup_call(const uint32_t *n, uint8_t own, u
     return (uint8_t)"ACGT-"[pick];
 }
 
-__global__ void __launch_bounds__(kPileupBlock)
+__global__ void __launch_bounds__(kPassBlock)
 pileup_consensus_kernel(const uint32_t *__restrict__ counts, const uint8_t *__restrict__ own, long long positions, uint32_t min_depth,
                         uint8_t *__restrict__ cons)
 {
-    const long long step = (long long)gridDim.x * kPileupBlock;
-    for (long long p = (long long)blockIdx.x * kPileupBlock + threadIdx.x; p < positions; p += step) {
+    const long long step = (long long)gridDim.x * kPassBlock;
+    for (long long p = (long long)blockIdx.x * kPassBlock + threadIdx.x; p < positions; p += step) {
         const uint4 *c = (const uint4 *)(counts + (size_t)p * 8);
         const uint4 lo = c[0], hi = c[1];
         const uint32_t n[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
@@ -197,13 +195,13 @@ pileup_consensus_kernel(const uint32_t *__restrict__ counts, const uint8_t *__re
     }
 }
 
-__global__ void __launch_bounds__(kPileupBlock)
+__global__ void __launch_bounds__(kPassBlock)
 pileup_reads_kernel(const uint32_t *__restrict__ counts, const uint8_t *__restrict__ own, const uint8_t *__restrict__ cons,
                     const int64_t *__restrict__ offsets, long long base, int n_reads, uint32_t min_depth,
                     const int32_t *__restrict__ n_aln, gact_read_pileup *__restrict__ reads)
 {
     const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * (kPileupBlock / 64) + (threadIdx.x >> 6), n_waves = gridDim.x * (kPileupBlock / 64);
+    const int wave = blockIdx.x * (kPassBlock / 64) + (threadIdx.x >> 6), n_waves = gridDim.x * (kPassBlock / 64);
     for (int read = wave; read < n_reads; read += n_waves) {    // (offsets: the window's first read's onwards)
         const long long first = offsets[read] - base, len = offsets[read + 1] - offsets[read];
         int called = 0, changed = 0, deleted = 0, flagged = 0;
@@ -260,14 +258,14 @@ __device__ __forceinline__ int pileup_slots(const uint32_t *__restrict__ ins, si
 // kWrite false: read_at[read] = the corrected read's length, reads[read] its record.  kWrite true, behind pileup_scan_kernel:
 // the read's bytes at seq + read_at[read]; a position that would write at or beyond seq_cap writes nothing.
 template <bool kWrite>
-__global__ void __launch_bounds__(kPileupBlock)
+__global__ void __launch_bounds__(kPassBlock)
 pileup_spell_kernel(const uint32_t *__restrict__ counts, const uint32_t *__restrict__ ins, int K, const uint8_t *__restrict__ own,
                     const uint8_t *__restrict__ cons, const int64_t *__restrict__ offsets, long long base, int n_reads,
                     uint32_t min_depth, long long *__restrict__ read_at, gact_read_corrected *__restrict__ reads,
                     uint8_t *__restrict__ seq, long long seq_cap)
 {
     const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * (kPileupBlock / 64) + (threadIdx.x >> 6), n_waves = gridDim.x * (kPileupBlock / 64);
+    const int wave = blockIdx.x * (kPassBlock / 64) + (threadIdx.x >> 6), n_waves = gridDim.x * (kPassBlock / 64);
     const uint64_t below_me = (1ull << lane) - 1;
     for (int read = wave; read < n_reads; read += n_waves) {    // (offsets: the window's first read's onwards)
         const long long first = offsets[read] - base, len = offsets[read + 1] - offsets[read];
@@ -317,29 +315,18 @@ pileup_spell_kernel(const uint32_t *__restrict__ counts, const uint32_t *__restr
 
 // one block: read_at[0, n_reads) (the lengths) -> their exclusive scan, in place; read_at[n_reads] = all bases,
 // read_at[n_reads + 1] = the inserted ones
-__global__ void __launch_bounds__(kPileupBlock)
+__global__ void __launch_bounds__(kPassBlock)
 pileup_scan_kernel(int n_reads, long long *__restrict__ read_at, const gact_read_corrected *__restrict__ reads)
 {
-    __shared__ long long s_len[kPileupBlock], s_ins[kPileupBlock];
     long long carry = 0, carry_ins = 0;
-    for (int base = 0; base < n_reads; base += kPileupBlock) {
+    for (int base = 0; base < n_reads; base += kPassBlock) {
         const int k = base + (int)threadIdx.x;
-        const long long own = k < n_reads ? read_at[k] : 0;
-        s_len[threadIdx.x] = own;
-        s_ins[threadIdx.x] = k < n_reads ? reads[k].inserted : 0;
-        __syncthreads();
-        for (int d = 1; d < kPileupBlock; d <<= 1) {
-            const long long a = (int)threadIdx.x >= d ? s_len[threadIdx.x - d] : 0;
-            const long long b = (int)threadIdx.x >= d ? s_ins[threadIdx.x - d] : 0;
-            __syncthreads();
-            s_len[threadIdx.x] += a;
-            s_ins[threadIdx.x] += b;
-            __syncthreads();
-        }
-        if (k < n_reads) read_at[k] = carry + s_len[threadIdx.x] - own;
-        carry += s_len[kPileupBlock - 1];
-        carry_ins += s_ins[kPileupBlock - 1];
-        __syncthreads();
+        long long own[2] = {0, 0}, before[2], total[2];
+        if (k < n_reads) { own[0] = read_at[k]; own[1] = reads[k].inserted; }  // (one branch: the loads fly together)
+        block_scan_step(own, before, total);
+        if (k < n_reads) read_at[k] = carry + before[0];
+        carry += total[0];
+        carry_ins += total[1];
     }
     if (threadIdx.x == 0) { read_at[n_reads] = carry; read_at[n_reads + 1] = carry_ins; }
 }
@@ -488,7 +475,7 @@ int gact_hip_pileup_add(gact_hip_engine *e, int slot, int32_t n_sel, const int32
             if (crc) return crc;
             const int32_t n = end - first;
             const int blocks = std::max(1, std::min((n + 3) / 4, 4096));
-            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(gact::kPileupBlock), 0, sl.stream, pb.cols.p, pb.col_off.p,
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(gact::kPassBlock), 0, sl.stream, pb.cols.p, pb.col_off.p,
                                pb.n_cols.p, pb.cands.p, pb.records.p, n, sn.d_rs, sn.d_qf, sn.d_qr, win);
             HIP_TRY(hipGetLastError());
             first = end;
@@ -526,13 +513,13 @@ int gact_hip_pileup_add(gact_hip_engine *e, int slot, int32_t n_sel, const int32
     return 0;
 }
 
-// the consensus bytes of the open window for min_depth, on `stream`; full: the blocks that fill the device
-static int pileup_launch_consensus(gact_hip_engine *e, hipStream_t stream, int32_t min_depth, size_t full)
+// the consensus bytes of the open window for min_depth, on `stream`
+static int pileup_launch_consensus(gact_hip_engine *e, hipStream_t stream, int32_t min_depth)
 {
     Pileup &pl = e->pileup;
     if (pl.positions <= 0) return 0;
-    const size_t want = ((size_t)pl.positions + gact::kPileupBlock - 1) / gact::kPileupBlock;
-    hipLaunchKernelGGL(gact::pileup_consensus_kernel, dim3((unsigned)std::min(want, full * 4)), dim3(gact::kPileupBlock), 0, stream,
+    const size_t want = lane_blocks((size_t)pl.positions).x;
+    hipLaunchKernelGGL(gact::pileup_consensus_kernel, dim3((unsigned)std::min(want, full_device_blocks(e) * 4)), dim3(gact::kPassBlock), 0, stream,
                        (const uint32_t *)pl.scratch.p, e->sets[GACT_SET_REF].d_raw + pl.base, (long long)pl.positions,
                        (uint32_t)min_depth, pl.scratch.p + pl.at_cons);
     HIP_TRY(hipGetLastError());
@@ -554,12 +541,10 @@ int gact_hip_pileup_finish(gact_hip_engine *e, int32_t min_depth, gact_pileup_co
     uint8_t *d_cons = ps.p + pl.at_cons;
     gact_read_pileup *d_reads = (gact_read_pileup *)(ps.p + pl.at_reads);
     const uint8_t *own = rs.d_raw + pl.base;
-    const size_t full = (size_t)std::max(1, e->prop.multiProcessorCount) * 8;              // eight waves on every SIMD
     if ((rc = ps.timer.start(stream, "pileup_finish"))) return rc;
-    if ((rc = pileup_launch_consensus(e, stream, min_depth, full))) return rc;
+    if ((rc = pileup_launch_consensus(e, stream, min_depth))) return rc;
     if (pl.n_reads > 0) {
-        const size_t want = ((size_t)pl.n_reads + gact::kPileupBlock / 64 - 1) / (gact::kPileupBlock / 64);
-        hipLaunchKernelGGL(gact::pileup_reads_kernel, dim3((unsigned)std::min(want, full)), dim3(gact::kPileupBlock), 0, stream, d_counts,
+        hipLaunchKernelGGL(gact::pileup_reads_kernel, wave_blocks(e, (size_t)pl.n_reads), dim3(gact::kPassBlock), 0, stream, d_counts,
                            own, d_cons, rs.d_offsets + pl.read_first, (long long)pl.base, pl.n_reads, (uint32_t)min_depth,
                            (const int32_t *)(ps.p + pl.at_aln), d_reads);
         HIP_TRY(hipGetLastError());
@@ -601,11 +586,9 @@ int gact_hip_pileup_corrected(gact_hip_engine *e, int32_t min_depth, gact_pileup
     long long *d_read_at = (long long *)(ps.p + pl.at_read_at);
     const uint8_t *own = rs.d_raw + pl.base;
     const int K = pl.ins_slots;
-    const size_t full = (size_t)std::max(1, e->prop.multiProcessorCount) * 8;              // eight waves on every SIMD
-    const size_t want = ((size_t)pl.n_reads + gact::kPileupBlock / 64 - 1) / (gact::kPileupBlock / 64);
-    const dim3 grid((unsigned)std::max((size_t)1, std::min(want, full))), block(gact::kPileupBlock);
+    const dim3 grid = wave_blocks(e, (size_t)pl.n_reads), block(gact::kPassBlock);
     if ((rc = ps.timer.start(stream, "pileup_corrected"))) return rc;
-    if ((rc = pileup_launch_consensus(e, stream, min_depth, full))) return rc;
+    if ((rc = pileup_launch_consensus(e, stream, min_depth))) return rc;
     if (pl.n_reads > 0) {
         hipLaunchKernelGGL(gact::pileup_spell_kernel<false>, grid, block, 0, stream, d_counts, d_ins, K, own, d_cons,
                            rs.d_offsets + pl.read_first, (long long)pl.base, pl.n_reads, (uint32_t)min_depth, d_read_at, d_reads,

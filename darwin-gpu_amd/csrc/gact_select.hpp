@@ -11,16 +11,12 @@
 // Records that were not emitted take no part.
 //
 // Three stages on the slot's stream, nothing on the host between them:
-//   1 select_insert_kernel   an open-addressing table of record indices (int32, kSelectEmpty = -1, a power of two >= 2 n
-//                            slots, linear probing).  A record claims an empty slot with atomicCAS, passes a slot of another
-//                            class, and at a slot of its own class replaces the holder only while it is better than the
-//                            holder.  A slot never becomes empty again and never changes its class, so every record of a class
-//                            ends at the same slot; the holder only ever gets better, so every CAS loop ends; nothing waits
-//                            for another wave.  The table holds indices, the class fields are read from the records, which
-//                            no kernel here writes.  Each record keeps the slot it ended at.
+//   1 select_insert_kernel   every emitted record into a best-holder table of record indices with >= 2 n slots, keyed by its
+//                            class (table_insert_best, gact_pass_device.hpp, which holds the argument); the class fields are
+//                            read from the records, which no kernel here writes.  Each record keeps the slot it ended at.
 //   2 select_flag_kernel     record i survives iff it is emitted and its slot holds i: one ballot per wave (kept: 64 flags in
 //                            one word), popcounts per wave, summed per block.
-//   3 select_scan_kernel     exclusive scan of the block counts, one block, a carry from chunk to chunk;
+//   3 select_scan_kernel     exclusive scan of the block counts, one block (block_scan_step);
 //     select_write_kernel    every block writes its survivors at its offset in index order.
 // Two levels on purpose: a single-pass scan has blocks spinning on other blocks' flags.  The list is ascending and the same on
 // every run, whichever order the atomics landed in: the winner of a class is decided by a total order, not by arrival.
@@ -31,28 +27,17 @@
 
 namespace gact {
 
-constexpr int kSelectBlock = 256;                 // four waves
-constexpr int kSelectEmpty = -1;
 constexpr int32_t kSelectMaxRecords = 1 << 30;    // (a slot position fits an int32)
-
-// murmur3's mixing of 32-bit words: ids that differ in one bit, high or low, part over the whole table
-__device__ inline uint32_t select_mix(uint32_t h, uint32_t k)
-{
-    k *= 0xcc9e2d51u; k = (k << 15) | (k >> 17); k *= 0x1b873593u;
-    h ^= k; h = (h << 13) | (h >> 19);
-    return h * 5u + 0xe6546b64u;
-}
 
 __device__ inline uint32_t select_hash(const gact_overlap &r, int mode)
 {
-    uint32_t h = select_mix(select_mix(select_mix(0x2545f491u, (uint32_t)r.ref_id), (uint32_t)r.query_id), (uint32_t)r.comp);
+    uint32_t h = hash_mix(hash_mix(hash_mix(kHashSeed, (uint32_t)r.ref_id), (uint32_t)r.query_id), (uint32_t)r.comp);
     if (mode == GACT_SELECT_EXACT) {
-        h = select_mix(select_mix(h, (uint32_t)r.ab), (uint32_t)r.ae);
-        h = select_mix(select_mix(h, (uint32_t)r.bb), (uint32_t)r.be);
-        h = select_mix(h, (uint32_t)r.score);
+        h = hash_mix(hash_mix(h, (uint32_t)r.ab), (uint32_t)r.ae);
+        h = hash_mix(hash_mix(h, (uint32_t)r.bb), (uint32_t)r.be);
+        h = hash_mix(h, (uint32_t)r.score);
     }
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return h;
+    return hash_final(h);
 }
 
 __device__ inline bool select_same_class(const gact_overlap &a, const gact_overlap &b, int mode)
@@ -74,99 +59,71 @@ __device__ inline bool select_better(int i, const gact_overlap &a, int j, const 
     return i < j;
 }
 
-__global__ void __launch_bounds__(kSelectBlock)
+__global__ void __launch_bounds__(kPassBlock)
 select_insert_kernel(const gact_overlap *__restrict__ rec, int n, int mode, int *table, uint32_t mask, int *__restrict__ pos)
 {
-    const int i = blockIdx.x * kSelectBlock + threadIdx.x;
+    const int i = blockIdx.x * kPassBlock + threadIdx.x;
     if (i >= n) return;
     const gact_overlap r = rec[i];
     if (!r.emitted) { pos[i] = -1; return; }
-    uint32_t s = select_hash(r, mode) & mask;
-    // (at most n of the >= 2 n slots are ever taken: an empty slot, or the class's own, comes up before the probe is round)
-    for (;;) {
-        int j = __hip_atomic_load(&table[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (j == kSelectEmpty) {
-            j = atomicCAS(&table[s], kSelectEmpty, i);
-            if (j == kSelectEmpty) break;                      // claimed
-        }
-        if (select_same_class(r, rec[j], mode)) {
-            // the holder is of this class for good; it is replaced only by a better record, so this ends
-            while (select_better(i, r, j, rec[j], mode)) {
-                const int seen = atomicCAS(&table[s], j, i);
-                if (seen == j) break;
-                j = seen;
-            }
-            break;
-        }
-        s = (s + 1) & mask;
-    }
-    pos[i] = (int)s;
+    pos[i] = (int)table_insert_best(table, mask, select_hash(r, mode), i,
+                                    [&](int j) { return select_same_class(r, rec[j], mode); },
+                                    [&](int j) { return select_better(i, r, j, rec[j], mode); });
 }
 
 // flags[w]: the ballot of wave w (records 64 w .. 64 w + 63); counts[b] / emitted[b]: survivors / emitted records of block b
-__global__ void __launch_bounds__(kSelectBlock)
+__global__ void __launch_bounds__(kPassBlock)
 select_flag_kernel(int n, const int *__restrict__ table, const int *__restrict__ pos, unsigned long long *__restrict__ flags,
                    int *__restrict__ counts, int *__restrict__ emitted)
 {
-    __shared__ int s_sel[kSelectBlock / 64], s_emit[kSelectBlock / 64];
-    const int i = blockIdx.x * kSelectBlock + threadIdx.x;
+    __shared__ int s_sel[kPassBlock / 64], s_emit[kPassBlock / 64];
+    const int i = blockIdx.x * kPassBlock + threadIdx.x;
     const int wave = threadIdx.x >> 6;
     const int p = i < n ? pos[i] : -1;
     const bool survives = p >= 0 && table[p] == i;
     const unsigned long long m_sel = __ballot(survives), m_emit = __ballot(p >= 0);
     if ((threadIdx.x & 63) == 0) {
-        flags[(size_t)blockIdx.x * (kSelectBlock / 64) + wave] = m_sel;
+        flags[(size_t)blockIdx.x * (kPassBlock / 64) + wave] = m_sel;
         s_sel[wave] = __popcll(m_sel);
         s_emit[wave] = __popcll(m_emit);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         int a = 0, b = 0;
-        for (int w = 0; w < kSelectBlock / 64; w++) { a += s_sel[w]; b += s_emit[w]; }
+        for (int w = 0; w < kPassBlock / 64; w++) { a += s_sel[w]; b += s_emit[w]; }
         counts[blockIdx.x] = a;
         emitted[blockIdx.x] = b;
     }
 }
 
 // one block: counts[0, nb) -> their exclusive scan, in place; totals[0] = survivors, totals[1] = emitted records
-__global__ void __launch_bounds__(kSelectBlock)
+__global__ void __launch_bounds__(kPassBlock)
 select_scan_kernel(int nb, int *__restrict__ counts, const int *__restrict__ emitted, int *__restrict__ totals)
 {
-    __shared__ int s_scan[kSelectBlock], s_emit[kSelectBlock];
-    int carry = 0, carry_emit = 0;
-    for (int base = 0; base < nb; base += kSelectBlock) {
+    long long carry = 0, carry_emit = 0;
+    for (int base = 0; base < nb; base += kPassBlock) {
         const int k = base + (int)threadIdx.x;
-        const int own = k < nb ? counts[k] : 0;
-        s_scan[threadIdx.x] = own;
-        s_emit[threadIdx.x] = k < nb ? emitted[k] : 0;
-        __syncthreads();
-        for (int d = 1; d < kSelectBlock; d <<= 1) {
-            const int a = (int)threadIdx.x >= d ? s_scan[threadIdx.x - d] : 0;
-            const int b = (int)threadIdx.x >= d ? s_emit[threadIdx.x - d] : 0;
-            __syncthreads();
-            s_scan[threadIdx.x] += a;
-            s_emit[threadIdx.x] += b;
-            __syncthreads();
-        }
-        if (k < nb) counts[k] = carry + s_scan[threadIdx.x] - own;
-        carry += s_scan[kSelectBlock - 1];
-        carry_emit += s_emit[kSelectBlock - 1];
-        __syncthreads();
+        long long own[2] = {0, 0}, before[2], total[2];
+        if (k < nb) { own[0] = counts[k]; own[1] = emitted[k]; }              // (one branch: the loads fly together)
+        block_scan_step(own, before, total);
+        if (k < nb) counts[k] = (int)(carry + before[0]);
+        carry += total[0];
+        carry_emit += total[1];
     }
-    if (threadIdx.x == 0) { totals[0] = carry; totals[1] = carry_emit; }
+    if (threadIdx.x == 0) { totals[0] = (int)carry; totals[1] = (int)carry_emit; }
 }
 
 // sel[offsets[b] + rank of i among block b's survivors] = i: ascending, since the offsets and the ranks are
-__global__ void __launch_bounds__(kSelectBlock)
+__global__ void __launch_bounds__(kPassBlock)
 select_write_kernel(const unsigned long long *__restrict__ flags, const int *__restrict__ offsets, int *__restrict__ sel)
 {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const unsigned long long *f = flags + (size_t)blockIdx.x * (kSelectBlock / 64);
+    const unsigned long long *f = flags + (size_t)blockIdx.x * (kPassBlock / 64);
     const unsigned long long mine = f[wave];
     if (!((mine >> lane) & 1)) return;
     int at = offsets[blockIdx.x] + __popcll(mine & ((1ull << lane) - 1));
     for (int w = 0; w < wave; w++) at += __popcll(f[w]);
-    sel[at] = blockIdx.x * kSelectBlock + (int)threadIdx.x;
+    sel[at] = blockIdx.x * kPassBlock + (int)threadIdx.x;
 }
 
 }  // namespace gact
@@ -192,11 +149,11 @@ int gact_hip_select_overlaps(gact_hip_engine *e, int slot, int32_t n, const gact
     PassScratch<gact_select_stats> &sb = sl.select;
     size_t slots = 2;
     while (slots < 2 * (size_t)n) slots <<= 1;
-    const size_t nb = ((size_t)n + gact::kSelectBlock - 1) / gact::kSelectBlock;
+    const size_t nb = ((size_t)n + gact::kPassBlock - 1) / gact::kPassBlock;
     const size_t at_table = records ? up16((size_t)n * sizeof(gact_overlap)) : 0;
     const size_t at_pos = at_table + slots * sizeof(int);
     const size_t at_flags = up16(at_pos + (size_t)n * sizeof(int));
-    const size_t at_counts = at_flags + nb * (gact::kSelectBlock / 64) * sizeof(unsigned long long);
+    const size_t at_counts = at_flags + nb * (gact::kPassBlock / 64) * sizeof(unsigned long long);
     const size_t at_sel = up16(at_counts + (2 * nb + 2) * sizeof(int));
     const size_t bytes = at_sel + (size_t)n * sizeof(int);
     if (sb.reserve(bytes)) return fail(GACT_HIP_ENOMEM, "select_overlaps: device allocation failed (%d records, %zu bytes)", n, bytes);
@@ -208,8 +165,8 @@ int gact_hip_select_overlaps(gact_hip_engine *e, int slot, int32_t n, const gact
     DevRecords in;
     if ((rc = slot_records_stage(sl, sb.p, n, records, n, nullptr, 0, nullptr, 0, in))) return rc;
     const gact_overlap *d_rec = in.rec;
-    HIP_TRY(hipMemsetAsync(d_table, 0xff, slots * sizeof(int), sl.stream));          // kSelectEmpty everywhere
-    const dim3 grid((unsigned)nb), block(gact::kSelectBlock);
+    HIP_TRY(hipMemsetAsync(d_table, 0xff, slots * sizeof(int), sl.stream));          // kTableEmpty everywhere
+    const dim3 grid((unsigned)nb), block(gact::kPassBlock);
     hipLaunchKernelGGL(gact::select_insert_kernel, grid, block, 0, sl.stream, d_rec, n, mode, d_table, (uint32_t)(slots - 1), d_pos);
     hipLaunchKernelGGL(gact::select_flag_kernel, grid, block, 0, sl.stream, n, d_table, d_pos, d_flags, d_counts, d_emitted);
     hipLaunchKernelGGL(gact::select_scan_kernel, dim3(1), block, 0, sl.stream, (int)nb, d_counts, d_emitted, d_totals);

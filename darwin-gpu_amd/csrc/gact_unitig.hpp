@@ -25,8 +25,8 @@
 //   unitig_recount_kernel  one lane per arc: the out-degrees of E1 = E0 without the arcs that touch a cut read
 //   unitig_heads_kernel    one lane per vertex: an emitted head (x == ptr[x] < ptr[x^1]) leaves 1, its read count and its length
 //                          (through its tail's record), every other vertex zeros; the longest and the circular ones counted
-//   unitig_scan_kernel     one block, in place, carries from chunk to chunk as graph_scan_kernel (shuffles inside a wave, LDS
-//                          across the four waves): the exclusive scans of the three over the vertex ids, in 64 bits, and their totals
+//   unitig_scan_kernel     one block, in place (block_scan_step): the exclusive scans of the three over the vertex ids, and
+//                          their totals
 //   unitig_fill_kernel     one lane per vertex: the entry and the place of a vertex of an emitted chain, the gact_unitig by the
 //                          tail's lane, the place of a read that is not placed by its even vertex's lane
 //   unitig_bases_kernel    one wave per layout entry, grid-stride; lanes stride over the entry's take: a forward entry reads
@@ -41,7 +41,6 @@
 
 namespace gact {
 
-constexpr int kUnitigBlock = 256;                          // four waves
 constexpr int32_t kUnitigMaxReads = 1 << 30;               // (a vertex 2 i + 1 fits an int32)
 constexpr int64_t kUnitigMaxArcs = 1 << 29;
 // bits of the flag word
@@ -73,10 +72,10 @@ __device__ inline bool unitig_live(const gact_graph_read *__restrict__ reads, co
     return reads[i].contained_by < 0 && cl > 0;
 }
 
-__global__ void __launch_bounds__(kUnitigBlock)
+__global__ void __launch_bounds__(kPassBlock)
 unitig_first_kernel(int nv, const gact_graph_arc *__restrict__ arcs, int n_arcs, int *__restrict__ first)
 {
-    const int x = blockIdx.x * kUnitigBlock + threadIdx.x;
+    const int x = blockIdx.x * kPassBlock + threadIdx.x;
     if (x > nv) return;
     int lo = 0, hi = n_arcs;                               // the first arc with u >= x
     while (lo < hi) {
@@ -86,12 +85,12 @@ unitig_first_kernel(int nv, const gact_graph_arc *__restrict__ arcs, int n_arcs,
     first[x] = lo;
 }
 
-__global__ void __launch_bounds__(kUnitigBlock)
+__global__ void __launch_bounds__(kPassBlock)
 unitig_check_kernel(int nv, const gact_graph_arc *__restrict__ arcs, int n_arcs, const int *__restrict__ first,
                     const gact_graph_read *__restrict__ reads, const int *__restrict__ lens, const int *__restrict__ clip,
                     int want_bases, int *out, unsigned long long *counters, int *flag)
 {
-    const int k = blockIdx.x * kUnitigBlock + threadIdx.x;
+    const int k = blockIdx.x * kPassBlock + threadIdx.x;
     bool e0 = false;
     if (k < n_arcs) {
         const gact_graph_arc a = arcs[k];
@@ -120,8 +119,7 @@ unitig_check_kernel(int nv, const gact_graph_arc *__restrict__ arcs, int n_arcs,
         }
         if (bad) atomicOr(flag, bad);
     }
-    const unsigned long long m = __ballot(e0);
-    if (m && (threadIdx.x & 63) == 0) atomicAdd(&counters[kUnitigE0], (unsigned long long)__popcll(m));
+    wave_count(&counters[kUnitigE0], e0);
 }
 
 // the arc is of the current set: E0, or E1 where cut is given
@@ -130,50 +128,46 @@ __device__ inline bool unitig_in_set(const gact_graph_arc &a, const int *__restr
     return a.flags == 0 && (!cut || (!cut[a.u >> 1] && !cut[a.v >> 1]));
 }
 
-__global__ void __launch_bounds__(kUnitigBlock)
+__global__ void __launch_bounds__(kPassBlock)
 unitig_recount_kernel(const gact_graph_arc *__restrict__ arcs, int n_arcs, const int *__restrict__ cut, int *out,
                       unsigned long long *counters, const int *__restrict__ flag)
 {
     if (*flag) return;
-    const int k = blockIdx.x * kUnitigBlock + threadIdx.x;
+    const int k = blockIdx.x * kPassBlock + threadIdx.x;
     bool in = false;
     if (k < n_arcs) {
         const gact_graph_arc a = arcs[k];
         in = unitig_in_set(a, cut);
         if (in) atomicAdd(&out[a.u], 1);
     }
-    const unsigned long long m = __ballot(in);
-    if (m && (threadIdx.x & 63) == 0) atomicAdd(&counters[kUnitigE1], (unsigned long long)__popcll(m));
+    wave_count(&counters[kUnitigE1], in);
 }
 
-__global__ void __launch_bounds__(kUnitigBlock)
+__global__ void __launch_bounds__(kPassBlock)
 unitig_links_kernel(const gact_graph_arc *__restrict__ arcs, int n_arcs, const int *__restrict__ cut, const int *__restrict__ out,
                     int *__restrict__ prev, int *__restrict__ len_in, int *__restrict__ len_out, unsigned long long *counters,
                     const int *__restrict__ flag)
 {
     if (*flag) return;
-    const int k = blockIdx.x * kUnitigBlock + threadIdx.x;
+    const int k = blockIdx.x * kPassBlock + threadIdx.x;
     bool join = false;
     if (k < n_arcs) {
         const gact_graph_arc a = arcs[k];
         join = unitig_in_set(a, cut) && out[a.u] == 1 && out[a.v ^ 1] == 1;
         if (join) { prev[a.v] = a.u; len_in[a.v] = a.len; len_out[a.u] = a.len; }
     }
-    if (counters) {
-        const unsigned long long m = __ballot(join);
-        if (m && (threadIdx.x & 63) == 0) atomicAdd(&counters[kUnitigJoins], (unsigned long long)__popcll(m));
-    }
+    if (counters) wave_count(&counters[kUnitigJoins], join);
 }
 
 // found: NULL, or the records the sweep in front left: a vertex on a cycle that is the cycle's place to open becomes a head,
 // and closing[x] gets the length of the join cut in front of it (0: none).  The cycle that holds the lowest id m of itself and
 // its complement (low < low_c) opens in front of m; its complement opens behind m^1, in front of the vertex whose prev is m^1
-__global__ void __launch_bounds__(kUnitigBlock)
+__global__ void __launch_bounds__(kPassBlock)
 unitig_init_kernel(int nv, const int *__restrict__ prev, const int *__restrict__ len_in, const UnitigRank *__restrict__ found,
                    int *__restrict__ closing, UnitigRank *__restrict__ rank, const int *__restrict__ flag)
 {
     if (*flag) return;
-    const int x = blockIdx.x * kUnitigBlock + threadIdx.x;
+    const int x = blockIdx.x * kPassBlock + threadIdx.x;
     if (x >= nv) return;
     int p = prev[x];
     if (found) {
@@ -191,11 +185,11 @@ unitig_init_kernel(int nv, const int *__restrict__ prev, const int *__restrict__
     rank[x] = r;
 }
 
-__global__ void __launch_bounds__(kUnitigBlock)
+__global__ void __launch_bounds__(kPassBlock)
 unitig_jump_kernel(int nv, const UnitigRank *__restrict__ from, UnitigRank *__restrict__ to, const int *__restrict__ flag)
 {
     if (*flag) return;
-    const int x = blockIdx.x * kUnitigBlock + threadIdx.x;
+    const int x = blockIdx.x * kPassBlock + threadIdx.x;
     if (x >= nv) return;
     UnitigRank r = from[x];
     const UnitigRank p = from[r.ptr];
@@ -207,13 +201,13 @@ unitig_jump_kernel(int nv, const UnitigRank *__restrict__ from, UnitigRank *__re
     to[x] = r;
 }
 
-__global__ void __launch_bounds__(kUnitigBlock)
+__global__ void __launch_bounds__(kPassBlock)
 unitig_tip_kernel(int n_reads, const gact_graph_read *__restrict__ reads, const int *__restrict__ lens, const int *__restrict__ clip,
                   const int *__restrict__ prev, const int *__restrict__ out, const UnitigRank *__restrict__ rank, int tip_reads,
                   int *__restrict__ cut, unsigned long long *counters, const int *__restrict__ flag)
 {
     if (*flag) return;
-    const int i = blockIdx.x * kUnitigBlock + threadIdx.x;
+    const int i = blockIdx.x * kPassBlock + threadIdx.x;
     bool tip = false, inside = false;
     if (i < n_reads) {
         inside = reads[i].contained_by >= 0;
@@ -224,11 +218,8 @@ unitig_tip_kernel(int n_reads, const gact_graph_read *__restrict__ reads, const 
         }
         cut[i] = tip;
     }
-    const unsigned long long m = __ballot(tip), mc = __ballot(inside);
-    if ((threadIdx.x & 63) == 0) {
-        if (m) atomicAdd(&counters[kUnitigCut], (unsigned long long)__popcll(m));
-        if (mc) atomicAdd(&counters[kUnitigContained], (unsigned long long)__popcll(mc));
-    }
+    wave_count(&counters[kUnitigCut], tip);
+    wave_count(&counters[kUnitigContained], inside);
 }
 
 // is x the head of a chain that is emitted?  and then its tail, read count, length and circular flag
@@ -251,14 +242,14 @@ __device__ inline bool unitig_emitted_head(int x, const gact_graph_read *__restr
 
 // one lane per vertex: an emitted head leaves (1, its reads, its length) in (number, layout_at, seq_at), every other vertex
 // zeros: what the scan sums.  The longest unitig and the circular ones go to the counters, once per wave
-__global__ void __launch_bounds__(kUnitigBlock)
+__global__ void __launch_bounds__(kPassBlock)
 unitig_heads_kernel(int nv, const gact_graph_read *__restrict__ reads, const int *__restrict__ lens, const int *__restrict__ clip,
                     const int *__restrict__ cut, const UnitigRank *__restrict__ rank, const int *__restrict__ closing,
                     int *__restrict__ number, long long *__restrict__ layout_at, long long *__restrict__ seq_at,
                     unsigned long long *counters, const int *__restrict__ flag)
 {
     if (*flag) return;
-    const int x = blockIdx.x * kUnitigBlock + threadIdx.x;
+    const int x = blockIdx.x * kPassBlock + threadIdx.x;
     int head = 0, tail, n = 0, circular = 0;
     long long length = 0;
     if (x < nv && unitig_emitted_head(x, reads, lens, clip, cut, rank, closing, tail, n, length, circular)) head = 1;
@@ -270,57 +261,36 @@ unitig_heads_kernel(int nv, const gact_graph_read *__restrict__ reads, const int
         most_reads = max(most_reads, __shfl_xor(most_reads, o));
         most_bases = max(most_bases, __shfl_xor(most_bases, o));
     }
-    const unsigned long long m = __ballot(circular != 0);
     if ((threadIdx.x & 63) == 0) {
         if (most_reads) atomicMax(&counters[kUnitigLongestReads], (unsigned long long)most_reads);
         if (most_bases) atomicMax(&counters[kUnitigLongestBases], (unsigned long long)most_bases);
-        if (m) atomicAdd(&counters[kUnitigCircular], (unsigned long long)__popcll(m));
     }
+    wave_count(&counters[kUnitigCircular], circular != 0);
 }
 
-// one block, in place: the exclusive scans of number, layout_at and seq_at over the vertex ids, and their totals.  A carry from
-// chunk to chunk as in graph_scan_kernel; inside a chunk shuffles scan a wave and LDS adds the waves in front: two barriers
-__global__ void __launch_bounds__(kUnitigBlock)
+// one block, in place: the exclusive scans of number, layout_at and seq_at over the vertex ids, and their totals
+__global__ void __launch_bounds__(kPassBlock)
 unitig_scan_kernel(int nv, int *__restrict__ number, long long *__restrict__ layout_at, long long *__restrict__ seq_at,
                    UnitigTotals *totals, const int *__restrict__ flag)
 {
     if (*flag) return;
-    __shared__ int s_heads[kUnitigBlock / 64];                   // what each of the block's waves adds
-    __shared__ long long s_reads[kUnitigBlock / 64], s_bases[kUnitigBlock / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int c_heads = 0;
-    long long c_reads = 0, c_bases = 0;
-    for (int base = 0; base < nv; base += kUnitigBlock) {
+    long long carry[3] = {0, 0, 0};                             // heads, reads, bases
+    for (int base = 0; base < nv; base += kPassBlock) {
         const int x = base + (int)threadIdx.x;
-        const int head = x < nv ? number[x] : 0;
-        const long long n = x < nv ? layout_at[x] : 0, length = x < nv ? seq_at[x] : 0;
-        int a = head;
-        long long b = n, c = length;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int ua = __shfl_up(a, d);
-            const long long ub = __shfl_up(b, d), uc = __shfl_up(c, d);
-            if (lane >= d) { a += ua; b += ub; c += uc; }
-        }
-        if (lane == 63) { s_heads[wave] = a; s_reads[wave] = b; s_bases[wave] = c; }
-        __syncthreads();
-        int t_heads = 0;
-        long long t_reads = 0, t_bases = 0;
-        for (int w = 0; w < kUnitigBlock / 64; w++) {
-            if (w == wave) { a += t_heads; b += t_reads; c += t_bases; }
-            t_heads += s_heads[w]; t_reads += s_reads[w]; t_bases += s_bases[w];
-        }
+        long long own[3] = {0, 0, 0}, before[3], total[3];
+        if (x < nv) { own[0] = number[x]; own[1] = layout_at[x]; own[2] = seq_at[x]; }     // (one branch: the loads fly together)
+        block_scan_step(own, before, total);
         if (x < nv) {
-            number[x] = c_heads + a - head;
-            layout_at[x] = c_reads + b - n;
-            seq_at[x] = c_bases + c - length;
+            number[x] = (int)(carry[0] + before[0]);
+            layout_at[x] = carry[1] + before[1];
+            seq_at[x] = carry[2] + before[2];
         }
-        c_heads += t_heads; c_reads += t_reads; c_bases += t_bases;
-        __syncthreads();
+        for (int i = 0; i < 3; i++) carry[i] += total[i];
     }
-    if (threadIdx.x == 0) { totals->unitigs = c_heads; totals->placed = c_reads; totals->length = c_bases; }
+    if (threadIdx.x == 0) { totals->unitigs = carry[0]; totals->placed = carry[1]; totals->length = carry[2]; }
 }
 
-__global__ void __launch_bounds__(kUnitigBlock)
+__global__ void __launch_bounds__(kPassBlock)
 unitig_fill_kernel(int nv, const gact_graph_read *__restrict__ reads, const int *__restrict__ lens, const int *__restrict__ clip,
                    const int *__restrict__ cut, const UnitigRank *__restrict__ rank, const int *__restrict__ closing,
                    const int *__restrict__ len_out, const int *__restrict__ number, const long long *__restrict__ layout_at,
@@ -328,7 +298,7 @@ unitig_fill_kernel(int nv, const gact_graph_read *__restrict__ reads, const int 
                    gact_unitig_place *__restrict__ places, const int *__restrict__ flag)
 {
     if (*flag) return;
-    const int x = blockIdx.x * kUnitigBlock + threadIdx.x;
+    const int x = blockIdx.x * kPassBlock + threadIdx.x;
     if (x >= nv) return;
     const int i = x >> 1;
     const bool live = unitig_live(reads, lens, clip, i);
@@ -375,7 +345,7 @@ __device__ inline uint8_t unitig_complement(uint8_t b)       // (revcomp_kernel'
     }
 }
 
-__global__ void __launch_bounds__(kUnitigBlock)
+__global__ void __launch_bounds__(kPassBlock)
 unitig_bases_kernel(const UnitigTotals *__restrict__ totals, const gact_unitig_entry *__restrict__ layout,
                     const gact_unitig_place *__restrict__ places, const gact_unitig *__restrict__ unitigs,
                     const uint8_t *__restrict__ raw, const int64_t *__restrict__ offsets, const int *__restrict__ lens,
@@ -383,7 +353,7 @@ unitig_bases_kernel(const UnitigTotals *__restrict__ totals, const gact_unitig_e
 {
     if (*flag) return;
     const int lane = threadIdx.x & 63;
-    const long long wave = (long long)blockIdx.x * (kUnitigBlock / 64) + (threadIdx.x >> 6), n_waves = (long long)gridDim.x * (kUnitigBlock / 64);
+    const long long wave = (long long)blockIdx.x * (kPassBlock / 64) + (threadIdx.x >> 6), n_waves = (long long)gridDim.x * (kPassBlock / 64);
     const long long n = totals->placed;
     for (long long e = wave; e < n; e += n_waves) {
         const gact_unitig_entry en = layout[e];
@@ -422,14 +392,8 @@ int gact_hip_unitigs(gact_hip_engine *e, int slot, int32_t n_reads, const int32_
         (seq && seq_cap < 0))
         return fail(GACT_HIP_EINVAL, "unitigs: bad arguments (n_reads = %d, at most %d; n_arcs = %lld, at most %lld; seq_cap = %lld)",
                     n_reads, gact::kUnitigMaxReads, (long long)n_arcs, (long long)gact::kUnitigMaxArcs, (long long)seq_cap);
-    int64_t clipped = 0;
-    for (int32_t i = 0; i < n_reads; i++) {
-        if (read_lens[i] < 0) return fail(GACT_HIP_EINVAL, "unitigs: read %d has the negative length %d", i, read_lens[i]);
-        if (clip && !(0 <= clip[2 * (size_t)i] && clip[2 * (size_t)i] <= clip[2 * (size_t)i + 1] && clip[2 * (size_t)i + 1] <= read_lens[i]))
-            return fail(GACT_HIP_EINVAL, "unitigs: the clip [%d, %d) of read %d is not inside [0, %d]", clip[2 * (size_t)i],
-                        clip[2 * (size_t)i + 1], i, read_lens[i]);
-        clipped += clip ? clip[2 * (size_t)i + 1] - clip[2 * (size_t)i] : read_lens[i];
-    }
+    const int64_t clipped = check_read_lens("unitigs", n_reads, read_lens, clip);
+    if (clipped < 0) return GACT_HIP_EINVAL;
     const SeqSet &rs = e->sets[GACT_SET_REF];
     if (seq) {
         if (rs.n == 0 || !rs.d_raw) return fail(GACT_HIP_EINVAL, "unitigs: bases asked for while GACT_SET_REF is not uploaded");
@@ -497,8 +461,7 @@ int gact_hip_unitigs(gact_hip_engine *e, int slot, int32_t n_reads, const int32_
     HIP_TRY(hipMemcpyAsync(d_lens, read_lens, n * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
     if (clip) HIP_TRY(hipMemcpyAsync(ub.p + at_clip, clip, nv * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(hipMemsetAsync(d_out0, 0, at_first - at_out0, sl.stream));
-    const dim3 block(gact::kUnitigBlock);
-    auto blocks = [](size_t lanes) { return dim3((unsigned)((std::max(lanes, (size_t)1) + gact::kUnitigBlock - 1) / gact::kUnitigBlock)); };
+    const dim3 block(gact::kPassBlock);
     int rounds = 1;
     while (((size_t)1 << rounds) < nv) rounds++;
     const int n_a = (int)n_arcs, i_nv = (int)nv;
@@ -507,37 +470,34 @@ int gact_hip_unitigs(gact_hip_engine *e, int slot, int32_t n_reads, const int32_
     auto sweep = [&](const int *cut, const int *out, const gact::UnitigRank *found, bool count) -> gact::UnitigRank * {
         if (!found) {
             (void)hipMemsetAsync(d_prev, 0xff, nv * sizeof(int), sl.stream);
-            hipLaunchKernelGGL(gact::unitig_links_kernel, blocks(na), block, 0, sl.stream, d_arcs, n_a, cut, out, d_prev, d_len_in, d_len_out,
+            hipLaunchKernelGGL(gact::unitig_links_kernel, lane_blocks(na), block, 0, sl.stream, d_arcs, n_a, cut, out, d_prev, d_len_in, d_len_out,
                                count ? d_counters : nullptr, d_flag);
         }
         const int at = found == d_rank[0] ? 1 : 0;             // (the records of the sweep in front are read while these are made)
-        hipLaunchKernelGGL(gact::unitig_init_kernel, blocks(nv), block, 0, sl.stream, i_nv, d_prev, d_len_in, found, d_closing, d_rank[at],
+        hipLaunchKernelGGL(gact::unitig_init_kernel, lane_blocks(nv), block, 0, sl.stream, i_nv, d_prev, d_len_in, found, d_closing, d_rank[at],
                            d_flag);
         int cur = at;
         for (int r = 0; r < rounds; r++, cur ^= 1, launches++)
-            hipLaunchKernelGGL(gact::unitig_jump_kernel, blocks(nv), block, 0, sl.stream, i_nv, d_rank[cur], d_rank[cur ^ 1], d_flag);
+            hipLaunchKernelGGL(gact::unitig_jump_kernel, lane_blocks(nv), block, 0, sl.stream, i_nv, d_rank[cur], d_rank[cur ^ 1], d_flag);
         return d_rank[cur];
     };
-    hipLaunchKernelGGL(gact::unitig_first_kernel, blocks(nv + 1), block, 0, sl.stream, i_nv, d_arcs, n_a, d_first);
-    hipLaunchKernelGGL(gact::unitig_check_kernel, blocks(na), block, 0, sl.stream, i_nv, d_arcs, n_a, d_first, d_reads, d_lens, d_clip,
+    hipLaunchKernelGGL(gact::unitig_first_kernel, lane_blocks(nv + 1), block, 0, sl.stream, i_nv, d_arcs, n_a, d_first);
+    hipLaunchKernelGGL(gact::unitig_check_kernel, lane_blocks(na), block, 0, sl.stream, i_nv, d_arcs, n_a, d_first, d_reads, d_lens, d_clip,
                        seq ? 1 : 0, d_out0, d_counters, d_flag);
     const gact::UnitigRank *on_e0 = sweep(nullptr, d_out0, nullptr, false);
-    hipLaunchKernelGGL(gact::unitig_tip_kernel, blocks(n), block, 0, sl.stream, n_reads, d_reads, d_lens, d_clip, d_prev, d_out0, on_e0,
+    hipLaunchKernelGGL(gact::unitig_tip_kernel, lane_blocks(n), block, 0, sl.stream, n_reads, d_reads, d_lens, d_clip, d_prev, d_out0, on_e0,
                        p.tip_reads, d_cut, d_counters, d_flag);
-    hipLaunchKernelGGL(gact::unitig_recount_kernel, blocks(na), block, 0, sl.stream, d_arcs, n_a, d_cut, d_out1, d_counters, d_flag);
+    hipLaunchKernelGGL(gact::unitig_recount_kernel, lane_blocks(na), block, 0, sl.stream, d_arcs, n_a, d_cut, d_out1, d_counters, d_flag);
     const gact::UnitigRank *cycles = sweep(d_cut, d_out1, nullptr, true);
     const gact::UnitigRank *ranks = sweep(d_cut, d_out1, cycles, false);
-    hipLaunchKernelGGL(gact::unitig_heads_kernel, blocks(nv), block, 0, sl.stream, i_nv, d_reads, d_lens, d_clip, d_cut, ranks, d_closing,
+    hipLaunchKernelGGL(gact::unitig_heads_kernel, lane_blocks(nv), block, 0, sl.stream, i_nv, d_reads, d_lens, d_clip, d_cut, ranks, d_closing,
                        d_number, d_layout_at, d_seq_at, d_counters, d_flag);
     hipLaunchKernelGGL(gact::unitig_scan_kernel, dim3(1), block, 0, sl.stream, i_nv, d_number, d_layout_at, d_seq_at, d_totals, d_flag);
-    hipLaunchKernelGGL(gact::unitig_fill_kernel, blocks(nv), block, 0, sl.stream, i_nv, d_reads, d_lens, d_clip, d_cut, ranks, d_closing,
+    hipLaunchKernelGGL(gact::unitig_fill_kernel, lane_blocks(nv), block, 0, sl.stream, i_nv, d_reads, d_lens, d_clip, d_cut, ranks, d_closing,
                        d_len_out, d_number, d_layout_at, d_seq_at, d_unitigs, d_layout, d_places, d_flag);
-    if (seq) {
-        const size_t want_blocks = (n + gact::kUnitigBlock / 64 - 1) / (gact::kUnitigBlock / 64);
-        const dim3 wave_grid((unsigned)std::min(want_blocks, (size_t)std::max(1, e->prop.multiProcessorCount) * 8));
-        hipLaunchKernelGGL(gact::unitig_bases_kernel, wave_grid, block, 0, sl.stream, d_totals, d_layout, d_places, d_unitigs, rs.d_raw,
-                           rs.d_offsets, d_lens, d_clip, d_seq, d_flag);
-    }
+    if (seq)
+        hipLaunchKernelGGL(gact::unitig_bases_kernel, wave_blocks(e, n), block, 0, sl.stream, d_totals, d_layout, d_places, d_unitigs,
+                           rs.d_raw, rs.d_offsets, d_lens, d_clip, d_seq, d_flag);
     HIP_TRY(hipGetLastError());
     // the one wait: the flag word, the number of unitigs and the total length, before the copies out
     int flag = 0;

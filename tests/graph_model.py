@@ -13,7 +13,7 @@ from gact_amd import engine
 NONE, SELF, DROPPED, INTERNAL, QUERY_CONTAINED, TARGET_CONTAINED, SHORT, DOVETAIL = range(8)
 DEFAULTS = dict(max_hang=1000, int_permille=800, min_ovlp=1000, fuzz=1000)
 PATTERNS = ("tiling", "contained", "mutual", "internal", "thresholds", "clip", "sums", "duplicates", "both_strands", "self",
-            "not_emitted", "sel", "disagree", "hub", "blocks257", "blocks513", "many_reads", "random", "empty")
+            "not_emitted", "sel", "disagree", "hub", "blocks257", "blocks513", "many_reads", "random", "empty", "tiling128", "tiling129")
 
 
 def classify(rec, k, i, lens, clip, sums, p):
@@ -343,6 +343,11 @@ def crafted(pattern, seed=20261019):
     elif pattern == "empty":
         layout = _random_layout(rng, 30, 20000, 3000, 7000)
         rows = [r[:8] + (0,) for r in layout_records(layout)]
+    elif pattern in ("tiling128", "tiling129"):
+        # the tiling with 128 and with 129 reads, strands at random: the 256 vertices of the one are the last that one chunk of
+        # the degree scan holds, the last two of the other's 258 are the first that lie behind its carry
+        layout = [(2000 * i, 5000, int(rng.integers(0, 2))) for i in range(int(pattern[6:]))]
+        rows = [layout_row(layout, t, q) for t in range(len(layout)) for q in range(max(0, t - 2), min(len(layout), t + 3)) if t != q]
     else:
         raise ValueError(pattern)
     return _noise(rng, records_of(rows)), np.array([ln for _, ln, _ in layout], dtype=np.int32), kw

@@ -316,6 +316,63 @@ def test_a_window_gives_the_full_windows_slice():
     eng.close()
 
 
+FILLERS = 260                                           # reads in front of the aligned ones: more than one chunk of pileup_scan_kernel (256)
+
+
+def _fillers(n, seed=20261021):
+    """n reads of 64 to 100 random bases"""
+    from gact_amd import synth
+    rng = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    rs = synth.ReadSet()
+    for k in range(n):
+        rs.reads.append(acgt[rng.integers(0, 4, int(rng.integers(64, 101)))])
+        rs.names.append("F%d" % k)
+    return rs
+
+
+def test_aligned_reads_behind_a_chunk_of_unaligned_ones_equal_the_model():
+    """pileup_scan_kernel takes 256 reads a chunk and carries the bases and the inserted bases on: here every read with an
+    alignment lies in the second chunk, behind 260 short reads that nothing aligns to"""
+    from conftest import workload_block
+    blk = workload_block("tiny")
+    rs = _fillers(FILLERS)
+    rs.reads += list(blk.rs.reads)
+    rs.names += list(blk.rs.names)
+    cf, cr = blk.cf.copy(), blk.cr.copy()
+    for c in (cf, cr):
+        c["ref_id"] += FILLERS
+        c["query_id"] += FILLERS
+    assert 256 < FILLERS < len(rs.reads) <= 512 and len(cf) > 0 and len(cr) > 0
+    eng, n, nf = engine_with(rs, cf, cr)
+    records, paths, ops = eng.candidates_paths(n=n, rc_from=nf)
+    eng.pileup_begin(ins_slots=2)
+    eng.pileup_add(n=n, rc_from=nf)
+    got = eng.pileup_corrected(min_depth=2, ins=True)
+    st = eng.last_pileup_ins_stats()
+    eng.close()
+    want = _model(rs, records, paths, ops, 2, min_depth=2)
+    table, read_at = want[1], want[2]
+    assert int(table["inserted"][FILLERS:].sum()) > 0 and not table["inserted"][:FILLERS].any() and read_at[256] > 0
+    _same(got, want)
+    assert st["emitted"] == int(table["inserted"].sum())
+
+
+def test_a_window_of_513_reads_with_no_add_gives_the_reads_back():
+    """two full chunks of the scan and one read in a third"""
+    from gact_amd import engine
+    rs = _fillers(513, seed=20261022)
+    none = np.zeros(0, dtype=engine.CAND_DTYPE)
+    eng, _, _ = engine_with(rs, none, none, slots=())
+    eng.pileup_begin(ins_slots=2)
+    reads, read_at, seq, ins = eng.pileup_corrected(min_depth=1, ins=True)
+    st = eng.last_pileup_ins_stats()
+    eng.close()
+    cat, offs = rs.concat()
+    assert len(read_at) == 514 and np.array_equal(read_at, offs) and seq == cat.tobytes()
+    assert np.array_equal(reads["length"], np.diff(offs)) and not reads["inserted"].any() and not ins.any() and st["emitted"] == 0
+
+
 def test_no_slots_the_room_protocol_and_the_refusals():
     import ctypes
     from gact_amd import engine

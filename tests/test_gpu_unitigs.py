@@ -101,6 +101,18 @@ def test_chains_with_shuffled_ids(eng, name, tip_reads):
         assert (want["places"]["orient"] == 0).all() and (_graph_of(name)[2]["u"][::2] & 1).any()    # emitted: the complement
 
 
+@pytest.mark.parametrize("tip_reads", [0, 3])
+@pytest.mark.parametrize("name", ["tiling128", "tiling129"])
+def test_tilings_that_end_with_the_scans_chunk_and_one_read_behind_it(eng, name, tip_reads):
+    """256 vertices: the last full chunk of unitig_scan_kernel; 258: the first carry, read by the head of read 128's unitig"""
+    want = _check(eng, name, tip_reads)
+    n = len(_graph_of(name)[0])
+    u = want["unitigs"]
+    assert len(u) == (25 if tip_reads else n - 102) and want["counts"]["cut"] == (n - 125 if tip_reads else 0)
+    if (n, tip_reads) == (129, 0):
+        assert u["first"][-1] == 256 and u["layout_at"][-1] == 128 and u["seq_at"][-1] == u["length"][:-1].sum() > 0
+
+
 @pytest.mark.parametrize("tip_reads", [0, 1, 3])
 @pytest.mark.parametrize("name", ["fork", "two_tips", "tip_lengths", "reverse_tip", "isolated", "no_arcs", "chain1"])
 def test_tips(eng, name, tip_reads):

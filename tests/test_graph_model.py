@@ -165,6 +165,12 @@ def test_what_the_large_patterns_hold():
         assert len(rec) == len(g["classes"]) == want and len(set(g["classes"].tolist())) >= 4 and g["counts"]["transitive"] > 0
     rec, lens, kw, g = _model("many_reads")
     assert len(lens) == 1500 > 2 * 256 and g["counts"]["kept"] == 2 * (len(lens) - 1) and g["counts"]["contained"] == 0
+    # 128 reads: one chunk of the degree scan, full; 129: two vertices behind it, with arcs of their own
+    for pattern, n in (("tiling128", 128), ("tiling129", 129)):
+        rec, lens, kw, g = _model(pattern)
+        assert len(lens) == n and len(rec) == 4 * n - 6 and g["classes"].tolist() == [DOVETAIL] * len(rec)
+        assert g["counts"]["arcs"] == len(rec) and g["counts"]["kept"] == 2 * (n - 1) and g["counts"]["contained"] == 0
+        assert g["reads"]["deg"].sum(axis=1).tolist() == [2, 3] + [4] * (n - 4) + [3, 2] and len(set(rec["comp"].tolist())) == 2
     rec, lens, kw, g = _model("random")
     assert len(rec) == 4000 and len(lens) == 300 and sorted(kw) == ["clip", "params"]
     assert all(n > 0 for n in g["counts"]["by_class"][INTERNAL:]) and g["counts"]["by_class"][NONE] > 0

@@ -227,6 +227,21 @@ def test_chains_come_out_whole_in_the_orientation_with_the_smaller_head():
     assert np.abs(np.diff(vertex_lists(_run("chain257", 0))[0])).max() > 128 and ordered         # neighbours far apart in id
 
 
+def test_the_tilings_end_with_the_scans_chunk_and_one_read_behind_it():
+    for name, n in (("tiling128", 128), ("tiling129", 129)):
+        lens, reads, arcs, clip = _graph_of(name)
+        assert len(lens) == n and set((arcs["u"] & 1).tolist()) == {0, 1}
+        pieces = [list(range(a, min(a + 5, 128))) for a in range(0, 128, 5)] + [[128]] * (n - 128)
+        res = _run(name, 0)
+        u = res["unitigs"]
+        assert _reads_of(res) == pieces and not u["circular"].any()
+        assert (u["first"] >> 1).tolist() == [p[0] for p in pieces] and u["layout_at"].tolist() == list(range(0, 126, 5)) + [128] * (n - 128)
+        if n == 129:                                     # the head behind the chunk: its number, layout_at and seq_at are all carries
+            assert u["first"][-1] == 256 and u["seq_at"][-1] == u["length"][:-1].sum() > 0 and len(u) - 1 == 26
+        res = _run(name, 3)
+        assert _reads_of(res) == pieces[:25] and np.flatnonzero(res["places"]["state"] == TIP).tolist() == list(range(125, n))
+
+
 def test_tips():
     assert _reads_of(_run("fork", 1)) == [[0, 1, 2, 3, 4], [5, 6, 7, 8, 9], [10, 11]]
     assert _reads_of(_run("fork", 3)) == [list(range(10))] and _run("fork", 3)["counts"]["cut"] == 2

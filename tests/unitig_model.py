@@ -244,7 +244,8 @@ def random_graph(n, seed):
 
 
 HAND_MADE = ("chain1", "chain64", "chain65", "chain257", "chain5000", "minus64", "fork", "two_tips", "tip_lengths", "reverse_tip",
-             "isolated", "no_arcs", "cycle2", "cycle3", "cycle300", "cycle_minus", "cycle_beside", "cycle_tip", "skipped")
+             "isolated", "no_arcs", "cycle2", "cycle3", "cycle300", "cycle_minus", "cycle_beside", "cycle_tip", "skipped",
+             "tiling128", "tiling129")
 
 
 def hand_made(pattern, seed=20261020):
@@ -305,6 +306,13 @@ def hand_made(pattern, seed=20261020):
         rows = path_rows([0, 3, 4, 7, 8, 10]) + [(0, 4, 2500, 1), (3, 7, 2600, 2)]
         contained = (6,)
         clip = np.array([(100, 4900)] * 7 + [(2000, 2000)], dtype=np.int32).reshape(-1)
+    elif pattern in ("tiling128", "tiling129"):
+        # reads in id order on random strands, joined in pieces of five; left over are reads 125 .. 127, a piece of three, and of
+        # 129 reads the last one alone.  256 vertices are the last that one chunk of the scan holds; the last two of 258 are the
+        # first behind its carry, and where no tip is cut read 128 is a unitig whose head is vertex 256
+        n = int(pattern[6:])
+        vs = [int(2 * i + s) for i, s in enumerate(rng.integers(0, 2, n))]
+        rows = [row for a in range(0, 128, 5) for row in path_rows(vs[a:min(a + 5, 128)])]
     else:
         raise ValueError(pattern)
     return np.full(n, 5000, dtype=np.int32), plain_reads(n, contained), make_arcs(rows), clip
