@@ -317,6 +317,8 @@ struct Slot {
     PassScratch<gact_graph_stats> graph;
     // gact_hip_unitigs (gact_unitig.hpp): arcs | reads | lens | clip | degrees, counters, flag | links | ranking records | scans | unitigs, layout, places | bases
     PassScratch<gact_unitig_stats> unitig;
+    // gact_hip_pop_bubbles (gact_bubble.hpp): arcs | reads | lens | clip | skip | degrees, found, gone, bits, counters, flag | first | owner | read_bubble | bubbles
+    PassScratch<gact_bubble_stats> bubble;
     // gact_hip_pileup_add (gact_pileup.hpp): the events around this slot's adds; the counts are the engine's (Pileup)
     PassTimer pile_timer;
 
@@ -333,6 +335,7 @@ struct Slot {
         cover.release();
         graph.release();
         unitig.release();
+        bubble.release();
         pile_timer.release();
         if (d_counter) (void)hipFree(d_counter);
         if (d_flags) (void)hipFree(d_flags);
@@ -1948,6 +1951,7 @@ int gact_hip_measure_valu_rate(gact_hip_engine *e, double *lane_ops_per_s)
 #include "gact_graph.hpp"        // gact_hip_overlap_graph: containment, dovetail arcs and their transitive flags, behind those
 #include "gact_pileup.hpp"       // gact_hip_pileup_*: per-base pileup and consensus from the alignments' columns
 #include "gact_unitig.hpp"       // gact_hip_unitigs: tip cut, chain ranking, layout and bases of the graph's unitigs, behind every other kernel
+#include "gact_bubble.hpp"       // gact_hip_pop_bubbles: the bubbles of the graph, one wave per search, on the unitigs' first kernels
 
 #ifdef GACT_STAMPS
 // diagnostic build: per-wave (start, queues empty, end, iterations) of the last main launch

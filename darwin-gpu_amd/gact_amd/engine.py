@@ -51,6 +51,13 @@ UNITIG_PLACE_DTYPE = np.dtype([(n, "<i4") for n in ("unitig", "rank", "orient", 
 assert UNITIG_DTYPE.itemsize == 40 and UNITIG_ENTRY_DTYPE.itemsize == 16 and UNITIG_PLACE_DTYPE.itemsize == 16
 UNITIG_PLACED, UNITIG_CONTAINED, UNITIG_EMPTY, UNITIG_TIP = range(4)
 UNITIG_DEFAULT_TIP_READS = 3
+# the bubbles of an overlap graph (include/gact_hip.h gact_hip_pop_bubbles): one record per bubble found
+BUBBLE_DTYPE = np.dtype([(n, "<i4") for n in ("source", "sink", "n_vertices", "n_path", "n_removed", "state")] + [("path_len", "<i8")])
+assert BUBBLE_DTYPE.itemsize == 32
+BUBBLE_POPPED, BUBBLE_LOST = 0, 1
+GRAPH_ARC_BUBBLE = 4
+BUBBLE_DEFAULT_MAX_DIST = 50000
+BUBBLE_MAX_VERTICES = 64
 # the kinds a position of a pileup counts (include/gact_hip.h GACT_PILEUP_*), and the per-read table of pileup_finish
 PILEUP_A, PILEUP_C, PILEUP_G, PILEUP_T, PILEUP_OTHER, PILEUP_DEL, PILEUP_INS, PILEUP_DEPTH = range(8)
 PILEUP_COL_DTYPE = np.dtype([("n", "<u4", (8,))])
@@ -172,6 +179,20 @@ class UnitigStats(C.Structure):
     _fields_ = [("device_ms", C.c_float)] + \
                [(n, C.c_int32) for n in ("reads", "placed", "cut", "contained", "unitigs", "circular", "longest_reads", "rank_launches")] + \
                [(n, C.c_int64) for n in ("longest_bases", "e0_arcs", "e1_arcs", "joins", "links", "scratch_bytes")]
+
+
+class BubbleParams(C.Structure):
+    """the defaults are GACT_BUBBLE_DEFAULT_MAX_DIST and GACT_BUBBLE_MAX_VERTICES"""
+    _fields_ = [("max_dist", C.c_int32), ("max_vertices", C.c_int32)]
+
+    def __init__(self, max_dist=BUBBLE_DEFAULT_MAX_DIST, max_vertices=BUBBLE_MAX_VERTICES):
+        super().__init__(max_dist, max_vertices)
+
+
+class BubbleStats(C.Structure):
+    _fields_ = [("device_ms", C.c_float)] + \
+               [(n, C.c_int32) for n in ("reads", "sources", "found", "popped", "lost", "reads_removed")] + \
+               [("working_arcs", C.c_int64), ("arcs_removed", C.c_int64), ("by_fail", C.c_int64 * 5), ("scratch_bytes", C.c_int64)]
 
 
 class PileupStats(C.Structure):
@@ -368,6 +389,14 @@ def load():
     except AttributeError:
         pass
     try:
+        L.gact_hip_pop_bubbles.argtypes = [vp, C.c_int, i32, vp, vp, vp, C.c_int64, vp, vp, C.POINTER(BubbleParams), vp, C.c_int64,
+                                           C.POINTER(C.c_int64), vp, vp]
+        L.gact_hip_pop_bubbles.restype = C.c_int
+        L.gact_hip_last_bubble_stats.argtypes = [vp, C.c_int, C.POINTER(BubbleStats)]
+        L.gact_hip_last_bubble_stats.restype = C.c_int
+    except AttributeError:
+        pass
+    try:
         L.gact_hip_pileup_begin.argtypes = [vp, i32, i32]
         L.gact_hip_pileup_add.argtypes = [vp, C.c_int, i32, vp, i32, C.c_int]
         L.gact_hip_pileup_finish.argtypes = [vp, i32, vp, vp, vp]
@@ -417,9 +446,9 @@ EXPORTS = ("gact_hip_create", "gact_hip_destroy", "gact_hip_last_error", "gact_h
            "gact_hip_candidates_paths", "gact_hip_last_paths_stats", "gact_hip_candidates_summaries",
            "gact_hip_last_summaries_stats", "gact_hip_format_paf", "gact_hip_select_overlaps", "gact_hip_last_select_stats",
            "gact_hip_read_coverage", "gact_hip_last_cover_stats", "gact_hip_overlap_graph", "gact_hip_last_graph_stats",
-           "gact_hip_unitigs", "gact_hip_last_unitig_stats", "gact_hip_pileup_begin", "gact_hip_pileup_add",
-           "gact_hip_pileup_finish", "gact_hip_last_pileup_stats", "gact_hip_pileup_begin_ins", "gact_hip_pileup_corrected",
-           "gact_hip_last_pileup_ins_stats")
+           "gact_hip_unitigs", "gact_hip_last_unitig_stats", "gact_hip_pop_bubbles", "gact_hip_last_bubble_stats",
+           "gact_hip_pileup_begin", "gact_hip_pileup_add", "gact_hip_pileup_finish", "gact_hip_last_pileup_stats",
+           "gact_hip_pileup_begin_ins", "gact_hip_pileup_corrected", "gact_hip_last_pileup_ins_stats")
 
 
 def plan(count, flags=0, compute_units=256, tile_size=320, tile_overlap=120, scoring=(1, -1, -1, -1), threshold=35):
@@ -777,6 +806,47 @@ class Engine:
         contained, unitigs, circular ones, the longest in reads and in bases, ranking launches, arcs with flags == 0, those
         left after the tip cut, joins and links among them, device bytes the call holds"""
         return self._stats(self.L.gact_hip_last_unitig_stats, UnitigStats, slot)
+
+    def pop_bubbles(self, read_lens, reads, arcs, clip=None, skip=None, max_dist=BUBBLE_DEFAULT_MAX_DIST,
+                    max_vertices=BUBBLE_MAX_VERTICES, slot=0):
+        """the bubbles of an overlap graph, found and popped on the device: (bubbles, read_bubble, arc_flags) -- one
+        BUBBLE_DTYPE record per bubble found, BUBBLE_POPPED or BUBBLE_LOST, ascending by source; per read the index of the
+        bubble that removed it or -1; per arc its flags with GRAPH_ARC_BUBBLE set where a popped bubble removed it.
+        read_lens, clip, reads and arcs as unitigs takes them; skip: None, or one value per read, != 0 takes the read's arcs
+        out of the working set (the tips of an earlier unitigs call, places["state"] == UNITIG_TIP)
+        (include/gact_hip.h gact_hip_pop_bubbles)"""
+        read_lens = np.ascontiguousarray(read_lens, dtype=np.int32)
+        reads = np.ascontiguousarray(reads, dtype=GRAPH_READ_DTYPE)
+        arcs = np.ascontiguousarray(arcs, dtype=GRAPH_ARC_DTYPE)
+        n = len(read_lens)
+        assert len(reads) == n
+        if clip is not None:
+            clip = np.ascontiguousarray(clip, dtype=np.int32).reshape(-1)
+            assert len(clip) == 2 * n
+        if skip is not None:
+            skip = np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8)
+            assert len(skip) == n
+        params = BubbleParams(int(max_dist), int(max_vertices))
+        read_bubble = np.zeros(n, dtype=np.int32)
+        arc_flags = np.zeros(len(arcs), dtype=np.int32)
+        n_bubbles = C.c_int64()
+        cap = 64                                    # (a bubble per hundred reads is many)
+        for attempt in range(2):
+            bubbles = np.zeros(cap, dtype=BUBBLE_DTYPE)
+            rc = self.L.gact_hip_pop_bubbles(self.h, slot, n, _ptr(read_lens), _ptr(clip), _ptr(reads), len(arcs), _ptr(arcs),
+                                             _ptr(skip), C.byref(params), _ptr(bubbles), cap, C.byref(n_bubbles),
+                                             _ptr(read_bubble), _ptr(arc_flags))
+            if rc == 0 or attempt or n_bubbles.value <= cap:
+                break
+            cap = n_bubbles.value                   # (EINVAL with *n_bubbles filled: once more with room for them)
+        self._check(rc)
+        return bubbles[:n_bubbles.value].copy(), read_bubble, arc_flags
+
+    def last_bubble_stats(self, slot=0):
+        """the slot's last bubble call: device ms (HIP events around the whole call), reads, sources searched from, bubbles
+        found, popped and lost, reads removed, arcs of the working set, arcs removed, the failed searches by their first
+        failure (a list of 5: open, dead, twice, dist, many), device bytes the call holds"""
+        return self._stats(self.L.gact_hip_last_bubble_stats, BubbleStats, slot)
 
     def pileup_begin(self, read_first=0, n_reads=None, ins_slots=0):
         """opens the pileup window: reads [read_first, read_first + n_reads) of SET_REF (n_reads None: to the set's end), counts

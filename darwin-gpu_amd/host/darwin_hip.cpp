@@ -3,7 +3,7 @@
 //   darwin_hip <REF.fasta> <READS.fasta> CPU_THREADS [--params params.cfg]
 //              [--candidates FILE | --dump-candidates FILE [--dsoft-only]] [--device-dsoft]
 //              [--device D] [--shard R/W] [--recode] [--cigar] [--paf] [--unique exact|pair] [--coverage K]
-//              [--pileup K [--ins-slots S]] [--gfa [--unitigs K]]
+//              [--pileup K [--ins-slots S]] [--gfa [--unitigs K [--bubbles D]]]
 //
 // Plays the part of reference darwin.cpp:451-646 for the GACT stage: owns the
 // globals gact.cpp reads, loads params.cfg and the two FASTA files, builds the
@@ -54,6 +54,11 @@
 // `S utg<6 digits><l|c> <bases> LN:i:<length>` line (l linear, c circular) followed by one `a <utg> <start> <read name>:<b>-<e>
 // <+|-> <take>` line per entry of its layout, [b, e) the read's clip; and then one `L <utg> <+|-> <utg> <+|-> <min(ov_u, ov_v)>M`
 // line per link (include/gact_hip.h, rule 7), in the arc list's order.  Every other output byte is as without the flag.
+// --bubbles D (with --gfa --unitigs K, K >= 1; 1 <= D <= 2^30): behind the graph call one gact_hip_unitigs call without bases to
+// learn the tips, then gact_hip_pop_bubbles with those tips as skip and max_dist = D; darwin.bubbles.tsv gets one line per
+// bubble found: source, sink, state (0 popped, 1 lost), n_vertices, n_path, n_removed, path_len, tab-separated; and the unitig
+// call of --unitigs runs over the arcs with arc_flags written into their flags -- its tip cut is the second round -- so
+// darwin.utg.gfa is made from the cleaned arcs.  darwin.gfa and every other file are as without the flag.
 //
 // --device D: the GPU this process uses (the reference is single-device, cuda_host.cu:195).  --shard R/W: this
 // process is rank R of W -- it extends every W-th candidate (host filter) or the R-th contiguous range of reads
@@ -98,6 +103,7 @@ static int pileup_depth = 0;                     // --pileup K: min_depth of dar
 static int pileup_ins_slots = 0;                 // --ins-slots S: the inserted bases kept per position, 0: none
 static bool want_gfa = false;                    // --gfa: darwin.gfa, the overlap graph of the records written
 static int unitig_tips = -1;                     // --unitigs K: tip_reads of darwin.utg.gfa, -1: no unitigs
+static int bubble_dist = 0;                      // --bubbles D: max_dist of the bubble popping in front of the unitigs, 0: none
 // --coverage, --gfa: the records every feeder wrote a line for, in its file's order, and with --paf their summaries
 static std::vector<std::vector<gact_overlap> > cover_records;
 static std::vector<std::vector<gact_path_summary> > cover_sums;
@@ -432,6 +438,41 @@ static int write_unitigs(gact_hip_engine *e, const std::vector<int32_t> &lens, c
     return 0;
 }
 
+// --bubbles: behind the graph call, on slot 0: one unitig call without bases to learn the tips, then gact_hip_pop_bubbles with
+// those tips as skip, then darwin.bubbles.tsv; arc_flags goes into the flags of `arcs`, which the unitig call of --unitigs takes
+static int pop_bubbles(gact_hip_engine *e, const std::vector<int32_t> &lens, const std::vector<int32_t> &clip,
+                       const std::vector<gact_graph_read> &reads, std::vector<gact_graph_arc> &arcs, int64_t n_arcs)
+{
+    const size_t n = lens.size();
+    const int32_t *clip_p = clip.empty() ? nullptr : clip.data();
+    std::vector<gact_unitig> utg(n);
+    std::vector<gact_unitig_entry> layout(n);
+    std::vector<gact_unitig_place> places(n);
+    int32_t n_utg = 0;
+    const gact_unitig_params tips = {unitig_tips};
+    int rc = gact_hip_unitigs(e, 0, (int32_t)n, lens.data(), clip_p, reads.data(), n_arcs, arcs.data(), &tips, utg.data(), &n_utg,
+                              layout.data(), places.data(), nullptr, 0, nullptr);
+    if (rc != 0) { printf("\ngact_hip_unitigs failed: %s\n\n", gact_hip_last_error()); return 1; }
+    std::vector<uint8_t> skip(n);
+    for (size_t i = 0; i < n; i++) skip[i] = places[i].state == GACT_UNITIG_TIP;
+    const gact_bubble_params params = {bubble_dist, GACT_BUBBLE_MAX_VERTICES};
+    std::vector<gact_bubble> bubbles(2 * n + 1);                     // (a bubble per vertex at most)
+    std::vector<int32_t> read_bubble(n), arc_flags((size_t)n_arcs + 1);
+    int64_t n_bubbles = 0;
+    rc = gact_hip_pop_bubbles(e, 0, (int32_t)n, lens.data(), clip_p, reads.data(), n_arcs, arcs.data(), skip.data(), &params,
+                              bubbles.data(), (int64_t)bubbles.size(), &n_bubbles, read_bubble.data(), arc_flags.data());
+    if (rc != 0) { printf("\ngact_hip_pop_bubbles failed: %s\n\n", gact_hip_last_error()); return 1; }
+    FILE *f = fopen("darwin.bubbles.tsv", "w");
+    if (!f) { fprintf(stderr, "--bubbles: cannot write darwin.bubbles.tsv\n"); return 1; }
+    for (int64_t j = 0; j < n_bubbles; j++) {
+        const gact_bubble &b = bubbles[(size_t)j];
+        fprintf(f, "%d\t%d\t%d\t%d\t%d\t%d\t%lld\n", b.source, b.sink, b.state, b.n_vertices, b.n_path, b.n_removed, (long long)b.path_len);
+    }
+    fclose(f);
+    for (int64_t k = 0; k < n_arcs; k++) arcs[(size_t)k].flags = arc_flags[(size_t)k];
+    return 0;
+}
+
 // --gfa: one call over the records all feeders kept, on slot 0, then darwin.gfa.  clip: the spans of --coverage, or empty
 static int write_gfa(gact_hip_engine *e, const std::vector<int32_t> &clip)
 {
@@ -463,6 +504,7 @@ static int write_gfa(gact_hip_engine *e, const std::vector<int32_t> &clip)
                 reads_descrips[(size_t)(a.v >> 1)][0].c_str(), a.v & 1 ? '-' : '+', std::min(a.ov_u, a.ov_v), a.len);
     }
     fclose(f);
+    if (bubble_dist && pop_bubbles(e, lens, clip, reads, arcs, n_arcs)) return 1;      // (darwin.gfa is written: the arcs may change)
     return unitig_tips >= 0 ? write_unitigs(e, lens, clip, reads, arcs, n_arcs) : 0;
 }
 
@@ -682,7 +724,7 @@ int main(int argc, char *argv[])
     if (argc >= 3 && strcmp(argv[1], "--selftest") == 0) return selftest(argv[2]);
     if (argc < 4) {
         fprintf(stderr, "Usage: darwin_hip <REFERENCE>.fasta <READS>.fasta CPU_THREADS --candidates FILE "
-                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K [--ins-slots S]] [--gfa [--unitigs K]]]\n");
+                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K [--ins-slots S]] [--gfa [--unitigs K [--bubbles D]]]]\n");
         return 1;
     }
     std::string cand_path, dump_path, cfg_path = "params.cfg", gather_id;
@@ -734,6 +776,13 @@ int main(int argc, char *argv[])
             if (!*v || *end || k < 0 || k > 0x7fffffffL) { fprintf(stderr, "--unitigs wants an integer >= 0, not '%s'\n", v); return 1; }
             unitig_tips = (int)k;
         }
+        else if (!strcmp(argv[a], "--bubbles")) {
+            const char *v = a + 1 < argc ? argv[++a] : "";
+            char *end = nullptr;
+            const long k = strtol(v, &end, 10);
+            if (!*v || *end || k < 1 || k > (1L << 30)) { fprintf(stderr, "--bubbles wants an integer from 1 to 2^30, not '%s'\n", v); return 1; }
+            bubble_dist = (int)k;
+        }
         else if (!strcmp(argv[a], "--rccl-gather") && a + 1 < argc) gather_id = argv[++a];
         else if (!strcmp(argv[a], "--device") && a + 1 < argc) setenv("GACT_HIP_DEVICE", argv[++a], 1);   // read by GPU_init
         else if (!strcmp(argv[a], "--shard") && a + 1 < argc) {
@@ -780,6 +829,12 @@ int main(int argc, char *argv[])
         // the graph is over one read set, from the records of one process's feeders: the host-filter mode keeps none, a rank of a
         // sharded job holds part of every read's overlaps, and with two files ref and query ids name different sequences
         fprintf(stderr, "--gfa: only with --device-dsoft and one input file used for both sides, and not with --shard\n");
+        return 1;
+    }
+    if (bubble_dist && (!want_gfa || unitig_tips < 1)) {
+        // the bubbles are popped between two rounds of tip cutting, the second one the unitig call's: with K == 0 no tip is cut and
+        // the reads a bubble removed would come back as unitigs of one read
+        fprintf(stderr, "--bubbles: only with --gfa --unitigs K and K >= 1\n");
         return 1;
     }
     if (unitig_tips >= 0 && !want_gfa) {

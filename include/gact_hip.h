@@ -520,8 +520,8 @@ int gact_hip_last_graph_stats(gact_hip_engine *e, int slot, gact_graph_stats *st
  * The arc checks run on the device.  n_reads == 0 returns 0 with *n_unitigs = 0 and *seq_len = 0.
  * Synchronous on the slot's stream; the slot's records and every other statistic stay as they were.  Device memory of its own, one
  * allocation per slot, grown on demand: 32 bytes per arc, about 300 per read (8 more with a clip), and with seq the reads'
- * clipped lengths.  Out of scope: bubble popping, repeated rounds of cleaning, pruning of short overlaps, sharded jobs, and
- * taking the arcs from the graph call's scratch. */
+ * clipped lengths.  Out of scope: repeated rounds of cleaning, pruning of short overlaps, sharded jobs, and taking the arcs from
+ * the graph call's scratch.  Bubble popping is gact_hip_pop_bubbles', below. */
 #define GACT_UNITIG_DEFAULT_TIP_READS 3
 #define GACT_UNITIG_PLACED    0
 #define GACT_UNITIG_CONTAINED 1
@@ -545,6 +545,80 @@ int gact_hip_unitigs(gact_hip_engine *e, int slot, int32_t n_reads, const int32_
 typedef struct { float device_ms; int32_t reads, placed, cut, contained, unitigs, circular, longest_reads, rank_launches;
                  int64_t longest_bases, e0_arcs, e1_arcs, joins, links, scratch_bytes; } gact_unitig_stats;
 int gact_hip_last_unitig_stats(gact_hip_engine *e, int slot, gact_unitig_stats *stats);
+
+/* ---- bubbles: the short alternative paths of the overlap graph, found and popped on the device ----
+ * The cleaning step of a layout stage that belongs between two rounds of tip cutting (miniasm's order): a bubble is two or more
+ * paths that leave one vertex and meet again a few reads later -- reads with errors, lost overlaps, arcs the triangle rule did
+ * not flag -- and gact_hip_unitigs breaks the layout at every one.  This call finds them, keeps one path of each and marks the
+ * rest as removed (csrc/gact_bubble.hpp).  All integer, path lengths in 64 bits, order-free across sources: every output is the
+ * same on every call and every slot.  The graph is not changed: the caller writes arc_flags into the arcs' flags for a
+ * following gact_hip_unitigs.
+ * Inputs.  read_lens, clip, reads, arcs: the ones gact_hip_unitigs takes, with the same meaning and the same refusals (no bases
+ * are asked for, so an arc may be longer than the read it leaves).
+ *   skip    NULL, or one byte per read: != 0 takes the read's arcs out of the working set.  A caller who wants the tips out of
+ *           the way first passes skip[i] = places[i].state == GACT_UNITIG_TIP of an earlier gact_hip_unitigs call
+ *   params  NULL: max_dist = GACT_BUBBLE_DEFAULT_MAX_DIST (miniasm's usual value: a parameter, not a measurement), max_vertices =
+ *           GACT_BUBBLE_MAX_VERTICES
+ * The rule.
+ *   1 The working set W = the arcs with flags == 0 whose two reads are not named by skip.  out(x) = the W arcs out of x, in
+ *     array order; in(x) = |out(x^1)|
+ *   2 One search per source s with |out(s)| >= 2.  Every seen vertex x has a record (r, d, c, pd, pred): the in-arcs not yet
+ *     crossed, the least distance from s, the arc count of the best path from s, that path's length (64 bits), its last arc.
+ *     s is seen with (0, 0, 0, 0, -1) and alone on a LIFO stack; pending = 0.  Repeat: pop v; out(v) empty fails with `dead`;
+ *     for each arc k: v -> w of out(v) in array order:
+ *       w == s, w == s^1 or w^1 seen fails with `twice`;  d' = d[v] + len > max_dist fails with `dist`;
+ *       w not seen: max_vertices vertices seen already fails with `many`, else w is seen with (in(w), d', c[v] + 1, pd[v] + len,
+ *       k) and pending += 1;  w seen: d[w] = min(d[w], d'), and (c, pd, pred) becomes (c[v] + 1, pd[v] + len, k) when that c is
+ *       larger, or equal with a smaller pd, or both equal with a lower k;
+ *       then r[w] -= 1, and at 0 w is pushed and pending -= 1.
+ *     Behind the arcs of v: exactly one vertex on the stack and pending == 0: it is the sink t, the search succeeds; the stack
+ *     empty fails with `open` (some seen vertex has an in-arc from outside).  A vertex is expanded only after all its in-arcs
+ *     are crossed, so its record is final when it is read; at success no arc of W enters the seen set from outside and none
+ *     leaves it but out of t
+ *   3 A found bubble: n_vertices = the seen vertices, s and t among them; its interior = the seen vertices without s and t, never
+ *     empty; its kept path = the walk back from t along pred -- the path of the most arcs, then the fewest bases; n_path = the
+ *     interior vertices on it, n_removed the others; path_len = pd[t]
+ *   4 owner[read] = the lowest source among the found bubbles whose interior holds a vertex of the read.  A bubble is
+ *     GACT_BUBBLE_POPPED iff it owns every read of its interior, else GACT_BUBBLE_LOST.  The same bubble found from its other
+ *     side (source t^1) has the same interior reads, so one of the two loses; of two nested bubbles the one that owns the
+ *     contested reads pops, and the other waits for a round this call does not make
+ *   5 A popped bubble removes (a) its interior reads that are not on the kept path: every W arc that touches one gets the bit
+ *     GACT_GRAPH_ARC_BUBBLE and read_bubble[i] = the bubble's index; (b) every W arc x -> y with x seen, x != t, x and y both on
+ *     the kept path (s and t included) that is not an arc of the path: it gets the bit and so does its complement y^1 -> x^1
+ * Result.  arc_flags[k] = arcs[k].flags | (removed ? GACT_GRAPH_ARC_BUBBLE : 0); read_bubble[i] = -1 for a read nothing removed;
+ * bubbles = every found bubble, POPPED and LOST, ascending by source.  bubbles_cap too small (or bubbles == NULL): GACT_HIP_EINVAL
+ * with *n_bubbles, read_bubble and arc_flags filled -- call again with room for *n_bubbles, as with arcs_cap in the graph call.
+ * What follows.  The arcs left (flags == 0, no bit set) are closed under complement.  After the pops out(s) == 1 for a popped
+ * bubble's source, and every arc of its kept path is a join in gact_hip_unitigs' sense.  A removed read keeps no arc: a
+ * following gact_hip_unitigs with tip_reads >= 1 gives it the state GACT_UNITIG_TIP, and with tip_reads == 0 makes it a unitig
+ * of one read: known, and not repaired, because the unitig call does not change.
+ * Refused with GACT_HIP_EINVAL, outputs untouched: what gact_hip_unitigs refuses of read_lens, clip, reads and arcs (the arc
+ * checks run on the device); max_dist < 1 or > 2^30; max_vertices < 3 or > GACT_BUBBLE_MAX_VERTICES; NULL n_bubbles, read_bubble
+ * or arc_flags; bubbles_cap < 0.  n_reads == 0 returns 0 with *n_bubbles = 0.
+ * Synchronous on the slot's stream; the slot's records and every other statistic stay as they were.  Device memory of its own,
+ * one allocation per slot, grown on demand: 36 bytes per arc and about 150 per read (8 more with a clip, 4 more with skip).
+ * Out of scope: repeated rounds (a caller may call again with the removed reads added to skip), pruning of short overlaps,
+ * bubbles of more than 64 vertices, sharded jobs. */
+#define GACT_GRAPH_ARC_BUBBLE 4            /* bit 2 of gact_graph_arc.flags: removed by gact_hip_pop_bubbles */
+#define GACT_BUBBLE_DEFAULT_MAX_DIST 50000 /* after miniasm: a parameter, not a measurement */
+#define GACT_BUBBLE_MAX_VERTICES 64        /* one wave: one seen vertex per lane */
+#define GACT_BUBBLE_POPPED 0
+#define GACT_BUBBLE_LOST   1               /* found, but some interior read belongs to a bubble with a lower source */
+typedef struct { int32_t max_dist, max_vertices; } gact_bubble_params;
+typedef struct { int32_t source, sink, n_vertices, n_path, n_removed, state; int64_t path_len; } gact_bubble;  /* 32 bytes */
+int gact_hip_pop_bubbles(gact_hip_engine *e, int slot, int32_t n_reads, const int32_t *read_lens, const int32_t *clip,
+                         const gact_graph_read *reads, int64_t n_arcs, const gact_graph_arc *arcs,
+                         const uint8_t *skip /* NULL, or n_reads bytes: != 0 takes the read's arcs out of the working set */,
+                         const gact_bubble_params *params /* NULL: the defaults */,
+                         gact_bubble *bubbles, int64_t bubbles_cap, int64_t *n_bubbles,
+                         int32_t *read_bubble /* n_reads */, int32_t *arc_flags /* n_arcs */);
+/* What the slot's last gact_hip_pop_bubbles call that got as far as the device did: HIP events on the slot's stream around the
+ * whole call (copies and kernels), the reads, the sources searched from, the bubbles found, popped and lost, the reads removed,
+ * the arcs of the working set and those removed, the searches that failed by their first failure (open, dead, twice, dist,
+ * many, in that order), and the device memory the call holds for itself. */
+typedef struct { float device_ms; int32_t reads, sources, found, popped, lost, reads_removed;
+                 int64_t working_arcs, arcs_removed, by_fail[5], scratch_bytes; } gact_bubble_stats;
+int gact_hip_last_bubble_stats(gact_hip_engine *e, int slot, gact_bubble_stats *stats);
 
 /* Per-base pileup and consensus of the reads of GACT_SET_REF from the overlaps' alignments, counted on the device: every chosen
  * candidate's alignment (the one gact_hip_candidates_paths returns as a CIGAR) is stacked on its target read, every position
