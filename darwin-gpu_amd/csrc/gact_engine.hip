@@ -319,6 +319,8 @@ struct Slot {
     PassScratch<gact_unitig_stats> unitig;
     // gact_hip_pop_bubbles (gact_bubble.hpp): arcs | reads | lens | clip | skip | degrees, found, gone, bits, counters, flag | first | owner | read_bubble | bubbles
     PassScratch<gact_bubble_stats> bubble;
+    // gact_hip_place_reads (gact_place.hpp): host records | sel | sums | lens | first | fill | flag, counters | reads | items | CSR | ranked | place | spans
+    PassScratch<gact_place_stats> place;
     // gact_hip_pileup_add (gact_pileup.hpp): the events around this slot's adds; the counts are the engine's (Pileup)
     PassTimer pile_timer;
 
@@ -336,6 +338,7 @@ struct Slot {
         graph.release();
         unitig.release();
         bubble.release();
+        place.release();
         pile_timer.release();
         if (d_counter) (void)hipFree(d_counter);
         if (d_flags) (void)hipFree(d_flags);
@@ -1952,6 +1955,7 @@ int gact_hip_measure_valu_rate(gact_hip_engine *e, double *lane_ops_per_s)
 #include "gact_pileup.hpp"       // gact_hip_pileup_*: per-base pileup and consensus from the alignments' columns
 #include "gact_unitig.hpp"       // gact_hip_unitigs: tip cut, chain ranking, layout and bases of the graph's unitigs, behind every other kernel
 #include "gact_bubble.hpp"       // gact_hip_pop_bubbles: the bubbles of the graph, one wave per search, on the unitigs' first kernels
+#include "gact_place.hpp"        // gact_hip_place_reads: primary, supplementary, secondary and MAPQ of every read, one wave per read
 
 #ifdef GACT_STAMPS
 // diagnostic build: per-wave (start, queues empty, end, iterations) of the last main launch
@@ -2042,6 +2046,85 @@ int gact_hip_format_paf(const gact_overlap *o, const gact_path_summary *s, const
                     query_name, (long long)query_len, (long long)qstart, (long long)qend, o->comp ? '-' : '+', ref_name,
                     (long long)ref_len, (long long)tstart, (long long)tend, (long long)s->n_eq, (long long)block, o->score,
                     (long long)(block - s->n_eq), de);
+}
+
+// SEQ of a SAM line: bases [from, to) of the read's strand (reverse: of its reverse complement), case kept
+static void sam_bases(std::string &line, const uint8_t *seq, int64_t len, bool reverse, int64_t from, int64_t to)
+{
+    static const char *const kFrom = "acgtACGT", *const kTo = "tgcaTGCA";
+    for (int64_t i = from; i < to; i++) {
+        if (!reverse) { line += (char)seq[i]; continue; }
+        const char c = (char)seq[len - 1 - i];
+        const char *at = c ? strchr(kFrom, c) : nullptr;
+        line += at ? kTo[at - kFrom] : 'N';
+    }
+}
+
+// the finished line into buf when it fits (with its terminator); its length either way
+static int64_t sam_put(const std::string &line, char *buf, int64_t cap)
+{
+    if (buf && cap > (int64_t)line.size()) memcpy(buf, line.c_str(), line.size() + 1);
+    else if (buf && cap > 0) buf[0] = 0;
+    return (int64_t)line.size();
+}
+
+int64_t gact_hip_format_sam(const gact_overlap *o, const uint32_t *ops, int32_t n_ops, const gact_placement *p, const char *query_name,
+                            const uint8_t *query_seq, int64_t query_len, const char *ref_name, char *buf, int64_t cap)
+{
+    if (!o || !ops || !p || !query_name || !ref_name || query_len < 0 || cap < 0 || (cap > 0 && !buf))
+        return fail(GACT_HIP_EINVAL, "format_sam: bad arguments");
+    if (n_ops <= 0) return fail(GACT_HIP_EINVAL, "format_sam: no ops (a record without an alignment has no line)");
+    if (p->kind != GACT_PLACE_PRIMARY && p->kind != GACT_PLACE_SUPPLEMENTARY && p->kind != GACT_PLACE_SECONDARY &&
+        p->kind != GACT_PLACE_EXTRA)
+        return fail(GACT_HIP_EINVAL, "format_sam: kind %d has no line (GACT_PLACE_NONE, or none of the kinds)", p->kind);
+    int64_t on_ref = 0, on_query = 0, nm = 0;
+    for (int32_t k = 0; k < n_ops; k++) {
+        const int64_t len = ops[k] >> 4;
+        switch (ops[k] & 15) {
+        case GACT_PATH_OP_EQ: on_ref += len; on_query += len; break;
+        case GACT_PATH_OP_X: on_ref += len; on_query += len; nm += len; break;
+        case GACT_PATH_OP_I: on_query += len; nm += len; break;
+        case GACT_PATH_OP_D: on_ref += len; nm += len; break;
+        default: return fail(GACT_HIP_EINVAL, "format_sam: op %d is none of =, X, I, D", (int)(ops[k] & 15));
+        }
+    }
+    // on the record's strand the alignment is [begin, be) of the read
+    const int64_t begin = (int64_t)o->be - on_query;
+    if (begin < 0 || o->be > query_len || (int64_t)o->ae - on_ref < 0)
+        return fail(GACT_HIP_EINVAL, "format_sam: the alignment [%lld, %d) lies outside the read of %lld bases (or begins in front of "
+                                     "the reference)", (long long)begin, o->be, (long long)query_len);
+    const bool primary = p->kind == GACT_PLACE_PRIMARY, supplementary = p->kind == GACT_PLACE_SUPPLEMENTARY;
+    if ((primary || supplementary) && !query_seq) return fail(GACT_HIP_EINVAL, "format_sam: query_seq is NULL");
+    const int flag = (o->comp ? 16 : 0) + (supplementary ? 2048 : primary ? 0 : 256);
+    const char clip = primary ? 'S' : 'H';
+    std::string line = query_name;
+    line += '\t' + std::to_string(flag) + '\t' + ref_name + '\t' + std::to_string((int64_t)o->ae - on_ref + 1) + '\t' +
+            std::to_string(p->mapq) + '\t';
+    if (begin > 0) line += std::to_string(begin) + clip;
+    for (int32_t k = 0; k < n_ops; k++) {
+        const uint32_t op = ops[k] & 15;
+        line += std::to_string(ops[k] >> 4);
+        line += op == GACT_PATH_OP_EQ ? '=' : op == GACT_PATH_OP_X ? 'X' : op == GACT_PATH_OP_I ? 'I' : 'D';
+    }
+    if (query_len - o->be > 0) line += std::to_string(query_len - o->be) + clip;
+    line += "\t*\t0\t0\t";
+    if (primary) sam_bases(line, query_seq, query_len, o->comp != 0, 0, query_len);
+    else if (supplementary && begin < o->be) sam_bases(line, query_seq, query_len, o->comp != 0, begin, o->be);
+    else line += '*';
+    line += "\t*\tAS:i:" + std::to_string(o->score) + "\tNM:i:" + std::to_string(nm) + '\n';
+    return sam_put(line, buf, cap);
+}
+
+int64_t gact_hip_format_sam_unmapped(const char *query_name, const uint8_t *query_seq, int64_t query_len, char *buf, int64_t cap)
+{
+    if (!query_name || query_len < 0 || (query_len > 0 && !query_seq) || cap < 0 || (cap > 0 && !buf))
+        return fail(GACT_HIP_EINVAL, "format_sam_unmapped: bad arguments");
+    std::string line = query_name;
+    line += "\t4\t*\t0\t0\t*\t*\t0\t0\t";
+    if (query_len > 0) sam_bases(line, query_seq, query_len, false, 0, query_len);
+    else line += '*';
+    line += "\t*\n";
+    return sam_put(line, buf, cap);
 }
 
 }  // extern "C"

@@ -58,6 +58,14 @@ BUBBLE_POPPED, BUBBLE_LOST = 0, 1
 GRAPH_ARC_BUBBLE = 4
 BUBBLE_DEFAULT_MAX_DIST = 50000
 BUBBLE_MAX_VERTICES = 64
+# the placement of reads (include/gact_hip.h gact_hip_place_reads): one record per chosen record, one per read of the window
+PLACE_DTYPE = np.dtype([(n, "<i4") for n in ("kind", "mapq", "parent", "rank")])
+READ_PLACE_DTYPE = np.dtype([(n, "<i4") for n in ("n_records", "primary", "n_supplementary", "n_secondary", "n_extra", "score",
+                                                  "second", "mapq")])
+assert PLACE_DTYPE.itemsize == 16 and READ_PLACE_DTYPE.itemsize == 32
+PLACE_NONE, PLACE_PRIMARY, PLACE_SUPPLEMENTARY, PLACE_SECONDARY, PLACE_EXTRA = range(5)
+PLACE_MAX_PARENTS = 64
+PLACE_DEFAULT_MASK_PERMILLE, PLACE_DEFAULT_MAPQ_CAP = 500, 60
 # the kinds a position of a pileup counts (include/gact_hip.h GACT_PILEUP_*), and the per-read table of pileup_finish
 PILEUP_A, PILEUP_C, PILEUP_G, PILEUP_T, PILEUP_OTHER, PILEUP_DEL, PILEUP_INS, PILEUP_DEPTH = range(8)
 PILEUP_COL_DTYPE = np.dtype([("n", "<u4", (8,))])
@@ -150,6 +158,17 @@ _SELECT_MODES = {"exact": SELECT_EXACT, "pair": SELECT_PAIR}
 
 class CoverStats(C.Structure):
     _fields_ = [("device_ms", C.c_float), ("reads", C.c_int32), ("intervals", C.c_int64), ("positions", C.c_int64),
+                ("scratch_bytes", C.c_int64)]
+
+
+class PlaceParams(C.Structure):
+    """the defaults are GACT_PLACE_DEFAULT_*"""
+    _fields_ = [("mask_permille", C.c_int32), ("mapq_cap", C.c_int32)]
+
+
+class PlaceStats(C.Structure):
+    _fields_ = [("device_ms", C.c_float), ("reads", C.c_int32), ("max_records", C.c_int32), ("reserved", C.c_int32),
+                ("counted", C.c_int64), ("parents", C.c_int64), ("secondaries", C.c_int64), ("extras", C.c_int64),
                 ("scratch_bytes", C.c_int64)]
 
 
@@ -373,6 +392,17 @@ def load():
     except AttributeError:
         pass
     try:
+        L.gact_hip_place_reads.argtypes = [vp, C.c_int, i32, vp, i32, vp, vp, i32, i32, vp, C.POINTER(PlaceParams), vp, vp]
+        L.gact_hip_place_reads.restype = C.c_int
+        L.gact_hip_last_place_stats.argtypes = [vp, C.c_int, C.POINTER(PlaceStats)]
+        L.gact_hip_last_place_stats.restype = C.c_int
+        L.gact_hip_format_sam.argtypes = [vp, vp, i32, vp, C.c_char_p, vp, C.c_int64, C.c_char_p, C.c_char_p, C.c_int64]
+        L.gact_hip_format_sam.restype = C.c_int64
+        L.gact_hip_format_sam_unmapped.argtypes = [C.c_char_p, vp, C.c_int64, C.c_char_p, C.c_int64]
+        L.gact_hip_format_sam_unmapped.restype = C.c_int64
+    except AttributeError:
+        pass
+    try:
         L.gact_hip_overlap_graph.argtypes = [vp, C.c_int, i32, vp, i32, vp, vp, i32, vp, vp, C.POINTER(GraphParams), vp, vp, vp,
                                              C.c_int64, C.POINTER(C.c_int64)]
         L.gact_hip_overlap_graph.restype = C.c_int
@@ -448,7 +478,8 @@ EXPORTS = ("gact_hip_create", "gact_hip_destroy", "gact_hip_last_error", "gact_h
            "gact_hip_read_coverage", "gact_hip_last_cover_stats", "gact_hip_overlap_graph", "gact_hip_last_graph_stats",
            "gact_hip_unitigs", "gact_hip_last_unitig_stats", "gact_hip_pop_bubbles", "gact_hip_last_bubble_stats",
            "gact_hip_pileup_begin", "gact_hip_pileup_add", "gact_hip_pileup_finish", "gact_hip_last_pileup_stats",
-           "gact_hip_pileup_begin_ins", "gact_hip_pileup_corrected", "gact_hip_last_pileup_ins_stats")
+           "gact_hip_pileup_begin_ins", "gact_hip_pileup_corrected", "gact_hip_last_pileup_ins_stats",
+           "gact_hip_place_reads", "gact_hip_last_place_stats", "gact_hip_format_sam", "gact_hip_format_sam_unmapped")
 
 
 def plan(count, flags=0, compute_units=256, tile_size=320, tile_overlap=120, scoring=(1, -1, -1, -1), threshold=35):
@@ -724,6 +755,38 @@ class Engine:
         """the slot's last coverage call: device ms (HIP events around the whole call), reads, intervals counted, positions,
         device bytes the call holds for itself"""
         return self._stats(self.L.gact_hip_last_cover_stats, CoverStats, slot)
+
+    def place_reads(self, read_lens, read_first=0, n=None, records=None, sel=None, sums=None, mask_permille=PLACE_DEFAULT_MASK_PERMILLE,
+                    mapq_cap=PLACE_DEFAULT_MAPQ_CAP, slot=0):
+        """every read of the window [read_first, read_first + len(read_lens)) of the query set placed on the device: (place,
+        reads) -- one PLACE_DTYPE record per chosen record (kind PLACE_*, mapq, parent, rank) and one READ_PLACE_DTYPE record
+        per read (its counted records, the chosen index of its primary or -1, supplementaries, secondaries, extras, the
+        primary's score, its best secondary's, its MAPQ).  records, n, sel and sums as in read_coverage; a read's counted
+        records are ordered by score, span and index, a record that an earlier parent's query interval overlaps by
+        mask_permille of the shorter one is that parent's secondary, the others are the primary and the supplementaries, and
+        mapq = mapq_cap * (s1 - s2) / s1 -- a stated rule, not a calibrated model (include/gact_hip.h gact_hip_place_reads)"""
+        read_lens = np.ascontiguousarray(read_lens, dtype=np.int32)
+        records, n = self._records_arg(records, n, slot)
+        if sel is not None:
+            sel = np.ascontiguousarray(sel, dtype=np.int32)
+        n_chosen = len(sel) if sel is not None else max(n, 0)
+        if sums is not None:
+            sums = np.ascontiguousarray(sums, dtype=SUMMARY_DTYPE)
+            assert len(sums) == n_chosen
+        place = np.zeros(n_chosen, dtype=PLACE_DTYPE)
+        place["parent"] = place["rank"] = -1
+        reads = np.zeros(len(read_lens), dtype=READ_PLACE_DTYPE)
+        reads["primary"] = -1
+        params = PlaceParams(int(mask_permille), int(mapq_cap))
+        self._check(self.L.gact_hip_place_reads(self.h, slot, n, _ptr(records), len(sel) if sel is not None else 0, _ptr(sel),
+                                                _ptr(sums), int(read_first), len(read_lens), _ptr(read_lens), C.byref(params),
+                                                _ptr(place), _ptr(reads)))
+        return place, reads
+
+    def last_place_stats(self, slot=0):
+        """the slot's last placement: device ms (HIP events around the whole call), reads of the window, the most counted
+        records on one read, counted records, parents, secondaries, extras, device bytes the call holds for itself"""
+        return self._stats(self.L.gact_hip_last_place_stats, PlaceStats, slot)
 
     def overlap_graph(self, read_lens, n=None, records=None, sel=None, sums=None, clip=None, params=None, classes=False, slot=0):
         """the overlap graph of an overlap set, made on the device: (reads, arcs) -- one GRAPH_READ_DTYPE record per read of
@@ -1015,6 +1078,47 @@ def format_paf(rec, summary, query_name, query_len, ref_name, ref_len, cap=1024)
     if n < 0:
         raise GactHipError("gact_hip error %d: %s" % (n, L.gact_hip_last_error().decode()))
     return buf.raw[:min(n, cap - 1)].decode()
+
+
+def _sam_line(call):
+    """call(buf, cap) -> the line: once with a guessed room, once more with what the first call said it needs"""
+    L = load()
+    cap = 4096
+    for _ in range(2):
+        buf = C.create_string_buffer(cap)
+        n = call(L, buf, cap)
+        if n < 0:
+            raise GactHipError("gact_hip error %d: %s" % (n, L.gact_hip_last_error().decode()))
+        if n < cap:
+            return buf.raw[:n].decode()
+        cap = int(n) + 1
+
+
+def _seq_bytes(seq):
+    """a read as a contiguous uint8 array: str, bytes or an array of bytes"""
+    if isinstance(seq, str):
+        seq = seq.encode()
+    if isinstance(seq, (bytes, bytearray)):
+        return np.frombuffer(bytes(seq), dtype=np.uint8)
+    return np.ascontiguousarray(seq, dtype=np.uint8)
+
+
+def format_sam(rec, ops, place, query_name, query_seq, ref_name):
+    """one SAM line for a record, its op words (candidates_paths) and its PLACE_DTYPE record; query_seq: the ORIGINAL read,
+    bytes or uint8 (include/gact_hip.h gact_hip_format_sam; no engine, no device)"""
+    rec = np.ascontiguousarray(rec, dtype=OVERLAP_DTYPE)
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    place = np.ascontiguousarray(place, dtype=PLACE_DTYPE)
+    seq = _seq_bytes(query_seq)
+    return _sam_line(lambda L, buf, cap: L.gact_hip_format_sam(rec.ctypes.data, ops.ctypes.data, len(ops), place.ctypes.data,
+                                                               query_name.encode(), seq.ctypes.data, len(seq), ref_name.encode(),
+                                                               buf, cap))
+
+
+def format_sam_unmapped(query_name, query_seq):
+    """the flag-4 SAM line of a read without a placement (include/gact_hip.h gact_hip_format_sam_unmapped)"""
+    seq = _seq_bytes(query_seq)
+    return _sam_line(lambda L, buf, cap: L.gact_hip_format_sam_unmapped(query_name.encode(), seq.ctypes.data, len(seq), buf, cap))
 
 
 class Comm:

@@ -3,7 +3,7 @@
 //   darwin_hip <REF.fasta> <READS.fasta> CPU_THREADS [--params params.cfg]
 //              [--candidates FILE | --dump-candidates FILE [--dsoft-only]] [--device-dsoft]
 //              [--device D] [--shard R/W] [--recode] [--cigar] [--paf] [--unique exact|pair] [--coverage K]
-//              [--pileup K [--ins-slots S]] [--gfa [--unitigs K [--bubbles D]]]
+//              [--pileup K [--ins-slots S]] [--gfa [--unitigs K [--bubbles D]]] [--sam primary|all]
 //
 // Plays the part of reference darwin.cpp:451-646 for the GACT stage: owns the
 // globals gact.cpp reads, loads params.cfg and the two FASTA files, builds the
@@ -59,6 +59,12 @@
 // bubble found: source, sink, state (0 popped, 1 lost), n_vertices, n_path, n_removed, path_len, tab-separated; and the unitig
 // call of --unitigs runs over the arcs with arc_flags written into their flags -- its tip cut is the second round -- so
 // darwin.utg.gfa is made from the cleaned arcs.  darwin.gfa and every other file are as without the flag.
+// --sam primary|all (with --device-dsoft, not with --shard): every feeder places its reads on the device behind its run (and
+// behind --unique) -- the summaries of the records it writes, gact_hip_place_reads over the slot's own records and the window
+// of its reads, gact_hip_candidates_paths for the records to print -- and writes darwin.<thread>.sam, a SAM file of its own:
+// `@HD VN:1.6 SO:unsorted`, one `@SQ SN:<name> LN:<n>` per reference sequence in id order, `@PG ID:darwin_hip`, then per read in
+// id order its primary and supplementary lines (all: its secondary and extra lines too) in rank order, or one unmapped line
+// (gact_hip_format_sam, gact_hip_format_sam_unmapped).  Every other output byte is as without the flag.
 //
 // --device D: the GPU this process uses (the reference is single-device, cuda_host.cu:195).  --shard R/W: this
 // process is rank R of W -- it extends every W-th candidate (host filter) or the R-th contiguous range of reads
@@ -69,6 +75,7 @@
 //
 //   darwin_hip --selftest FILE   exercises AlignWithBT / Align_Batch / Align_Batch_GPU / GACT
 //                                on the cases in FILE and prints what they return.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -103,6 +110,7 @@ static int pileup_depth = 0;                     // --pileup K: min_depth of dar
 static int pileup_ins_slots = 0;                 // --ins-slots S: the inserted bases kept per position, 0: none
 static bool want_gfa = false;                    // --gfa: darwin.gfa, the overlap graph of the records written
 static int unitig_tips = -1;                     // --unitigs K: tip_reads of darwin.utg.gfa, -1: no unitigs
+static int sam_mode = 0;                         // --sam: 1 primary (and supplementary) lines, 2 all lines, 0: no SAM files
 static int bubble_dist = 0;                      // --bubbles D: max_dist of the bubble popping in front of the unitigs, 0: none
 // --coverage, --gfa: the records every feeder wrote a line for, in its file's order, and with --paf their summaries
 static std::vector<std::vector<gact_overlap> > cover_records;
@@ -211,6 +219,13 @@ static std::string paf_name(int cpu_id)
     return out.substr(0, out.size() - 3) + "paf";
 }
 
+// --sam: darwin.<thread>.sam beside darwin.<thread>.out
+static std::string sam_name(int cpu_id)
+{
+    const std::string out = out_name(cpu_id);
+    return out.substr(0, out.size() - 3) + "sam";
+}
+
 // darwin.cpp:314-398: the -DGPU build recodes every base in place before GACT_Batch; anything else stays
 static void recode_in_place(std::vector<std::string> &seqs)
 {
@@ -238,6 +253,101 @@ static void feeder(int cpu_id, const std::vector<Cand> *all, size_t lo, size_t h
                gap_open, gap_extend, fout);
     fout.close();
     print_stage("Time GACT calling", t0, now());                 // darwin.cpp:441
+}
+
+// --sam: reads [lo, hi) of a feeder placed on its slot, behind its run, and darwin.<thread>.sam.  o: the run's records as
+// fetched, keep: the ones --unique left; the records chosen for the placement are the ones the feeder writes a line for
+static void write_sam(gact_hip_engine *e, int slot, int cpu_id, int lo, int hi, const std::vector<gact_overlap> &o,
+                      const std::vector<char> &keep, int32_t nf)
+{
+    auto check = [](int rc, const char *what) {
+        if (rc != 0) { printf("\n%s failed: %s\n\n", what, gact_hip_last_error()); exit(-1); }
+    };
+    const int32_t n = (int32_t)o.size();
+    // 1 the summaries of the chosen records: the placement's intervals begin where the alignments do
+    std::vector<int32_t> chosen;
+    for (int32_t k = 0; k < n; k++)
+        if (o[(size_t)k].emitted && keep[(size_t)k]) chosen.push_back(k);
+    const int32_t n_chosen = (int32_t)chosen.size();
+    std::vector<gact_overlap> rec((size_t)n_chosen);
+    std::vector<gact_path_summary> sums((size_t)n_chosen);
+    if (n_chosen)
+        check(gact_hip_candidates_summaries(e, slot, n_chosen, chosen.data(), nf, same_file, rec.data(), sums.data()),
+              "gact_hip_candidates_summaries");
+    // 2 the placement, over the slot's own records and the window of this feeder's reads
+    std::vector<int32_t> lens((size_t)(hi - lo));
+    for (int r = lo; r < hi; r++) lens[(size_t)(r - lo)] = (int32_t)reads_seqs[(size_t)r].size();
+    std::vector<gact_placement> place((size_t)n_chosen);
+    std::vector<gact_read_place> reads((size_t)(hi - lo));
+    if (n_chosen)
+        check(gact_hip_place_reads(e, slot, n, nullptr, n_chosen, chosen.data(), sums.data(), lo, hi - lo, lens.data(), nullptr,
+                                   place.data(), reads.data()), "gact_hip_place_reads");
+    // 3 the alignments of the records to print, per read in id order, in rank order
+    std::vector<int32_t> order;                   // positions in `chosen`
+    for (int32_t k = 0; k < n_chosen; k++) {
+        const int kind = place[(size_t)k].kind;
+        if (kind == GACT_PLACE_PRIMARY || kind == GACT_PLACE_SUPPLEMENTARY ||
+            (sam_mode == 2 && (kind == GACT_PLACE_SECONDARY || kind == GACT_PLACE_EXTRA)))
+            order.push_back(k);
+    }
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+        const gact_overlap &ra = o[(size_t)chosen[(size_t)a]], &rb = o[(size_t)chosen[(size_t)b]];
+        return ra.query_id != rb.query_id ? ra.query_id < rb.query_id : place[(size_t)a].rank < place[(size_t)b].rank;
+    });
+    std::vector<int32_t> sel(order.size());
+    size_t room = 1;
+    for (size_t k = 0; k < order.size(); k++) {
+        const gact_overlap &r = o[(size_t)chosen[(size_t)order[k]]];
+        sel[k] = chosen[(size_t)order[k]];
+        room += (size_t)(r.ae - r.ab) + (size_t)(r.be - r.bb);
+    }
+    std::vector<gact_overlap> prec(sel.size());
+    std::vector<gact_path> paths(sel.size());
+    std::vector<uint32_t> ops(room);
+    if (!sel.empty()) {
+        int64_t needed = 0;
+        int rc = gact_hip_candidates_paths(e, slot, (int32_t)sel.size(), sel.data(), nf, same_file, prec.data(), paths.data(), ops.data(),
+                                           (int64_t)ops.size(), &needed);
+        if (rc == GACT_HIP_EINVAL && needed > (int64_t)ops.size()) {
+            ops.resize((size_t)needed);
+            rc = gact_hip_candidates_paths(e, slot, (int32_t)sel.size(), sel.data(), nf, same_file, prec.data(), paths.data(), ops.data(),
+                                           (int64_t)ops.size(), &needed);
+        }
+        check(rc, "gact_hip_candidates_paths");
+    }
+    // 4 the file: a SAM file of its own
+    std::ofstream fsam(sam_name(cpu_id));
+    fsam << "@HD\tVN:1.6\tSO:unsorted\n";
+    for (size_t r = 0; r < reference_seqs.size(); r++)
+        fsam << "@SQ\tSN:" << reference_descrips[r][0] << "\tLN:" << reference_seqs[r].size() << "\n";
+    fsam << "@PG\tID:darwin_hip\tPN:darwin_hip\n";
+    std::vector<char> line;
+    auto put = [&](int64_t len) {                 // false: the line needs more room than it had
+        if (len < 0) { printf("\ngact_hip_format_sam failed: %s\n\n", gact_hip_last_error()); exit(-1); }
+        if (len >= (int64_t)line.size()) { line.resize((size_t)len + 1); return false; }
+        fsam.write(line.data(), (std::streamsize)len);
+        return true;
+    };
+    size_t next = 0;
+    for (int r = lo; r < hi; r++) {
+        const std::string &seq = reads_seqs[(size_t)r];
+        const char *name = reads_descrips[(size_t)r][0].c_str();
+        line.resize(std::max(line.size(), 2 * seq.size() + 1024));
+        const size_t first = next;
+        for (; next < order.size() && o[(size_t)sel[next]].query_id == r; next++) {
+            const gact_overlap &rr = o[(size_t)sel[next]];
+            const gact_path &p = paths[next];
+            for (int attempt = 0; attempt < 2; attempt++)
+                if (put(gact_hip_format_sam(&rr, ops.data() + p.op_offset, p.n_ops, &place[(size_t)order[next]], name,
+                                            (const uint8_t *)seq.data(), (int64_t)seq.size(), reference_descrips[(size_t)rr.ref_id][0].c_str(),
+                                            line.data(), (int64_t)line.size())))
+                    break;
+        }
+        if (next == first)
+            for (int attempt = 0; attempt < 2; attempt++)
+                if (put(gact_hip_format_sam_unmapped(name, (const uint8_t *)seq.data(), (int64_t)seq.size(), line.data(), (int64_t)line.size())))
+                    break;
+    }
 }
 
 // --device-dsoft: reads [lo, hi) are filtered and extended on the device, slot s.slot
@@ -356,6 +466,7 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
         }
         next++;
     }
+    if (sam_mode) write_sam(e, s.slot, cpu_id, lo, hi, o, keep, nf);
     print_stage("Time GACT calling", t1, now());                 // darwin.cpp:441
 }
 
@@ -724,7 +835,7 @@ int main(int argc, char *argv[])
     if (argc >= 3 && strcmp(argv[1], "--selftest") == 0) return selftest(argv[2]);
     if (argc < 4) {
         fprintf(stderr, "Usage: darwin_hip <REFERENCE>.fasta <READS>.fasta CPU_THREADS --candidates FILE "
-                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K [--ins-slots S]] [--gfa [--unitigs K [--bubbles D]]]]\n");
+                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K [--ins-slots S]] [--gfa [--unitigs K [--bubbles D]]] [--sam primary|all]]\n");
         return 1;
     }
     std::string cand_path, dump_path, cfg_path = "params.cfg", gather_id;
@@ -783,6 +894,12 @@ int main(int argc, char *argv[])
             if (!*v || *end || k < 1 || k > (1L << 30)) { fprintf(stderr, "--bubbles wants an integer from 1 to 2^30, not '%s'\n", v); return 1; }
             bubble_dist = (int)k;
         }
+        else if (!strcmp(argv[a], "--sam")) {
+            const char *v = a + 1 < argc ? argv[++a] : "";
+            if (!strcmp(v, "primary")) sam_mode = 1;
+            else if (!strcmp(v, "all")) sam_mode = 2;
+            else { fprintf(stderr, "--sam wants primary or all, not '%s'\n", v); return 1; }
+        }
         else if (!strcmp(argv[a], "--rccl-gather") && a + 1 < argc) gather_id = argv[++a];
         else if (!strcmp(argv[a], "--device") && a + 1 < argc) setenv("GACT_HIP_DEVICE", argv[++a], 1);   // read by GPU_init
         else if (!strcmp(argv[a], "--shard") && a + 1 < argc) {
@@ -840,6 +957,12 @@ int main(int argc, char *argv[])
     if (unitig_tips >= 0 && !want_gfa) {
         // the unitigs are made from what the graph call of --gfa returns
         fprintf(stderr, "--unitigs: only with --gfa\n");
+        return 1;
+    }
+    if (sam_mode && (!device_dsoft || shard_given || !gather_id.empty())) {
+        // a read is placed among ALL its records, which one feeder's slot holds behind the device filter; the ranks of a sharded job
+        // split the reads, and every rank's files would need a header and a name of their own: left to the caller
+        fprintf(stderr, "--sam: only with --device-dsoft, and not with --shard\n");
         return 1;
     }
     std::map<std::string, double> cfg = parse_cfg(cfg_path);

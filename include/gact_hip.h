@@ -381,6 +381,74 @@ int gact_hip_read_coverage(gact_hip_engine *e, int slot, int32_t n, const gact_o
 typedef struct { float device_ms; int32_t reads; int64_t intervals, positions, scratch_bytes; } gact_cover_stats;
 int gact_hip_last_cover_stats(gact_hip_engine *e, int slot, gact_cover_stats *stats);
 
+/* ---- placement: where every read goes -- primary, supplementary and secondary records, and a MAPQ ----
+ * What a user who maps reads against a reference or against contigs asks first: where does this read go, how sure is that, is
+ * the read split between two places.  GACT_SELECT_PAIR answers per (ref, query, strand) only; this entry orders ALL records of
+ * a read, across references and strands, and says of each what a mapper says of it (csrc/gact_place.hpp).  The records of a
+ * query read sit together on the slot that ran its batch (gact_hip_dsoft_query(first_query, n_queries)), so a feeder places its
+ * reads behind its run, before anything is fetched.  The rule, all integers, the same on every call and slot:
+ *
+ *   chosen   records sel[0..n_sel) of the n records; sel == NULL: all of [0, n) (n_sel is not read then, but for its sign).  k is
+ *            a record's position in that list; an index that sel repeats is a chosen record of its own; sums[k], when given,
+ *            belongs to chosen record k, as in gact_hip_read_coverage.
+ *   counted  a chosen record is counted iff it is emitted and its query interval is not empty: the interval GACT_COVER_QUERY
+ *            puts on the ORIGINAL read -- [bb', be) for comp == 0, [len - be, len - bb') for comp == 1, bb' = be - (n_eq + n_x +
+ *            ins_bases) when sums is given, else bb -- clipped to [0, len).  A record that is not counted gets kind
+ *            GACT_PLACE_NONE, mapq 0, parent -1 and rank -1.
+ *   order    the counted records of one query_id, by 1. higher score, 2. larger (ae - ab) + (be - bb), 3. lower k.  rank is a
+ *            record's position in that order, from 0.
+ *   walk     through the read's records in rank order, with a list of PARENTS in the order they were made.  The current record
+ *            t is tested against every parent p in that order: ov = min(e_t, e_p) - max(b_t, b_p), and p MASKS t iff ov > 0 and
+ *            1000 * ov >= mask_permille * min(e_t - b_t, e_p - b_p) (64-bit; abutting intervals never mask).  If some parent
+ *            masks t: t is GACT_PLACE_SECONDARY and its parent is the k of the first parent that masks it.  Else, with fewer
+ *            than GACT_PLACE_MAX_PARENTS parents, t becomes a parent: GACT_PLACE_PRIMARY if it is the read's first one, else
+ *            GACT_PLACE_SUPPLEMENTARY; its parent is its own k.  Else t is GACT_PLACE_EXTRA: parent its own k, not a parent,
+ *            and nothing is tested against it.
+ *   mapq     of a parent: s1 = its own score, s2 = the highest score among its secondaries (0 without any), clamped to
+ *            [0, s1] (to 0 when s1 < 0); mapq = s1 <= 0 ? 0 : mapq_cap * (s1 - s2) / s1, floored, in 64 bits.  Secondaries,
+ *            extras and NONE get 0.  A STATED RULE WITH TWO PARAMETERS, NOT A CALIBRATED MODEL: mapq says how far the best
+ *            competing record of the same stretch falls short in score, nothing about an error probability.  The defaults follow
+ *            minimap2's conventions (mask at half the shorter interval, MAPQ up to 60); they are parameters, not measurements.
+ *
+ *   records, sel, n_sel, sums   as in gact_hip_read_coverage; records == NULL: the slot's device array behind its last run
+ *   window   reads [read_first, read_first + n_reads) of the query set; read_lens[i] is the length of read read_first + i
+ *   place    NULL, or one gact_placement per chosen record
+ *   reads    NULL, or one gact_read_place per read of the window: n_records = its counted records, primary = the chosen index k
+ *            of its primary or -1, the counts per kind, score / second / mapq = the primary's s1, s2 and mapq.  A read without
+ *            counted records is all zero with primary = -1.
+ * Refused with GACT_HIP_EINVAL: mask_permille outside [0, 1000], mapq_cap outside [0, 255], negative n (or n > 2^30), n_sel,
+ * n_reads or read_first, NULL read_lens with n_reads > 0, a negative length, records == NULL on a slot without records or with
+ * n beyond them, an index in sel outside [0, n).  Refused with GACT_HIP_ERANGE: an emitted chosen record whose query_id lies
+ * outside the window (its interval cannot be made without its read's length); the check is made on the device before the id
+ * is used as an index.  On a refusal place and reads are untouched.  n_reads == 0 returns 0 and writes nothing; no chosen
+ * record (n_sel == 0, or n == 0 without sel) returns 0 with every reads[i] empty.
+ * Synchronous on the slot's stream; the slot's records and its run, paths, summaries, select, cover and graph statistics stay
+ * as they were.  Device memory of its own, one allocation per slot, grown on demand: 80 bytes per chosen record and 44 per
+ * read, 56 per host record, 4 per sel entry, 32 per summary.  One wave places one read, and ranks its m records in about
+ * m * m / 64 steps: right for reads against a reference (tens of records), correct and slow for a read with many thousands. */
+#define GACT_PLACE_NONE          0
+#define GACT_PLACE_PRIMARY       1
+#define GACT_PLACE_SUPPLEMENTARY 2
+#define GACT_PLACE_SECONDARY     3
+#define GACT_PLACE_EXTRA         4
+#define GACT_PLACE_MAX_PARENTS   64
+#define GACT_PLACE_DEFAULT_MASK_PERMILLE 500
+#define GACT_PLACE_DEFAULT_MAPQ_CAP      60
+typedef struct { int32_t mask_permille, mapq_cap; } gact_place_params;
+typedef struct { int32_t kind, mapq, parent, rank; } gact_placement;                 /* 16 bytes, one per chosen record */
+typedef struct { int32_t n_records, primary, n_supplementary, n_secondary, n_extra,
+                 score, second, mapq; } gact_read_place;                             /* 32 bytes, one per read of the window */
+int gact_hip_place_reads(gact_hip_engine *e, int slot, int32_t n, const gact_overlap *records,
+                         int32_t n_sel, const int32_t *sel, const gact_path_summary *sums,
+                         int32_t read_first, int32_t n_reads, const int32_t *read_lens,
+                         const gact_place_params *params /* NULL: defaults */,
+                         gact_placement *place, gact_read_place *reads);
+/* What the slot's last gact_hip_place_reads call that got as far as the device did: HIP events on the slot's stream around the
+ * whole call (copies and kernels), the reads of the window, the most counted records on one read, the counted records, the
+ * parents (primaries and supplementaries), secondaries and extras among them, and the device memory the call holds for itself. */
+typedef struct { float device_ms; int32_t reads, max_records, reserved; int64_t counted, parents, secondaries, extras, scratch_bytes; } gact_place_stats;
+int gact_hip_last_place_stats(gact_hip_engine *e, int slot, gact_place_stats *stats);
+
 /* ---- overlap graph: containment, bidirected dovetail arcs and their transitive flags, made on the device ----
  * The step between an all-vs-all overlap set and an assembler's layout stage (miniasm's): every overlap is classified against the
  * clipped reads, contained reads are marked, every dovetail overlap between two reads that are not contained becomes an arc and
@@ -917,6 +985,26 @@ int gact_hip_format_overlap(const gact_overlap *o, const char *ref_name, const c
  * The line ends in '\n'; a caller that appends a cg:Z: tag overwrites it.  GACT_HIP_EINVAL for a summary without columns. */
 int gact_hip_format_paf(const gact_overlap *o, const gact_path_summary *s, const char *query_name, int64_t query_len,
                         const char *ref_name, int64_t ref_len, char *buf, int32_t cap);
+
+/* One SAM line for a record, its ops (gact_hip_candidates_paths: n_ops words len << 4 | GACT_PATH_OP_*, left to right) and its
+ * placement (gact_hip_place_reads); no engine, no device.  Returns the line's length as snprintf does: with cap too small
+ * (cap <= length) nothing useful is in buf, and the caller asks again with room for length + 1.
+ *   QNAME FLAG RNAME POS MAPQ CIGAR * 0 0 SEQ * AS:i:<score> NM:i:<X + I + D columns>\n
+ *   FLAG   16 for comp == 1, + 256 for GACT_PLACE_SECONDARY and GACT_PLACE_EXTRA, + 2048 for GACT_PLACE_SUPPLEMENTARY
+ *   POS    ae - (the ref-consuming columns of ops: =, X, D) + 1; MAPQ is p->mapq
+ *   CIGAR  the ops as =, X, I, D (the engine's I consumes the query, as SAM's does), a clip of be - (the query-consuming columns:
+ *          =, X, I) in front -- where the alignment begins on the record's strand -- and a clip of query_len - be behind; clips of
+ *          length 0 are omitted; S for a primary, H for the others
+ *   SEQ    primary: the whole read, reverse-complemented for comp == 1 (case kept; the complement of anything outside acgtACGT
+ *          is N).  Supplementary: the aligned stretch of that only.  Secondary and extra: *
+ * query_seq is the ORIGINAL read (query_len bytes), whatever comp says; it is not read for a secondary or an extra.
+ * GACT_HIP_EINVAL: n_ops <= 0, kind GACT_PLACE_NONE (or none of the kinds), an op that is none of the four, an alignment that
+ * begins in front of the read or ends behind it.
+ * gact_hip_format_sam_unmapped writes the line of a read without a placement: QNAME 4 * 0 0 * * 0 0 SEQ *\n. */
+int64_t gact_hip_format_sam(const gact_overlap *o, const uint32_t *ops, int32_t n_ops, const gact_placement *p,
+                            const char *query_name, const uint8_t *query_seq /* the ORIGINAL read */, int64_t query_len,
+                            const char *ref_name, char *buf, int64_t cap);
+int64_t gact_hip_format_sam_unmapped(const char *query_name, const uint8_t *query_seq, int64_t query_len, char *buf, int64_t cap);
 
 #ifdef __cplusplus
 }
