@@ -319,6 +319,10 @@ struct Slot {
     PassScratch<gact_unitig_stats> unitig;
     // gact_hip_pop_bubbles (gact_bubble.hpp): arcs | reads | lens | clip | skip | degrees, found, gone, bits, counters, flag | first | owner | read_bubble | bubbles
     PassScratch<gact_bubble_stats> bubble;
+    // gact_hip_prune_overlaps (gact_clean.hpp): arcs | reads | lens | clip | skip | degrees, bits, counters, flag | first | best
+    PassScratch<gact_prune_stats> prune;
+    // gact_hip_clean_graph (gact_clean.hpp): arcs | reads | lens | clip | degrees, found, gone, bits, counters | flag | first | links | cut, owner | ranking records | bubbles | state
+    PassScratch<gact_clean_stats> clean;
     // gact_hip_place_reads (gact_place.hpp): host records | sel | sums | lens | first | fill | flag, counters | reads | items | CSR | ranked | place | spans
     PassScratch<gact_place_stats> place;
     // gact_hip_pileup_add (gact_pileup.hpp): the events around this slot's adds; the counts are the engine's (Pileup)
@@ -338,6 +342,8 @@ struct Slot {
         graph.release();
         unitig.release();
         bubble.release();
+        prune.release();
+        clean.release();
         place.release();
         pile_timer.release();
         if (d_counter) (void)hipFree(d_counter);
@@ -1955,6 +1961,7 @@ int gact_hip_measure_valu_rate(gact_hip_engine *e, double *lane_ops_per_s)
 #include "gact_pileup.hpp"       // gact_hip_pileup_*: per-base pileup and consensus from the alignments' columns
 #include "gact_unitig.hpp"       // gact_hip_unitigs: tip cut, chain ranking, layout and bases of the graph's unitigs, behind every other kernel
 #include "gact_bubble.hpp"       // gact_hip_pop_bubbles: the bubbles of the graph, one wave per search, on the unitigs' first kernels
+#include "gact_clean.hpp"        // gact_hip_prune_overlaps, gact_hip_clean_graph: the weak arcs, and the rounds of tips, bubbles and weak arcs on resident arcs
 #include "gact_place.hpp"        // gact_hip_place_reads: primary, supplementary, secondary and MAPQ of every read, one wave per read
 
 #ifdef GACT_STAMPS

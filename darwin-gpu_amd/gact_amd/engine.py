@@ -58,6 +58,16 @@ BUBBLE_POPPED, BUBBLE_LOST = 0, 1
 GRAPH_ARC_BUBBLE = 4
 BUBBLE_DEFAULT_MAX_DIST = 50000
 BUBBLE_MAX_VERTICES = 64
+# the weak arcs and the cleaning rounds (include/gact_hip.h gact_hip_prune_overlaps, gact_hip_clean_graph): a step of the log, a read's state
+GRAPH_ARC_TIP, GRAPH_ARC_SHORT = 8, 16
+PRUNE_DEFAULT_RATIO_PERMILLE = 500
+CLEAN_TIPS, CLEAN_BUBBLES, CLEAN_PRUNE = 0, 1, 2
+CLEAN_KINDS = ("tips", "bubbles", "prune")
+CLEAN_KEPT, CLEAN_BUBBLE = 0, 4                      # (states 1 .. 3 are UNITIG_CONTAINED, UNITIG_EMPTY, UNITIG_TIP)
+CLEAN_STEP_DTYPE = np.dtype([(n, "<i4") for n in ("kind", "param", "reads_removed", "examined")] +
+                            [(n, "<i8") for n in ("arcs_removed", "arcs_left")])
+CLEAN_READ_DTYPE = np.dtype([("state", "<i4"), ("step", "<i4")])
+assert CLEAN_STEP_DTYPE.itemsize == 32 and CLEAN_READ_DTYPE.itemsize == 8
 # the placement of reads (include/gact_hip.h gact_hip_place_reads): one record per chosen record, one per read of the window
 PLACE_DTYPE = np.dtype([(n, "<i4") for n in ("kind", "mapq", "parent", "rank")])
 READ_PLACE_DTYPE = np.dtype([(n, "<i4") for n in ("n_records", "primary", "n_supplementary", "n_secondary", "n_extra", "score",
@@ -212,6 +222,34 @@ class BubbleStats(C.Structure):
     _fields_ = [("device_ms", C.c_float)] + \
                [(n, C.c_int32) for n in ("reads", "sources", "found", "popped", "lost", "reads_removed")] + \
                [("working_arcs", C.c_int64), ("arcs_removed", C.c_int64), ("by_fail", C.c_int64 * 5), ("scratch_bytes", C.c_int64)]
+
+
+class PruneParams(C.Structure):
+    """the default is GACT_PRUNE_DEFAULT_RATIO_PERMILLE"""
+    _fields_ = [("ratio_permille", C.c_int32)]
+
+    def __init__(self, ratio_permille=PRUNE_DEFAULT_RATIO_PERMILLE):
+        super().__init__(ratio_permille)
+
+
+class PruneStats(C.Structure):
+    _fields_ = [("device_ms", C.c_float)] + [(n, C.c_int32) for n in ("reads", "examined", "bared")] + \
+               [(n, C.c_int64) for n in ("working_arcs", "weak", "arcs_removed", "scratch_bytes")]
+
+
+class CleanParams(C.Structure):
+    """the defaults are the ones gact_hip_clean_graph takes for NULL"""
+    _fields_ = [(n, C.c_int32) for n in ("tip_reads", "max_dist", "max_vertices", "ratio_lo_permille", "ratio_hi_permille",
+                                         "n_ratios", "max_passes")]
+
+    def __init__(self, tip_reads=UNITIG_DEFAULT_TIP_READS, max_dist=BUBBLE_DEFAULT_MAX_DIST, max_vertices=BUBBLE_MAX_VERTICES,
+                 ratio_lo_permille=500, ratio_hi_permille=700, n_ratios=3, max_passes=4):
+        super().__init__(tip_reads, max_dist, max_vertices, ratio_lo_permille, ratio_hi_permille, n_ratios, max_passes)
+
+
+class CleanStats(C.Structure):
+    _fields_ = [("device_ms", C.c_float)] + [(n, C.c_int32) for n in ("reads", "steps", "passes", "reads_tip", "reads_bubble")] + \
+               [("arcs_removed", C.c_int64 * 3), ("arcs_left", C.c_int64), ("scratch_bytes", C.c_int64)]
 
 
 class PileupStats(C.Structure):
@@ -427,6 +465,18 @@ def load():
     except AttributeError:
         pass
     try:
+        L.gact_hip_prune_overlaps.argtypes = [vp, C.c_int, i32, vp, vp, vp, C.c_int64, vp, vp, C.POINTER(PruneParams), vp, vp]
+        L.gact_hip_prune_overlaps.restype = C.c_int
+        L.gact_hip_last_prune_stats.argtypes = [vp, C.c_int, C.POINTER(PruneStats)]
+        L.gact_hip_last_prune_stats.restype = C.c_int
+        L.gact_hip_clean_graph.argtypes = [vp, C.c_int, i32, vp, vp, vp, C.c_int64, vp, C.POINTER(CleanParams), vp, vp, vp, C.c_int64,
+                                           C.POINTER(C.c_int64)]
+        L.gact_hip_clean_graph.restype = C.c_int
+        L.gact_hip_last_clean_stats.argtypes = [vp, C.c_int, C.POINTER(CleanStats)]
+        L.gact_hip_last_clean_stats.restype = C.c_int
+    except AttributeError:
+        pass
+    try:
         L.gact_hip_pileup_begin.argtypes = [vp, i32, i32]
         L.gact_hip_pileup_add.argtypes = [vp, C.c_int, i32, vp, i32, C.c_int]
         L.gact_hip_pileup_finish.argtypes = [vp, i32, vp, vp, vp]
@@ -477,6 +527,7 @@ EXPORTS = ("gact_hip_create", "gact_hip_destroy", "gact_hip_last_error", "gact_h
            "gact_hip_last_summaries_stats", "gact_hip_format_paf", "gact_hip_select_overlaps", "gact_hip_last_select_stats",
            "gact_hip_read_coverage", "gact_hip_last_cover_stats", "gact_hip_overlap_graph", "gact_hip_last_graph_stats",
            "gact_hip_unitigs", "gact_hip_last_unitig_stats", "gact_hip_pop_bubbles", "gact_hip_last_bubble_stats",
+           "gact_hip_prune_overlaps", "gact_hip_last_prune_stats", "gact_hip_clean_graph", "gact_hip_last_clean_stats",
            "gact_hip_pileup_begin", "gact_hip_pileup_add", "gact_hip_pileup_finish", "gact_hip_last_pileup_stats",
            "gact_hip_pileup_begin_ins", "gact_hip_pileup_corrected", "gact_hip_last_pileup_ins_stats",
            "gact_hip_place_reads", "gact_hip_last_place_stats", "gact_hip_format_sam", "gact_hip_format_sam_unmapped")
@@ -910,6 +961,69 @@ class Engine:
         found, popped and lost, reads removed, arcs of the working set, arcs removed, the failed searches by their first
         failure (a list of 5: open, dead, twice, dist, many), device bytes the call holds"""
         return self._stats(self.L.gact_hip_last_bubble_stats, BubbleStats, slot)
+
+    def _graph_args(self, read_lens, reads, arcs, clip, skip=None):
+        """the arrays of a call on an overlap graph, as the C-ABI takes them"""
+        read_lens = np.ascontiguousarray(read_lens, dtype=np.int32)
+        reads = np.ascontiguousarray(reads, dtype=GRAPH_READ_DTYPE)
+        arcs = np.ascontiguousarray(arcs, dtype=GRAPH_ARC_DTYPE)
+        n = len(read_lens)
+        assert len(reads) == n
+        if clip is not None:
+            clip = np.ascontiguousarray(clip, dtype=np.int32).reshape(-1)
+            assert len(clip) == 2 * n
+        if skip is not None:
+            skip = np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8)
+            assert len(skip) == n
+        return read_lens, reads, arcs, clip, skip, n
+
+    def prune_overlaps(self, read_lens, reads, arcs, clip=None, skip=None, ratio_permille=PRUNE_DEFAULT_RATIO_PERMILLE, best=False,
+                       slot=0):
+        """the weak arcs of an overlap graph, marked on the device: arc_flags -- per arc its flags with GRAPH_ARC_SHORT set where
+        the arc's overlap, or its complement's, is below ratio_permille thousandths of the best one of its vertex -- or
+        (arc_flags, vertex_best) with the best overlap of every examined vertex (0 elsewhere) when `best` is set.  read_lens,
+        clip, reads, arcs and skip as pop_bubbles takes them (include/gact_hip.h gact_hip_prune_overlaps)"""
+        read_lens, reads, arcs, clip, skip, n = self._graph_args(read_lens, reads, arcs, clip, skip)
+        params = PruneParams(int(ratio_permille))
+        arc_flags = np.zeros(len(arcs), dtype=np.int32)
+        vertex_best = np.zeros(2 * n, dtype=np.int32) if best else None
+        self._check(self.L.gact_hip_prune_overlaps(self.h, slot, n, _ptr(read_lens), _ptr(clip), _ptr(reads), len(arcs), _ptr(arcs),
+                                                   _ptr(skip), C.byref(params), _ptr(arc_flags), _ptr(vertex_best)))
+        return (arc_flags, vertex_best) if best else arc_flags
+
+    def last_prune_stats(self, slot=0):
+        """the slot's last prune call: device ms (HIP events around the whole call), reads, vertices examined, vertices that
+        lost their last arc, arcs of the working set, weak arcs, arcs removed, device bytes the call holds"""
+        return self._stats(self.L.gact_hip_last_prune_stats, PruneStats, slot)
+
+    def clean_graph(self, read_lens, reads, arcs, clip=None, tip_reads=UNITIG_DEFAULT_TIP_READS, max_dist=BUBBLE_DEFAULT_MAX_DIST,
+                    max_vertices=BUBBLE_MAX_VERTICES, ratios=(500, 700, 3), max_passes=4, slot=0):
+        """the cleaning rounds of an overlap graph on the device -- tips and bubbles until a pass removes nothing, then the weak
+        arcs at the ratios (lo, hi, n) in thousandths, settling again after every drop: (arc_flags, read_state, steps) -- per arc
+        its flags with GRAPH_ARC_TIP, GRAPH_ARC_BUBBLE and GRAPH_ARC_SHORT set where a step removed it, one CLEAN_READ_DTYPE
+        record per read, one CLEAN_STEP_DTYPE record per step made.  arc_flags written into arcs["flags"] is what unitigs takes
+        (include/gact_hip.h gact_hip_clean_graph)"""
+        read_lens, reads, arcs, clip, _, n = self._graph_args(read_lens, reads, arcs, clip)
+        lo, hi, n_ratios = (int(v) for v in ratios)
+        params = CleanParams(int(tip_reads), int(max_dist), int(max_vertices), lo, hi, n_ratios, int(max_passes))
+        arc_flags = np.zeros(len(arcs), dtype=np.int32)
+        read_state = np.zeros(n, dtype=CLEAN_READ_DTYPE)
+        n_steps = C.c_int64()
+        cap = 16                                    # (a graph that settles at once takes 2 + 3 steps)
+        for attempt in range(2):
+            steps = np.zeros(cap, dtype=CLEAN_STEP_DTYPE)
+            rc = self.L.gact_hip_clean_graph(self.h, slot, n, _ptr(read_lens), _ptr(clip), _ptr(reads), len(arcs), _ptr(arcs),
+                                             C.byref(params), _ptr(arc_flags), _ptr(read_state), _ptr(steps), cap, C.byref(n_steps))
+            if rc == 0 or attempt or n_steps.value <= cap:
+                break
+            cap = n_steps.value                     # (EINVAL with *n_steps filled: once more with room for them)
+        self._check(rc)
+        return arc_flags, read_state, steps[:n_steps.value].copy()
+
+    def last_clean_stats(self, slot=0):
+        """the slot's last clean call: device ms (HIP events around the whole call), reads, steps, passes, reads removed as tips
+        and by bubbles, arcs removed by kind (a list of 3: tips, bubbles, prune), arcs left, device bytes the call holds"""
+        return self._stats(self.L.gact_hip_last_clean_stats, CleanStats, slot)
 
     def pileup_begin(self, read_first=0, n_reads=None, ins_slots=0):
         """opens the pileup window: reads [read_first, read_first + n_reads) of SET_REF (n_reads None: to the set's end), counts

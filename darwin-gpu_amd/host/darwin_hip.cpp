@@ -3,7 +3,7 @@
 //   darwin_hip <REF.fasta> <READS.fasta> CPU_THREADS [--params params.cfg]
 //              [--candidates FILE | --dump-candidates FILE [--dsoft-only]] [--device-dsoft]
 //              [--device D] [--shard R/W] [--recode] [--cigar] [--paf] [--unique exact|pair] [--coverage K]
-//              [--pileup K [--ins-slots S]] [--gfa [--unitigs K [--bubbles D]]] [--sam primary|all]
+//              [--pileup K [--ins-slots S]] [--gfa [--unitigs K [--bubbles D] [--clean LO:HI:N]]] [--sam primary|all]
 //
 // Plays the part of reference darwin.cpp:451-646 for the GACT stage: owns the
 // globals gact.cpp reads, loads params.cfg and the two FASTA files, builds the
@@ -59,6 +59,11 @@
 // bubble found: source, sink, state (0 popped, 1 lost), n_vertices, n_path, n_removed, path_len, tab-separated; and the unitig
 // call of --unitigs runs over the arcs with arc_flags written into their flags -- its tip cut is the second round -- so
 // darwin.utg.gfa is made from the cleaned arcs.  darwin.gfa and every other file are as without the flag.
+// --clean LO:HI:N (with --gfa --unitigs K, K >= 1; integers, 0 <= LO <= HI <= 1000 per mille, 0 <= N <= 16 ratios): behind the graph
+// call one gact_hip_clean_graph call with tip_reads = K, max_dist = D of --bubbles (which then only supplies it; without it the
+// default) and the ratios LO .. HI in N steps; darwin.clean.tsv gets one line per step of its log: index, kind (tips, bubbles or
+// prune), param, reads_removed, examined, arcs_removed, arcs_left, tab-separated; darwin.bubbles.tsv is not written; and the
+// unitig call of --unitigs runs over the arcs with arc_flags written into their flags.  Every other file is as without the flag.
 // --sam primary|all (with --device-dsoft, not with --shard): every feeder places its reads on the device behind its run (and
 // behind --unique) -- the summaries of the records it writes, gact_hip_place_reads over the slot's own records and the window
 // of its reads, gact_hip_candidates_paths for the records to print -- and writes darwin.<thread>.sam, a SAM file of its own:
@@ -111,6 +116,7 @@ static int pileup_ins_slots = 0;                 // --ins-slots S: the inserted 
 static bool want_gfa = false;                    // --gfa: darwin.gfa, the overlap graph of the records written
 static int unitig_tips = -1;                     // --unitigs K: tip_reads of darwin.utg.gfa, -1: no unitigs
 static int sam_mode = 0;                         // --sam: 1 primary (and supplementary) lines, 2 all lines, 0: no SAM files
+static int clean_lo = -1, clean_hi = 0, clean_n = 0;   // --clean LO:HI:N: the ratios of the cleaning rounds in front of the unitigs, lo < 0: none
 static int bubble_dist = 0;                      // --bubbles D: max_dist of the bubble popping in front of the unitigs, 0: none
 // --coverage, --gfa: the records every feeder wrote a line for, in its file's order, and with --paf their summaries
 static std::vector<std::vector<gact_overlap> > cover_records;
@@ -584,6 +590,34 @@ static int pop_bubbles(gact_hip_engine *e, const std::vector<int32_t> &lens, con
     return 0;
 }
 
+// --clean: behind the graph call, on slot 0: the cleaning rounds, then darwin.clean.tsv; arc_flags goes into the flags of `arcs`,
+// which the unitig call of --unitigs takes
+static int clean_graph(gact_hip_engine *e, const std::vector<int32_t> &lens, const std::vector<int32_t> &clip,
+                       const std::vector<gact_graph_read> &reads, std::vector<gact_graph_arc> &arcs, int64_t n_arcs)
+{
+    const size_t n = lens.size();
+    const gact_clean_params params = {unitig_tips, bubble_dist ? bubble_dist : GACT_BUBBLE_DEFAULT_MAX_DIST, GACT_BUBBLE_MAX_VERTICES,
+                                      clean_lo, clean_hi, clean_n, 4};
+    std::vector<gact_clean_step> steps((size_t)(params.n_ratios + 1) * (2 * params.max_passes + 1));   // (always suffices)
+    std::vector<gact_clean_read> state(n + 1);
+    std::vector<int32_t> arc_flags((size_t)n_arcs + 1);
+    int64_t n_steps = 0;
+    const int rc = gact_hip_clean_graph(e, 0, (int32_t)n, lens.data(), clip.empty() ? nullptr : clip.data(), reads.data(), n_arcs,
+                                        arcs.data(), &params, arc_flags.data(), state.data(), steps.data(), (int64_t)steps.size(), &n_steps);
+    if (rc != 0) { printf("\ngact_hip_clean_graph failed: %s\n\n", gact_hip_last_error()); return 1; }
+    FILE *f = fopen("darwin.clean.tsv", "w");
+    if (!f) { fprintf(stderr, "--clean: cannot write darwin.clean.tsv\n"); return 1; }
+    static const char *const kinds[3] = {"tips", "bubbles", "prune"};
+    for (int64_t j = 0; j < n_steps; j++) {
+        const gact_clean_step &s = steps[(size_t)j];
+        fprintf(f, "%lld\t%s\t%d\t%d\t%d\t%lld\t%lld\n", (long long)j, kinds[s.kind], s.param, s.reads_removed, s.examined,
+                (long long)s.arcs_removed, (long long)s.arcs_left);
+    }
+    fclose(f);
+    for (int64_t k = 0; k < n_arcs; k++) arcs[(size_t)k].flags = arc_flags[(size_t)k];
+    return 0;
+}
+
 // --gfa: one call over the records all feeders kept, on slot 0, then darwin.gfa.  clip: the spans of --coverage, or empty
 static int write_gfa(gact_hip_engine *e, const std::vector<int32_t> &clip)
 {
@@ -615,7 +649,8 @@ static int write_gfa(gact_hip_engine *e, const std::vector<int32_t> &clip)
                 reads_descrips[(size_t)(a.v >> 1)][0].c_str(), a.v & 1 ? '-' : '+', std::min(a.ov_u, a.ov_v), a.len);
     }
     fclose(f);
-    if (bubble_dist && pop_bubbles(e, lens, clip, reads, arcs, n_arcs)) return 1;      // (darwin.gfa is written: the arcs may change)
+    // (darwin.gfa is written: the arcs may change)
+    if (clean_lo >= 0 ? clean_graph(e, lens, clip, reads, arcs, n_arcs) : bubble_dist && pop_bubbles(e, lens, clip, reads, arcs, n_arcs)) return 1;
     return unitig_tips >= 0 ? write_unitigs(e, lens, clip, reads, arcs, n_arcs) : 0;
 }
 
@@ -835,7 +870,7 @@ int main(int argc, char *argv[])
     if (argc >= 3 && strcmp(argv[1], "--selftest") == 0) return selftest(argv[2]);
     if (argc < 4) {
         fprintf(stderr, "Usage: darwin_hip <REFERENCE>.fasta <READS>.fasta CPU_THREADS --candidates FILE "
-                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K [--ins-slots S]] [--gfa [--unitigs K [--bubbles D]]] [--sam primary|all]]\n");
+                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K [--ins-slots S]] [--gfa [--unitigs K [--bubbles D] [--clean LO:HI:N]]] [--sam primary|all]]\n");
         return 1;
     }
     std::string cand_path, dump_path, cfg_path = "params.cfg", gather_id;
@@ -893,6 +928,16 @@ int main(int argc, char *argv[])
             const long k = strtol(v, &end, 10);
             if (!*v || *end || k < 1 || k > (1L << 30)) { fprintf(stderr, "--bubbles wants an integer from 1 to 2^30, not '%s'\n", v); return 1; }
             bubble_dist = (int)k;
+        }
+        else if (!strcmp(argv[a], "--clean")) {
+            const char *v = a + 1 < argc ? argv[++a] : "";
+            int lo = 0, hi = 0, k = 0, used = 0;
+            if (sscanf(v, "%d:%d:%d%n", &lo, &hi, &k, &used) != 3 || v[used] || lo < 0 || lo > hi || hi > 1000 || k < 0 ||
+                k > GACT_CLEAN_MAX_RATIOS) {
+                fprintf(stderr, "--clean wants LO:HI:N with 0 <= LO <= HI <= 1000 and 0 <= N <= %d, not '%s'\n", GACT_CLEAN_MAX_RATIOS, v);
+                return 1;
+            }
+            clean_lo = lo; clean_hi = hi; clean_n = k;
         }
         else if (!strcmp(argv[a], "--sam")) {
             const char *v = a + 1 < argc ? argv[++a] : "";
@@ -952,6 +997,11 @@ int main(int argc, char *argv[])
         // the bubbles are popped between two rounds of tip cutting, the second one the unitig call's: with K == 0 no tip is cut and
         // the reads a bubble removed would come back as unitigs of one read
         fprintf(stderr, "--bubbles: only with --gfa --unitigs K and K >= 1\n");
+        return 1;
+    }
+    if (clean_lo >= 0 && (!want_gfa || unitig_tips < 1)) {
+        // (for the same reason: the rounds cut tips with K, and with K == 0 the removed reads would come back)
+        fprintf(stderr, "--clean: only with --gfa --unitigs K and K >= 1\n");
         return 1;
     }
     if (unitig_tips >= 0 && !want_gfa) {

@@ -588,8 +588,9 @@ int gact_hip_last_graph_stats(gact_hip_engine *e, int slot, gact_graph_stats *st
  * The arc checks run on the device.  n_reads == 0 returns 0 with *n_unitigs = 0 and *seq_len = 0.
  * Synchronous on the slot's stream; the slot's records and every other statistic stay as they were.  Device memory of its own, one
  * allocation per slot, grown on demand: 32 bytes per arc, about 300 per read (8 more with a clip), and with seq the reads'
- * clipped lengths.  Out of scope: repeated rounds of cleaning, pruning of short overlaps, sharded jobs, and taking the arcs from
- * the graph call's scratch.  Bubble popping is gact_hip_pop_bubbles', below. */
+ * clipped lengths.  Out of scope: sharded jobs, and taking the arcs from the graph call's scratch.  Bubble popping is
+ * gact_hip_pop_bubbles', below; repeated rounds of cleaning and the pruning of short overlaps are gact_hip_clean_graph's and
+ * gact_hip_prune_overlaps', below that. */
 #define GACT_UNITIG_DEFAULT_TIP_READS 3
 #define GACT_UNITIG_PLACED    0
 #define GACT_UNITIG_CONTAINED 1
@@ -665,8 +666,8 @@ int gact_hip_last_unitig_stats(gact_hip_engine *e, int slot, gact_unitig_stats *
  * or arc_flags; bubbles_cap < 0.  n_reads == 0 returns 0 with *n_bubbles = 0.
  * Synchronous on the slot's stream; the slot's records and every other statistic stay as they were.  Device memory of its own,
  * one allocation per slot, grown on demand: 36 bytes per arc and about 150 per read (8 more with a clip, 4 more with skip).
- * Out of scope: repeated rounds (a caller may call again with the removed reads added to skip), pruning of short overlaps,
- * bubbles of more than 64 vertices, sharded jobs. */
+ * Out of scope: bubbles of more than 64 vertices, sharded jobs.  Repeated rounds are gact_hip_clean_graph's and the pruning of
+ * short overlaps is gact_hip_prune_overlaps', both below. */
 #define GACT_GRAPH_ARC_BUBBLE 4            /* bit 2 of gact_graph_arc.flags: removed by gact_hip_pop_bubbles */
 #define GACT_BUBBLE_DEFAULT_MAX_DIST 50000 /* after miniasm: a parameter, not a measurement */
 #define GACT_BUBBLE_MAX_VERTICES 64        /* one wave: one seen vertex per lane */
@@ -687,6 +688,96 @@ int gact_hip_pop_bubbles(gact_hip_engine *e, int slot, int32_t n_reads, const in
 typedef struct { float device_ms; int32_t reads, sources, found, popped, lost, reads_removed;
                  int64_t working_arcs, arcs_removed, by_fail[5], scratch_bytes; } gact_bubble_stats;
 int gact_hip_last_bubble_stats(gact_hip_engine *e, int slot, gact_bubble_stats *stats);
+
+/* ---- weak arcs: the overlaps that are much shorter than the best one of their vertex, marked on the device ----
+ * The third cleaning step of a layout stage (miniasm's asg_arc_del_short), the one that copes with repeats: a repeat shorter than
+ * the reads puts an arc between two unrelated places; that arc is not transitive, no tip and no bubble, and gact_hip_unitigs
+ * breaks the layout there.  Its overlap is short beside the true ones of the same read end, and that is what this call looks
+ * for (csrc/gact_clean.hpp).  All integer, the products in 64 bits, order-free: every output is the same on every call and every
+ * slot.  The graph is not changed: the caller writes arc_flags into the arcs' flags for a following call.
+ * Inputs.  read_lens, clip, reads, arcs, skip: the ones gact_hip_pop_bubbles takes, with the same meaning and the same refusals.
+ *   params  NULL: ratio_permille = GACT_PRUNE_DEFAULT_RATIO_PERMILLE (after miniasm: a parameter, not a measurement)
+ * The rule.
+ *   1 The working set W = the arcs with flags == 0 whose two reads are not named by skip.  out(x) = the W arcs out of x
+ *   2 A vertex with |out(x)| >= 2 is examined; best(x) = the largest ov_u over out(x).  vertex_best[x] = best(x), and 0 for a
+ *     vertex that is not examined
+ *   3 An arc k: x -> w of an examined vertex is weak iff 1000 * ov_u(k) < ratio_permille * best(x), the products in 64 bits.
+ *     Equality is not weak; an arc of a vertex with one W arc is never weak at that vertex
+ *   4 An arc is removed iff it is weak or its complement w^1 -> x^1 (found in W as the arc checks find it) is weak: the removed
+ *     set is closed under complement, and an arc can go although it is the best one of its own vertex
+ *   5 arc_flags[k] = arcs[k].flags | (removed ? GACT_GRAPH_ARC_SHORT : 0)
+ * Refused with GACT_HIP_EINVAL, outputs untouched: what gact_hip_pop_bubbles refuses of read_lens, clip, reads and arcs (the arc
+ * checks run on the device); ratio_permille outside [0, 1000]; a NULL arc_flags.  n_reads == 0 returns 0.
+ * Synchronous on the slot's stream; the slot's records and every other statistic stay as they were.  Device memory of its own,
+ * one allocation per slot, grown on demand: 36 bytes per arc and about 60 per read (8 more with a clip, 4 more with skip).
+ * Out of scope: a cut-off on the absolute overlap length (the graph call's min_ovlp is that), sharded jobs. */
+#define GACT_GRAPH_ARC_TIP    8   /* bit 3: the arc touched a read cut as a tip by gact_hip_clean_graph */
+#define GACT_GRAPH_ARC_SHORT 16   /* bit 4: removed as a weak arc */
+#define GACT_PRUNE_DEFAULT_RATIO_PERMILLE 500   /* after miniasm: a parameter, not a measurement */
+typedef struct { int32_t ratio_permille; } gact_prune_params;
+int gact_hip_prune_overlaps(gact_hip_engine *e, int slot, int32_t n_reads, const int32_t *read_lens, const int32_t *clip,
+                            const gact_graph_read *reads, int64_t n_arcs, const gact_graph_arc *arcs,
+                            const uint8_t *skip /* NULL, or n_reads bytes */, const gact_prune_params *params /* NULL: the default */,
+                            int32_t *arc_flags /* n_arcs */, int32_t *vertex_best /* NULL, or 2 n_reads */);
+/* What the slot's last gact_hip_prune_overlaps call that got as far as the device did: HIP events on the slot's stream around the
+ * whole call (copies and kernels), the reads, the vertices examined, the vertices with an arc in W and none behind the call
+ * (bared), the arcs of W, the weak ones (rule 3), the removed ones (rule 4), and the device memory the call holds for itself. */
+typedef struct { float device_ms; int32_t reads, examined, bared; int64_t working_arcs, weak, arcs_removed, scratch_bytes; } gact_prune_stats;
+int gact_hip_last_prune_stats(gact_hip_engine *e, int slot, gact_prune_stats *stats);
+
+/* ---- cleaning in rounds: tips, bubbles and weak arcs until nothing goes, on the device ----
+ * The loop of a layout stage around the three steps above (miniasm's order): cut the tips and pop the bubbles until a pass
+ * removes nothing, then drop the weak arcs at a rising ratio and settle again after every drop.  The arcs are uploaded once and
+ * stay on the device; every step runs the kernels of its own entry on them and ORs its bits into their flags there; the host
+ * reads one small block of counts per step to decide whether to go on (csrc/gact_clean.hpp).
+ * The rule runs over a flags array F, which starts as arcs[].flags.
+ *   T (tips)     rules 1 - 3 of gact_hip_unitigs on the arcs with F, with tip_reads.  Every read with the state TIP is removed,
+ *                and every arc with F == 0 that touches one gets GACT_GRAPH_ARC_TIP.  A read that an earlier step removed has no
+ *                arc left and is a tip again; it keeps the state and the step of its first removal and is not counted again
+ *   B (bubbles)  the rule of gact_hip_pop_bubbles on the arcs with F, skip NULL, with max_dist and max_vertices.  Its
+ *                GACT_GRAPH_ARC_BUBBLE bits go into F, the reads it removes get the state GACT_CLEAN_BUBBLE
+ *   pass         T then B.  settle: passes until one removes no arc, or until max_passes passes have been made
+ *   P(r)         the rule of gact_hip_prune_overlaps on the arcs with F, skip NULL, ratio_permille = r
+ *   the call     settle; then for j = 0 .. n_ratios - 1: r_j = lo + (hi - lo) * j / (n_ratios - 1) in integer division (lo when
+ *                n_ratios == 1); P(r_j); if it removed an arc, settle again.  n_ratios == 0 prunes nothing
+ * The log.  One gact_clean_step per T, B and P, in the order made: kind, param = tip_reads, max_dist or r_j, the reads and arcs
+ * the step removed, examined = the linear chains of the tip rule (one per head vertex, so a chain and its complement count
+ * twice), the sources searched from, or the vertices examined, and arcs_left = the arcs with F == 0 behind the step.
+ * read_state[i] = (state, step): GACT_CLEAN_KEPT, GACT_UNITIG_CONTAINED, GACT_UNITIG_EMPTY, GACT_UNITIG_TIP or GACT_CLEAN_BUBBLE,
+ * and the index of the log step that removed the read, -1 for KEPT, CONTAINED and EMPTY.  A read that lost all its arcs to a
+ * prune step is KEPT until a T step cuts it.  arc_flags = F behind the last step: written into the arcs it is what a following
+ * gact_hip_unitigs takes.  The arcs left are closed under complement after every step.
+ * steps_cap too small (or steps == NULL): GACT_HIP_EINVAL with *n_steps, arc_flags and read_state filled -- call again with room
+ * for *n_steps, as with bubbles_cap.  (n_ratios + 1) * (2 * max_passes + 1) always suffices.
+ * Refused with GACT_HIP_EINVAL, outputs untouched: what gact_hip_pop_bubbles refuses of read_lens, clip, reads and arcs (the arc
+ * checks run on the device); tip_reads < 1 (with 0 the removed reads would come back as unitigs of one read); max_dist and
+ * max_vertices as the bubble call; a ratio outside [0, 1000] or lo > hi; n_ratios outside [0, 16]; max_passes outside [1, 16];
+ * NULL arc_flags, read_state or n_steps; steps_cap < 0.  n_reads == 0 returns 0 with *n_steps = 0.
+ * Synchronous on the slot's stream; the slot's records and every other statistic stay as they were.  Device memory of its own,
+ * one allocation per slot, grown on demand: 36 bytes per arc and about 230 per read (8 more with a clip).
+ * Out of scope: bubbles of more than 64 vertices, sharded jobs, taking the arcs from the graph call's scratch. */
+#define GACT_CLEAN_TIPS    0
+#define GACT_CLEAN_BUBBLES 1
+#define GACT_CLEAN_PRUNE   2
+#define GACT_CLEAN_KEPT    0      /* read states 1..3 are GACT_UNITIG_CONTAINED / _EMPTY / _TIP */
+#define GACT_CLEAN_BUBBLE  4
+#define GACT_CLEAN_MAX_RATIOS 16
+#define GACT_CLEAN_MAX_PASSES 16
+typedef struct { int32_t tip_reads, max_dist, max_vertices, ratio_lo_permille, ratio_hi_permille, n_ratios, max_passes; } gact_clean_params;
+typedef struct { int32_t kind, param, reads_removed, examined; int64_t arcs_removed, arcs_left; } gact_clean_step;   /* 32 bytes */
+typedef struct { int32_t state, step; } gact_clean_read;                                                              /* 8 bytes */
+int gact_hip_clean_graph(gact_hip_engine *e, int slot, int32_t n_reads, const int32_t *read_lens, const int32_t *clip,
+                         const gact_graph_read *reads, int64_t n_arcs, const gact_graph_arc *arcs,
+                         const gact_clean_params *params /* NULL: 3, 50000, 64, 500, 700, 3, 4 */,
+                         int32_t *arc_flags /* n_arcs */, gact_clean_read *read_state /* n_reads */,
+                         gact_clean_step *steps, int64_t steps_cap, int64_t *n_steps);
+/* What the slot's last gact_hip_clean_graph call that got as far as the device did: HIP events on the slot's stream around the
+ * whole call (copies, kernels and the waits between the steps), the reads, the steps of the log, the passes made, the reads
+ * removed as tips and by bubbles, the arcs removed by kind (GACT_CLEAN_TIPS, _BUBBLES, _PRUNE), the arcs left, and the device
+ * memory the call holds for itself. */
+typedef struct { float device_ms; int32_t reads, steps, passes, reads_tip, reads_bubble;
+                 int64_t arcs_removed[3], arcs_left, scratch_bytes; } gact_clean_stats;
+int gact_hip_last_clean_stats(gact_hip_engine *e, int slot, gact_clean_stats *stats);
 
 /* Per-base pileup and consensus of the reads of GACT_SET_REF from the overlaps' alignments, counted on the device: every chosen
  * candidate's alignment (the one gact_hip_candidates_paths returns as a CIGAR) is stacked on its target read, every position
