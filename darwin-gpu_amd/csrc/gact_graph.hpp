@@ -89,7 +89,9 @@ graph_class_kernel(const gact_overlap *__restrict__ rec, int n, const int *__res
                 long long cbt = 0, cet = len_t, cbq = 0, ceq = len_q;
                 if (clip) { cbt = clip[2 * t]; cet = clip[2 * t + 1]; cbq = clip[2 * q]; ceq = clip[2 * q + 1]; }
                 if (rev) { const long long b = cbq; cbq = len_q - ceq; ceq = len_q - b; }
-                long long ts = max(ab, cbt), te = min(ae, cet), qs = max(bb, cbq), qe = min(be, ceq);
+                // both reads' ends move together, by what the deeper clip cuts: (ts, qs) and (te, qe) stay points of the alignment
+                const long long cut5 = max(max(cbt - ab, cbq - bb), 0LL), cut3 = max(max(ae - cet, be - ceq), 0LL);
+                long long ts = ab + cut5, te = ae - cut3, qs = bb + cut5, qe = be - cut3;
                 if (te <= ts || qe <= qs) cls = GACT_GRAPH_DROPPED;
                 else {
                     ts -= cbt; te -= cbt; qs -= cbq; qe -= cbq;

@@ -468,9 +468,11 @@ int gact_hip_last_place_stats(gact_hip_engine *e, int slot, gact_place_stats *st
  * Class of a counted record (t = ref_id, q = query_id, rev = comp != 0); the first rule that applies wins; 64-bit arithmetic:
  *   1 GACT_GRAPH_SELF     t == q
  *   2 clip.  The query's clip is taken in the frame of its strand: (cbq, ceq) becomes (len_q - ceq, len_q - cbq) when rev.  Then
- *     ts = max(ab', cb_t), te = min(ae, ce_t), qs = max(bb', cbq), qe = min(be, ceq): each end is clamped on its own, the other
- *     read's end is not moved with it.  GACT_GRAPH_DROPPED when te <= ts or qe <= qs (so every record of a read whose clip is
- *     empty).  Then all four are rebased to the clips' begins; tl, ql are the clipped lengths
+ *     cut5 = max(cb_t - ab', cbq - bb', 0), cut3 = max(ae - ce_t, be - ceq, 0) and ts = ab' + cut5, qs = bb' + cut5,
+ *     te = ae - cut3, qe = be - cut3: both reads' ends move together, by what the deeper clip cuts, so that (ts, qs) and (te, qe)
+ *     stay points of the alignment (to within its indels) and len below is the distance between the clipped reads' heads.  (Each
+ *     end clamped on its own leaves len short by the entered read's cb.)  GACT_GRAPH_DROPPED when te <= ts or qe <= qs (so every
+ *     record of a read whose clip is empty).  Then all four are rebased to the clips' begins; tl, ql are the clipped lengths
  *   3 ext5 = min(qs, ts), ext3 = min(ql - qe, tl - te), sq = qe - qs, st = te - ts.  GACT_GRAPH_INTERNAL when ext5 > max_hang or
  *     ext3 > max_hang or 1000 sq < int_permille (sq + ext5 + ext3)
  *   4 q_in = qs <= ts && ql - qe <= tl - te; t_in = qs >= ts && ql - qe >= tl - te.  GACT_GRAPH_QUERY_CONTAINED /

@@ -30,7 +30,8 @@ def classify(rec, k, i, lens, clip, sums, p):
     cbq, ceq = (0, lens[q]) if clip is None else (clip[2 * q], clip[2 * q + 1])
     if rev:
         cbq, ceq = lens[q] - ceq, lens[q] - cbq
-    ts, te, qs, qe = max(ab, cbt), min(ae, cet), max(bb, cbq), min(be, ceq)
+    cut5, cut3 = max(cbt - ab, cbq - bb, 0), max(ae - cet, be - ceq, 0)
+    ts, te, qs, qe = ab + cut5, ae - cut3, bb + cut5, be - cut3
     if te <= ts or qe <= qs:
         return DROPPED, None
     ts, te, qs, qe, tl, ql = ts - cbt, te - cbt, qs - cbq, qe - cbq, cet - cbt, ceq - cbq

@@ -125,7 +125,7 @@ def test_graphs_without_a_branch(eng, name):
 
 
 @pytest.mark.parametrize("skip", [None, "tips"])
-@pytest.mark.parametrize("name,at_least", [("random300_1", 5), ("random300_2", 5), ("random3000_1", 50)])
+@pytest.mark.parametrize("name,at_least", [("random300_3", 5), ("random300_2", 5), ("random3000_1", 50)])
 def test_random_graphs(eng, name, at_least, skip):
     want = _check(eng, name, skip=skip)
     print(name, skip, want["counts"])

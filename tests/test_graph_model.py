@@ -103,8 +103,10 @@ def test_clip_moves_the_frame_and_empties_reads():
     assert classes[(7, 5)] == DROPPED and classes[(5, 7)] == DROPPED
     # read 8, other strand, clip [100, 4100): with the clip mirrored into the record's frame it follows read 5; it contains read 7
     assert classes[(5, 8)] == DOVETAIL and classes[(8, 7)] == QUERY_CONTAINED and classes[(7, 8)] == TARGET_CONTAINED
-    assert (10, 17, 3000) in [(u, v, ln) for u, v, ln, _, _ in _arcs(g)]
-    # the six clipped reads still tile: each end is clamped on its own, so ov gains the clamped bases (3300, 1300), len does not
+    # (len is the distance between the clipped heads: read 5's at genome 10000, vertex 17's -- read 8 without the 900 -- at 13900)
+    assert (10, 17, 3900) in [(u, v, ln) for u, v, ln, _, _ in _arcs(g)]
+    # the six clipped reads still tile, 2000 from head to head as their genome starts are: both reads' ends move with the deeper clip
+    assert sorted(ln for u, v, ln, _, fl in _arcs(g) if fl == 0 and max(u, v) < 12) == [2000] * 10
     assert sum(fl == 0 for _, _, _, _, fl in _arcs(g)) == 12 and g["counts"]["by_class"][DROPPED] == 18
     # without the clip nothing is dropped, and the adapter overhangs (300 on every end) stay under max_hang
     assert DROPPED not in graph(rec, lens)["classes"].tolist()
