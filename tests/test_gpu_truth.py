@@ -1,23 +1,27 @@
 """GPU suite: the device's passes behind a run held to the simulator's ground truth (tests/truth_checks.py), not to their models:
 the records and summaries of a run of both strands, the pair selection, the coverage's clip, the overlap graph, the cleaning, the
-unitigs with bases and the corrected reads of the pileup, on the `tiny` block with true candidates only (block A) and with the
-synthesiser's share of false hits (block B).  What a kernel and its model could both misread -- the frame of a complement
-record's bb / be, the end a minus vertex starts from, which read the inserted and the deleted bases belong to -- fails here.
+unitigs with bases and the corrected reads of the pileup, the alignment paths column by column, the per-base depth of the
+coverage per side and the identities, on the `tiny` block with true candidates only (block A) and with the synthesiser's share
+of false hits (block B); and the placement of the same reads on contigs with a diverged decoy (block P).  What a kernel and its
+model could both misread -- the frame of a complement record's bb / be, the end a minus vertex starts from, which read the
+inserted and the deleted bases belong to, the direction of a path's ops, the mirror of a complement record's query interval,
+which record is the primary -- fails here.
 The model equalities are other files' (tests/test_gpu_unitigs.py and the passes' own); tests/test_truth_model.py runs the
 reference path through the same checks and shows that every such misreading makes its check raise."""
 import numpy as np
 import pytest
 
 import truth_checks as tc
-from test_truth_model import INS_SLOTS, MIN_DEPTH, block, block_b_figures
+from test_truth_model import INS_SLOTS, MIN_DEPTH, block, block_b_figures, block_p
 
 pytestmark = pytest.mark.gpu
 
 
 def device_path(name):
     """candidates_run_mixed -> select_overlaps("pair") -> candidates_summaries -> read_coverage -> overlap_graph(clip) ->
-    clean_graph -> unitigs(seq) at tip_reads 0 and 3, then the pileup with two slots; the records are taken from the slot and
-    fetched last.  One engine per block"""
+    clean_graph -> unitigs(seq) at tip_reads 0 and 3, then the pileup with two slots, the paths of the selected records and the
+    coverage with its per-base depth, one call per side; the records are taken from the slot and fetched last.  One engine per
+    block"""
     from path_cases import engine_with
     rs, cf, cr, law = block(name)
     e, n, nf = engine_with(rs, cf, cr)
@@ -39,12 +43,15 @@ def device_path(name):
         e.pileup_begin(ins_slots=INS_SLOTS)
         e.pileup_add(sel=sel, rc_from=nf)
         table, read_at, seq, _ = e.pileup_corrected(min_depth=MIN_DEPTH, ins=True)
+        _, paths, words = e.candidates_paths(sel=sel, rc_from=nf)
+        by_side = {s: e.read_coverage(lens, sel=sel, sums=sums, sides=s, min_depth=MIN_DEPTH, depth=True) for s in tc.SIDES}
         records = e.candidates_fetch(n).copy()
     finally:
         e.close()
+    ops = [words[int(p["op_offset"]):int(p["op_offset"]) + int(p["n_ops"])] for p in paths]
     return dict(rs=rs, law=law, cands=np.concatenate([cf, cr]), nf=nf, lens=lens, records=records, sel=sel, sums=sums, clip=clip,
                 reads=reads, arcs=arcs, clip2=clip2, reads2=reads2, arcs2=arcs2, cleaned=cleaned, utg=utg, table=table,
-                read_at=read_at, seq=seq)
+                read_at=read_at, seq=seq, ops=ops, by_side=by_side, cover=cover)
 
 
 @pytest.fixture(scope="module")
@@ -123,11 +130,87 @@ def test_check_6_corrected_reads(run_a):
     assert f["reads"] == (p["rs"].n + 3) // 4 and int(p["table"]["inserted"].sum()) > 0
 
 
+def test_check_7_alignment_columns(run_a):
+    """every = and X op of every selected record's path, at its first and its last column, against the genome: the direction of
+    the ops, which of I and D moves which read, the frame of a complement record's query -- inside the record, not at its ends"""
+    p = run_a
+    f = tc.alignment_columns(p["rs"], p["records"], p["sel"], p["sums"], p["ops"])
+    print("check 7, alignment columns:", f)
+    assert f["records"] == int(p["records"]["emitted"][p["sel"]].sum()) and f["run_ends"] > 100 * f["records"]
+
+
+def test_check_8_depth_against_true_depth(run_a):
+    """the per-base depth of read_coverage between the true depth of the overlaps narrowed by REACH and widened by END_SLACK, per
+    side and for both: the mirror that puts a complement record's query interval on the stored read, and which read gets which
+    interval"""
+    p = run_a
+    f = tc.depth_of_sides(p["rs"], p["records"], p["sel"], p["sums"], p["by_side"], MIN_DEPTH)
+    print("check 8, depth against true depth:", f)
+    print("check 8, positions (under, over) at reach 70 and a widening of 5:",
+          tc.depth_misses(p["rs"], p["records"], p["sel"], p["by_side"]["both"][1], reach=70, slack=5))
+    assert f["both"]["intervals"] == 2 * int(p["records"]["emitted"][p["sel"]].sum())
+    assert p["by_side"]["both"][0].tobytes() == p["cover"].tobytes()         # (the table is the same with and without the depth)
+    comp = p["records"]["comp"][p["sel"]] != 0
+    assert (np.asarray(p["rs"].strand)[p["records"]["query_id"][p["sel"]][comp]] == 1).any()
+
+
+def test_check_10_identities_of_true_records(run_a):
+    p = run_a
+    f = tc.identities(p["records"], p["sel"], p["sums"])
+    print("check 10, identities on block A:", f)
+    assert f["true"][0] == int(p["records"]["emitted"][p["sel"]].sum()) and f["false"][0] == 0
+
+
 def test_block_b_false_hits_what_must_hold():
     p = device_path("B")
     utg = {k: p["utg"][k][:3] for k in (0, 3)}
-    f = block_b_figures(p["rs"], p["law"], tc.false_hits(p["rs"], p["cands"], p["nf"]), p["records"], p["sel"], p["sums"], p["clip"],
+    false = tc.false_hits(p["rs"], p["cands"], p["nf"])
+    f = block_b_figures(p["rs"], p["law"], false, p["records"], p["sel"], p["sums"], p["clip"],
                         p["arcs"], p["cleaned"], utg, p["read_at"], p["seq"], range(0, p["rs"].n, 4))
     for k, v in f.items():
         print("block B on the device, %s: %s" % (k, v))
     assert f["of_reads_with_disjoint_spans"] > 0, "block B holds no false pair"
+    f10 = tc.identities(p["records"], p["sel"], p["sums"], false=false[0])
+    print("check 10, identities on block B:", f10)
+    assert f10["false"][0] == f["false_hits_selected"] > 0
+    f7 = tc.alignment_columns(p["rs"], p["records"], p["sel"], p["sums"], p["ops"], false=false[0])
+    print("check 7, the alignment columns of block B's true records:", f7)
+    assert f7["records"] == f10["true"][0]
+
+
+@pytest.fixture(scope="module")
+def run_p():
+    """block P on the device: the contigs as the reference set, the reads and their reverse complements as the queries, the
+    truth candidates run on both strands, summarised and placed ahead of the fetch"""
+    from gact_amd import engine, synth
+    b = block_p()
+    rs, n, nf = b["rs"], len(b["cands"]), b["nf"]
+    e = engine.Engine()
+    try:
+        e.upload_seqs(engine.SET_REF, b["seqs"])
+        e.upload_seqs(engine.SET_QUERY, rs.reads)
+        e.upload_seqs(engine.SET_QUERY_RC, [synth.revcomp(r) for r in rs.reads])
+        e.candidates_upload(b["cands"])
+        e.candidates_run_mixed(n, rc_from=nf, same_file=False)
+        _, sums = e.candidates_summaries(n=n, rc_from=nf, same_file=False)
+        lens = np.array([len(r) for r in rs.reads], dtype=np.int32)
+        place, table = e.place_reads(lens, sums=sums)
+        records = e.candidates_fetch(n).copy()
+    finally:
+        e.close()
+    return dict(b, lens=lens, records=records, sums=sums, place=place, table=table)
+
+
+def test_check_9_placements_on_contigs_with_a_decoy(run_p):
+    """the primary where the read came from, a supplementary for every piece a contig boundary cuts off, the diverged copy a
+    secondary of the true locus with a lower MAPQ; and the device's placement is the model's on the same records"""
+    import place_model
+    p = run_p
+    f = tc.placements(p["rs"], p["contigs"], p["decoy"], p["records"], p["sums"], p["place"], p["table"])
+    print("check 9, block P on the device: %d chains, %d forward;" % (len(p["cands"]), p["nf"]), f)
+    assert f["ends"] == 2 * int(p["records"]["emitted"].sum()) and f["kinds"][tc.PRIMARY] == p["rs"].n
+    want = place_model.place(p["records"], p["lens"], sums=p["sums"])
+    for got, model, what in zip((p["place"], p["table"]), want, ("place", "reads")):
+        for name in got.dtype.names:
+            bad = np.flatnonzero(got[name] != model[name])
+            assert len(bad) == 0, (what, name, bad[:5].tolist(), got[bad[:5]].tolist(), model[bad[:5]].tolist())

@@ -1,7 +1,9 @@
 """CPU suite: the reference path behind a run -- the oracle's chains, then the models of selection, coverage, the overlap graph,
 cleaning, the unitigs and the pileup with corrected reads -- held to the simulator's ground truth by tests/truth_checks.py, on
-the `tiny` block with true candidates only (block A) and with the synthesiser's share of false hits (block B); and the checks'
-teeth: every misreading of a frame, an end or a sign that kernel and model could share makes the named check raise.
+the `tiny` block with true candidates only (block A) and with the synthesiser's share of false hits (block B); the alignment
+paths column by column, the per-base depth per side and the identities on the same blocks; the placement of the reads on
+contigs with a diverged decoy (block P: the oracle's chains, then tests/place_model.py); and the checks' teeth: every
+misreading of a frame, an end, a sign, a direction or a kind that kernel and model could share makes the named check raise.
 tests/test_gpu_truth.py holds the device to the same checks."""
 import numpy as np
 import pytest
@@ -76,8 +78,10 @@ def reference_path(oracle, name):
     p = graph_stages(rs, records, sel, sums)
     _, table, read_at, seq, _ = pileup_ins(rs.reads, _Rc(rs), records[sel], [cigars[i] for i in sel.tolist()], (0, rs.n),
                                            MIN_DEPTH, INS_SLOTS)
+    by_side = {s: cover_model.cover(records, p["lens"], sel=sel, sums=sums, sides=tc.SIDES.index(s) + 1, min_depth=MIN_DEPTH)
+               for s in tc.SIDES}
     p.update(rs=rs, law=law, cands=cands, nf=nf, records=records, sel=sel, sums=sums, n_candidates=len(cands), read_at=read_at,
-             seq=seq, table=table)
+             seq=seq, table=table, ops=[summary_cases.ops_of_cigar(cigars[i]) for i in sel.tolist()], by_side=by_side)
     _PATHS[name] = p
     return p
 
@@ -283,3 +287,231 @@ def test_block_b_false_hits_what_must_hold(oracle):
     for k, v in f.items():
         print("block B, %s: %s" % (k, v))
     assert f["of_reads_with_disjoint_spans"] > 0, "block B holds no false pair"
+
+
+# ---- checks 7, 8 and 10 on blocks A and B
+
+def test_block_a_columns_depth_and_identity(oracle):
+    p = reference_path(oracle, "A")
+    rs, records, sel, sums = p["rs"], p["records"], p["sel"], p["sums"]
+    f = tc.alignment_columns(rs, records, sel, sums, p["ops"])
+    print("check 7, alignment columns:", f)
+    assert f["records"] == int(records["emitted"][sel].sum()) and f["run_ends"] > 100 * f["records"]
+    # REACH, taken here: twice the smallest multiple of 10 at which no position lies under the narrowed true depth
+    depth = p["by_side"]["both"][1]
+    misses = {r: tc.depth_misses(rs, records, sel, depth, reach=r, slack=s) for r, s in
+              [(r, tc.END_SLACK) for r in range(10, 110, 10)] + [(tc.REACH, 5)]}
+    print("check 8, positions (under, over) by reach:", misses)
+    least = min(r for r in range(10, 110, 10) if misses[r][0] == 0)
+    assert tc.REACH == 2 * least, "REACH is %d, the reference path needs %d" % (tc.REACH, least)
+    f = tc.depth_of_sides(rs, records, sel, sums, p["by_side"], MIN_DEPTH)
+    print("check 8, depth against true depth:", f)
+    assert f["both"]["intervals"] == f["ref"]["intervals"] + f["query"]["intervals"] == 2 * int(records["emitted"][sel].sum())
+    f = tc.identities(records, sel, sums)
+    print("check 10, identities on block A:", f)
+    assert f["false"][0] == 0
+
+
+def _exchanged(ops):
+    swap = {tc.OP_I: tc.OP_D, tc.OP_D: tc.OP_I}
+    return [np.array([(int(w) & ~15) | swap.get(int(w) & 15, int(w) & 15) for w in o], dtype=np.uint32) for o in ops]
+
+
+def _ins_and_del_exchanged_in_the_walk(p):
+    ops = _exchanged(p["ops"])
+    return lambda: tc.alignment_columns(p["rs"], p["records"], p["sel"], p["sums"], ops)
+
+
+def _ins_and_del_exchanged_in_ops_and_summary(p):
+    """... consistently: the walk still ends at (ae, be), from begins that are off by ins_bases - del_bases"""
+    ops, sums = _exchanged(p["ops"]), p["sums"].copy()
+    sums["ins_bases"], sums["del_bases"] = p["sums"]["del_bases"], p["sums"]["ins_bases"]
+    return lambda: tc.alignment_columns(p["rs"], p["records"], p["sel"], sums, ops)
+
+
+def _ops_reversed(p):
+    ops = [o[::-1] for o in p["ops"]]
+    return lambda: tc.alignment_columns(p["rs"], p["records"], p["sel"], p["sums"], ops)
+
+
+def _stored_frame_columns(p):
+    rec = _stored_frame_records(p)
+    return lambda: tc.alignment_columns(p["rs"], rec, p["sel"], p["sums"], p["ops"])
+
+
+def _ops_of_the_record_before(p):
+    ops = p["ops"][-1:] + p["ops"][:-1]
+    return lambda: tc.alignment_columns(p["rs"], p["records"], p["sel"], p["sums"], ops)
+
+
+def _with_side(p, **sides):
+    by_side = dict(p["by_side"])
+    by_side.update(sides)
+    return lambda: tc.depth_of_sides(p["rs"], p["records"], p["sel"], p["sums"], by_side, MIN_DEPTH)
+
+
+def _query_unmirrored(p):
+    """a complement record's [bb, be) put on the stored read as it stands: the records mirrored once, so that the model's own
+    mirror undoes it"""
+    rec = _stored_frame_records(p)
+    got = {s: cover_model.cover(rec, p["lens"], sel=p["sel"], sums=p["sums"], sides=tc.SIDES.index(s) + 1, min_depth=MIN_DEPTH)
+           for s in ("query", "both")}
+    over = tc.depth_misses(p["rs"], p["records"], p["sel"], got["both"][1])[1]
+    print("the query interval of complement records unmirrored: %d of %d positions over the widened true depth" % (
+        over, len(got["both"][1])))
+    return _with_side(p, **got)
+
+
+def _target_and_query_exchanged(p):
+    rec = p["records"].copy()
+    rec["ref_id"], rec["query_id"] = p["records"]["query_id"], p["records"]["ref_id"]
+    return _with_side(p, ref=cover_model.cover(rec, p["lens"], sel=p["sel"], sums=p["sums"], sides=cover_model.REF,
+                                               min_depth=MIN_DEPTH))
+
+
+def _depth_shifted_by_one_read(p):
+    cover, depth = p["by_side"]["both"]
+    n = int(p["lens"][-1])
+    return _with_side(p, both=(cover, np.concatenate([depth[-n:], depth[:-n]])))
+
+
+TEETH = {"ins_and_del_exchanged_in_the_walk/check7": (_ins_and_del_exchanged_in_the_walk, "the walk of its ops"),
+         "ins_and_del_exchanged_in_ops_and_summary/check7": (_ins_and_del_exchanged_in_ops_and_summary,
+                                                             "alignment column|leaves its reads"),
+         "ops_reversed/check7": (_ops_reversed, "alignment column"),
+         "complement_query_in_the_stored_frame/check7": (_stored_frame_columns, "alignment column"),
+         "ops_of_the_record_before/check7": (_ops_of_the_record_before, "the walk of its ops"),
+         "complement_query_unmirrored/check8": (_query_unmirrored, "sides query: .* over the true depth"),
+         "target_and_query_exchanged/check8": (_target_and_query_exchanged, "sides ref: .* the true depth"),
+         "depth_shifted_by_one_read/check8": (_depth_shifted_by_one_read, "sides both: .* the true depth")}
+
+
+@pytest.mark.parametrize("name", sorted(TEETH))
+def test_a_misreading_of_columns_or_depth_makes_the_named_check_raise(oracle, name):
+    p = reference_path(oracle, "A")
+    make, message = TEETH[name]
+    with pytest.raises(AssertionError, match=message) as info:
+        make(p)()
+    print("%s: %s" % (name, info.value))
+
+
+def test_block_b_identity_tells_false_records_from_true_ones(oracle):
+    p = reference_path(oracle, "B")
+    hits, _ = tc.false_hits(p["rs"], p["cands"], p["nf"])
+    f = tc.identities(p["records"], p["sel"], p["sums"], false=hits)
+    print("check 10, identities on block B:", f)
+    assert f["false"][0] == sum(1 for i in p["sel"].tolist() if i in hits and p["records"]["emitted"][i]) > 0
+    f7 = tc.alignment_columns(p["rs"], p["records"], p["sel"], p["sums"], p["ops"], false=hits)
+    print("check 7, the alignment columns of block B's true records:", f7)
+    assert f7["records"] == f["true"][0]
+    with pytest.raises(AssertionError, match="identity does not tell"):
+        tc.identities(p["records"], p["sel"], p["sums"], false=set(p["sel"][::2].tolist()))
+
+
+# ---- block P: the reads placed on contigs, with a decoy
+
+CONTIG, DECOY, DECOY_RATE, MIN_SHARE, P_SEED = 10000, (12000, 16000), 0.05, 300, 20261021
+_P = {}
+
+
+def block_p():
+    """the `tiny` reads against the genome cut into four contigs and a fifth, genome[12000:16000] with 5 % of its bases
+    substituted; one candidate, from truth, for every read and every contig that share 300 genome bases, the forward ones
+    first.  -> dict(rs, contigs (begin, end), decoy, seqs, cands, nf)"""
+    if "block" not in _P:
+        from gact_amd import engine, synth
+        rs = block("A")[0]
+        rng = np.random.default_rng(P_SEED)
+        contigs = [(b, b + CONTIG) for b in range(0, len(rs.genome), CONTIG)] + [DECOY]
+        seqs = [rs.genome[b:e].copy() for b, e in contigs]
+        acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+        at = rng.choice(len(seqs[-1]), int(DECOY_RATE * len(seqs[-1])), replace=False)
+        seqs[-1][at] = acgt[(np.searchsorted(acgt, seqs[-1][at]) + rng.integers(1, 4, len(at))) % 4]
+        hits = {0: [], 1: []}
+        for i in range(rs.n):
+            for c, (b, e) in enumerate(contigs):
+                lo, hi = max(b, int(rs.start[i])), min(e, int(rs.start[i] + rs.span[i]))
+                if hi - lo >= MIN_SHARE:
+                    g, comp = int(rng.integers(lo, hi)), int(rs.strand[i])
+                    hits[comp].append((c, i, g - b, synth._read_coord(rs, i, g, comp)))
+        _P["block"] = dict(rs=rs, contigs=contigs, decoy=len(contigs) - 1, seqs=seqs, nf=len(hits[0]),
+                           cands=np.array(hits[0] + hits[1], dtype=engine.CAND_DTYPE))
+    return _P["block"]
+
+
+def reference_path_p(oracle):
+    """the oracle's chain of every candidate of block P, its summary, and the model's placement; computed once"""
+    if "path" not in _P:
+        import place_model
+        from gact_amd import engine
+        from path_model import gact_path
+        b = block_p()
+        rs, cands, nf = b["rs"], b["cands"], b["nf"]
+        records = np.zeros(len(cands), dtype=engine.OVERLAP_DTYPE)
+        records["ref_id"], records["query_id"], records["comp"] = cands["ref_id"], cands["query_id"], np.arange(len(cands)) >= nf
+        sums = np.zeros(len(cands), dtype=engine.SUMMARY_DTYPE)
+        for k, c in enumerate(cands):
+            q = int(c["query_id"])
+            m = gact_path(oracle.align_with_bt, b["seqs"][int(c["ref_id"])], rs.rc(q) if k >= nf else rs.reads[q],
+                          int(c["ref_pos"]), int(c["query_pos"]))
+            for f in path_cases.RECORD_FIELDS:
+                records[f][k] = m[f]
+            sums[k] = engine.summarise(m["ops"])
+        records["emitted"] = records["score"] > 0
+        lens = np.array([len(r) for r in rs.reads], dtype=np.int32)
+        place, table = place_model.place(records, lens, sums=sums)
+        _P["path"] = dict(b, lens=lens, records=records, sums=sums, place=place, table=table)
+    return _P["path"]
+
+
+def test_block_p_placements(oracle):
+    p = reference_path_p(oracle)
+    f = tc.placements(p["rs"], p["contigs"], p["decoy"], p["records"], p["sums"], p["place"], p["table"])
+    print("check 9, block P: %d chains, %d forward;" % (len(p["cands"]), p["nf"]), f)
+    assert f["ends"] == 2 * int(p["records"]["emitted"].sum()) and f["kinds"][tc.PRIMARY] == p["rs"].n
+
+
+def _decoy_and_home_exchanged(p):
+    rec = p["records"].copy()
+    k = int(np.flatnonzero((p["place"]["kind"] == tc.SECONDARY) & (rec["ref_id"] == p["decoy"]))[0])
+    parent = int(p["place"]["parent"][k])
+    rec["ref_id"][k], rec["ref_id"][parent] = p["records"]["ref_id"][parent], p["records"]["ref_id"][k]
+    return dict(records=rec)
+
+
+def _supplementary_and_secondary_exchanged(p):
+    place = p["place"].copy()
+    place["kind"][p["place"]["kind"] == tc.SUPPLEMENTARY] = tc.SECONDARY
+    place["kind"][p["place"]["kind"] == tc.SECONDARY] = tc.SUPPLEMENTARY
+    return dict(place=place)
+
+
+def _comp_inverted_on_one_record(p):
+    rec = p["records"].copy()
+    rec["comp"][len(rec) // 2] ^= 1
+    return dict(records=rec)
+
+
+def _primary_at_the_lowest_score(p):
+    table = p["table"].copy()
+    many = int(np.argmax(table["n_records"]))
+    mine = np.flatnonzero((p["records"]["query_id"] == many) & (p["records"]["emitted"] != 0))
+    table["primary"][many] = mine[np.argmin(p["records"]["score"][mine])]
+    assert table["primary"][many] != p["table"]["primary"][many]
+    return dict(table=table)
+
+
+P_TEETH = {"decoy_and_true_contig_exchanged": (_decoy_and_home_exchanged, "its primary is|on the decoy|apart"),
+           "supplementary_and_secondary_exchanged": (_supplementary_and_secondary_exchanged, "not SUPPLEMENTARY|SECONDARY of"),
+           "comp_inverted_on_one_record": (_comp_inverted_on_one_record, "apart|leaves its sequences|outside read"),
+           "primary_at_the_lowest_score": (_primary_at_the_lowest_score, "its primary is")}
+
+
+@pytest.mark.parametrize("name", sorted(P_TEETH))
+def test_a_misplacement_makes_check_9_raise(oracle, name):
+    p = dict(reference_path_p(oracle))
+    make, message = P_TEETH[name]
+    p.update(make(p))
+    with pytest.raises(AssertionError, match=message) as info:
+        tc.placements(p["rs"], p["contigs"], p["decoy"], p["records"], p["sums"], p["place"], p["table"])
+    print("%s: %s" % (name, info.value))
