@@ -386,9 +386,12 @@ struct Pileup {
     gact_pileup_ins_stats ins_stats{};    // (under mu)
     uint8_t *seq = nullptr;               // the corrected reads' bytes of the last gact_hip_pileup_corrected that had room for them
     size_t seq_cap = 0;
+    // gact_hip_pileup_variants (gact_variants.hpp): position bytes | chunk_at | totals | the sequences' table | records
+    PassScratch<gact_variant_stats> variants;
     void release()
     {
         scratch.release();
+        variants.release();
         if (seq) (void)hipFree(seq);
         seq = nullptr; seq_cap = 0;
         open = false;
@@ -1959,6 +1962,7 @@ int gact_hip_measure_valu_rate(gact_hip_engine *e, double *lane_ops_per_s)
 #include "gact_cover.hpp"        // gact_hip_read_coverage: per-read coverage of an overlap set, behind those
 #include "gact_graph.hpp"        // gact_hip_overlap_graph: containment, dovetail arcs and their transitive flags, behind those
 #include "gact_pileup.hpp"       // gact_hip_pileup_*: per-base pileup and consensus from the alignments' columns
+#include "gact_variants.hpp"     // gact_hip_pileup_variants: INS, DEL and SNV records from the pileup's counts, one wave per chunk of positions
 #include "gact_unitig.hpp"       // gact_hip_unitigs: tip cut, chain ranking, layout and bases of the graph's unitigs, behind every other kernel
 #include "gact_bubble.hpp"       // gact_hip_pop_bubbles: the bubbles of the graph, one wave per search, on the unitigs' first kernels
 #include "gact_clean.hpp"        // gact_hip_prune_overlaps, gact_hip_clean_graph: the weak arcs, and the rounds of tips, bubbles and weak arcs on resident arcs

@@ -88,6 +88,15 @@ PILEUP_INS_DTYPE = np.dtype([("n", "<u4", (4,))])
 READ_CORRECTED_DTYPE = np.dtype([(n, "<i4") for n in ("length", "inserted", "ins_sites", "deleted", "changed")] +
                                 [("reserved", "<i4", (3,))])
 assert PILEUP_INS_DTYPE.itemsize == 16 and READ_CORRECTED_DTYPE.itemsize == 32
+# the variants of the pileup (include/gact_hip.h gact_hip_pileup_variants): one record per variant, one per sequence of the window
+VARIANT_INS, VARIANT_DEL, VARIANT_SNV = range(3)
+VARIANT_TRUNCATED = 4                                 # bit 2 of flags; the gt (1: 0/1, 2: 1/1) is flags & 3
+VARIANT_CHUNK = 4096                                  # GACT_VARIANT_CHUNK: the positions one wave takes
+VARIANT_DEFAULTS = dict(min_depth=8, min_alt=4, min_permille=250, hom_permille=750)       # GACT_VARIANT_DEFAULT_*
+VARIANT_DTYPE = np.dtype([("seq", "<i4"), ("pos", "<i4"), ("kind", "<i4"), ("len", "<i4"), ("bases", "<u4"), ("alt", "<u4"),
+                          ("depth", "<u4"), ("flags", "<i4")])
+SEQ_VARIANTS_DTYPE = np.dtype([(n, "<i4") for n in ("examined", "n_ins", "n_del", "n_snv", "first")] + [("reserved", "<i4", (3,))])
+assert VARIANT_DTYPE.itemsize == 32 and SEQ_VARIANTS_DTYPE.itemsize == 32
 
 # alignment ops (include/gact_hip.h GACT_PATH_OP_*): BAM's CIGAR numbering; an op word is len << 4 | op
 OP_I, OP_D, OP_EQ, OP_X = 1, 2, 7, 8
@@ -260,6 +269,16 @@ class PileupStats(C.Structure):
 class PileupInsStats(C.Structure):
     _fields_ = [("device_ms", C.c_float), ("ins_slots", C.c_int32), ("slot_adds", C.c_int64), ("runs_truncated", C.c_int64),
                 ("emitted", C.c_int64), ("table_bytes", C.c_int64)]
+
+
+class VariantParams(C.Structure):
+    """the defaults are GACT_VARIANT_DEFAULT_*"""
+    _fields_ = [(n, C.c_int32) for n in ("min_depth", "min_alt", "min_permille", "hom_permille")]
+
+
+class VariantStats(C.Structure):
+    _fields_ = [("device_ms", C.c_float), ("chunks", C.c_int32), ("n_ins", C.c_int64), ("n_del", C.c_int64), ("n_snv", C.c_int64),
+                ("examined", C.c_int64), ("scratch_bytes", C.c_int64)]
 
 
 COVER_REF, COVER_QUERY, COVER_BOTH = 1, 2, 3
@@ -493,6 +512,14 @@ def load():
             getattr(L, "gact_hip_" + name).restype = C.c_int
     except AttributeError:
         pass
+    try:
+        L.gact_hip_pileup_variants.argtypes = [vp, C.POINTER(VariantParams), vp, C.c_int64, C.POINTER(C.c_int64), vp]
+        L.gact_hip_last_variant_stats.argtypes = [vp, C.POINTER(VariantStats)]
+        L.gact_hip_format_vcf.argtypes = [vp, C.c_char_p, vp, C.c_int64, C.c_char_p, C.c_size_t]
+        for name in ("pileup_variants", "last_variant_stats", "format_vcf"):
+            getattr(L, "gact_hip_" + name).restype = C.c_int
+    except AttributeError:
+        pass
     try:                                    # (an older build loaded through GACT_HIP_LIB_PATH for an A/B run has none)
         L.gact_hip_comm_create.argtypes = [vp, i32, i32, C.c_char_p, i32, C.POINTER(vp)]
         L.gact_hip_comm_gather_lines.argtypes = [vp, C.c_int, i32, vp, vp, C.c_int64]
@@ -530,7 +557,8 @@ EXPORTS = ("gact_hip_create", "gact_hip_destroy", "gact_hip_last_error", "gact_h
            "gact_hip_prune_overlaps", "gact_hip_last_prune_stats", "gact_hip_clean_graph", "gact_hip_last_clean_stats",
            "gact_hip_pileup_begin", "gact_hip_pileup_add", "gact_hip_pileup_finish", "gact_hip_last_pileup_stats",
            "gact_hip_pileup_begin_ins", "gact_hip_pileup_corrected", "gact_hip_last_pileup_ins_stats",
-           "gact_hip_place_reads", "gact_hip_last_place_stats", "gact_hip_format_sam", "gact_hip_format_sam_unmapped")
+           "gact_hip_place_reads", "gact_hip_last_place_stats", "gact_hip_format_sam", "gact_hip_format_sam_unmapped",
+           "gact_hip_pileup_variants", "gact_hip_last_variant_stats", "gact_hip_format_vcf")
 
 
 def plan(count, flags=0, compute_units=256, tile_size=320, tile_overlap=120, scoring=(1, -1, -1, -1), threshold=35):
@@ -1099,6 +1127,34 @@ class Engine:
         longer than ins_slots, bases the last pileup_corrected put in, the table's bytes"""
         return self._stats(self.L.gact_hip_last_pileup_ins_stats, PileupInsStats)
 
+    def pileup_variants(self, min_depth=VARIANT_DEFAULTS["min_depth"], min_alt=VARIANT_DEFAULTS["min_alt"],
+                        min_permille=VARIANT_DEFAULTS["min_permille"], hom_permille=VARIANT_DEFAULTS["hom_permille"], table=False):
+        """the variants of the open window, called from its counts on the device: VARIANT_DTYPE records ordered by seq, pos,
+        kind (VARIANT_INS, _DEL, _SNV) and the SNV's base -- or, with `table`, (records, SEQ_VARIANTS_DTYPE [n_reads]).  A record
+        exists where a >= min_alt reads and at least min_permille of the depth say so at a position of depth >= min_depth; its
+        gt (flags & 3) is 2 from hom_permille of the depth on, else 1: thresholds of a stated rule, not likelihoods.  The counts
+        stay (include/gact_hip.h gact_hip_pileup_variants)"""
+        if self._pileup is None:                      # (the table's size is the window's)
+            raise GactHipError("gact_hip error -1: pileup_variants: no window is open (gact_hip_pileup_begin first)")
+        params = VariantParams(int(min_depth), int(min_alt), int(min_permille), int(hom_permille))
+        seqs = np.zeros(self._pileup[0], dtype=SEQ_VARIANTS_DTYPE)
+        n = C.c_int64(-1)
+        cap = 1024                                  # (a guess; a window with more records says how many)
+        for attempt in range(2):
+            out = np.zeros(cap, dtype=VARIANT_DTYPE)
+            rc = self.L.gact_hip_pileup_variants(self.h, C.byref(params), out.ctypes.data, cap, C.byref(n), _ptr(seqs))
+            if rc == 0 or attempt or n.value <= cap:
+                break
+            cap = n.value                           # (EINVAL with *n_variants filled: once more with room for the records)
+        self._check(rc)
+        out = out[:n.value].copy()
+        return (out, seqs) if table else out
+
+    def last_variant_stats(self):
+        """the last pileup_variants call: device ms (HIP events around the whole call), chunks, records per kind, examined
+        positions, device bytes the pass holds"""
+        return self._stats(self.L.gact_hip_last_variant_stats, VariantStats)
+
     def register_output(self, out, slot=0):
         """page-locks a caller-owned record array that will be fetched into repeatedly (opt-in; it must outlive the
         registration)"""
@@ -1227,6 +1283,14 @@ def format_sam(rec, ops, place, query_name, query_seq, ref_name):
     return _sam_line(lambda L, buf, cap: L.gact_hip_format_sam(rec.ctypes.data, ops.ctypes.data, len(ops), place.ctypes.data,
                                                                query_name.encode(), seq.ctypes.data, len(seq), ref_name.encode(),
                                                                buf, cap))
+
+
+def format_vcf(variant, seq_name, seq):
+    """one VCF line for a VARIANT_DTYPE record and the sequence it lies on (bytes or uint8); "" for a deletion of the whole
+    sequence (include/gact_hip.h gact_hip_format_vcf; no engine, no device)"""
+    v = np.ascontiguousarray(variant, dtype=VARIANT_DTYPE)
+    seq = _seq_bytes(seq)
+    return _sam_line(lambda L, buf, cap: L.gact_hip_format_vcf(v.ctypes.data, seq_name.encode(), seq.ctypes.data, len(seq), buf, cap))
 
 
 def format_sam_unmapped(query_name, query_seq):

@@ -72,12 +72,18 @@ class ReadSet:
 
 def simulate_reads(genome_len, n_reads=None, coverage=None, seed=1, mean_len=10000, sd_len=2000,
                    min_len=1000, max_len=25000, error=0.15, split=(10, 60, 30),
-                   uniform_len=None, n_frac=0.0):
+                   uniform_len=None, n_frac=0.0, genome=None):
     """Returns a ReadSet.  Give n_reads or coverage.  uniform_len=(lo,hi) switches
-    the length law to uniform (ONT-shape config 5).  n_frac sprinkles 'N's."""
+    the length law to uniform (ONT-shape config 5).  n_frac sprinkles 'N's.
+    genome: a uint8 array that IS the genome (genome_len is then its length, whatever was
+    passed); None draws a random one, as ever."""
     rng = np.random.default_rng(seed)
     rs = ReadSet()
-    genome = _ACGT[rng.integers(0, 4, size=genome_len)]
+    if genome is None:
+        genome = _ACGT[rng.integers(0, 4, size=genome_len)]
+    else:
+        genome = np.ascontiguousarray(genome, dtype=np.uint8)
+        genome_len = len(genome)
     rs.genome = genome
     if n_reads is None:
         mean = mean_len if uniform_len is None else 0.5 * (uniform_len[0] + uniform_len[1])

@@ -3,7 +3,7 @@
 //   darwin_hip <REF.fasta> <READS.fasta> CPU_THREADS [--params params.cfg]
 //              [--candidates FILE | --dump-candidates FILE [--dsoft-only]] [--device-dsoft]
 //              [--device D] [--shard R/W] [--recode] [--cigar] [--paf] [--unique exact|pair] [--coverage K]
-//              [--pileup K [--ins-slots S]] [--gfa [--unitigs K [--bubbles D] [--clean LO:HI:N]]] [--sam primary|all]
+//              [--pileup K [--ins-slots S] [--vcf A:P:H]] [--gfa [--unitigs K [--bubbles D] [--clean LO:HI:N]]] [--sam primary|all]
 //
 // Plays the part of reference darwin.cpp:451-646 for the GACT stage: owns the
 // globals gact.cpp reads, loads params.cfg and the two FASTA files, builds the
@@ -70,6 +70,13 @@
 // `@HD VN:1.6 SO:unsorted`, one `@SQ SN:<name> LN:<n>` per reference sequence in id order, `@PG ID:darwin_hip`, then per read in
 // id order its primary and supplementary lines (all: its secondary and extra lines too) in rank order, or one unmapped line
 // (gact_hip_format_sam, gact_hip_format_sam_unmapped).  Every other output byte is as without the flag.
+// --vcf A:P:H (with --pileup K; integers min_alt:min_permille:hom_permille, A >= 1, 0 <= P <= H <= 1000; min_depth is K): after
+// the join, behind darwin.cons.fa, one gact_hip_pileup_variants call over the same counts and darwin.vcf: `##fileformat=VCFv4.2`,
+// one `##contig=<ID=name,length=n>` per reference sequence, the INFO lines of DP and AD and the FORMAT line of GT, the
+// `#CHROM ... FORMAT darwin` line, then the records in device order (gact_hip_format_vcf).  A stated rule of thresholds: no QUAL,
+// no likelihoods.  With --sam as well a feeder's gact_hip_pileup_add takes only the records its placement made primary or
+// supplementary -- the one gact_hip_place_reads call serves both -- so that a read that maps onto several copies of a repeat
+// votes once, and darwin.cons.fa is made from those counts too.  Without --vcf every output byte is as without the flag.
 //
 // --device D: the GPU this process uses (the reference is single-device, cuda_host.cu:195).  --shard R/W: this
 // process is rank R of W -- it extends every W-th candidate (host filter) or the R-th contiguous range of reads
@@ -115,6 +122,8 @@ static int pileup_depth = 0;                     // --pileup K: min_depth of dar
 static int pileup_ins_slots = 0;                 // --ins-slots S: the inserted bases kept per position, 0: none
 static bool want_gfa = false;                    // --gfa: darwin.gfa, the overlap graph of the records written
 static int unitig_tips = -1;                     // --unitigs K: tip_reads of darwin.utg.gfa, -1: no unitigs
+static bool want_vcf = false;                    // --vcf A:P:H: darwin.vcf from the pileup's counts (min_depth is --pileup's K)
+static int vcf_min_alt = 0, vcf_min_permille = 0, vcf_hom_permille = 0;
 static int sam_mode = 0;                         // --sam: 1 primary (and supplementary) lines, 2 all lines, 0: no SAM files
 static int clean_lo = -1, clean_hi = 0, clean_n = 0;   // --clean LO:HI:N: the ratios of the cleaning rounds in front of the unitigs, lo < 0: none
 static int bubble_dist = 0;                      // --bubbles D: max_dist of the bubble popping in front of the unitigs, 0: none
@@ -261,17 +270,23 @@ static void feeder(int cpu_id, const std::vector<Cand> *all, size_t lo, size_t h
     print_stage("Time GACT calling", t0, now());                 // darwin.cpp:441
 }
 
-// --sam: reads [lo, hi) of a feeder placed on its slot, behind its run, and darwin.<thread>.sam.  o: the run's records as
-// fetched, keep: the ones --unique left; the records chosen for the placement are the ones the feeder writes a line for
-static void write_sam(gact_hip_engine *e, int slot, int cpu_id, int lo, int hi, const std::vector<gact_overlap> &o,
-                      const std::vector<char> &keep, int32_t nf)
+// --sam: the placement of a feeder's reads [lo, hi) on its slot, behind its run: the one gact_hip_place_reads call, which
+// darwin.<thread>.sam is written from and which --vcf takes the records to stack from.  o: the run's records as fetched,
+// keep: the ones --unique left; the records chosen for the placement are the ones the feeder writes a line for
+struct Placed {
+    std::vector<int32_t> chosen;                  // indices into the run's records
+    std::vector<gact_placement> place;            // one per chosen record
+};
+
+static void place_feeder_reads(gact_hip_engine *e, int slot, int lo, int hi, const std::vector<gact_overlap> &o,
+                               const std::vector<char> &keep, int32_t nf, Placed &pd)
 {
     auto check = [](int rc, const char *what) {
         if (rc != 0) { printf("\n%s failed: %s\n\n", what, gact_hip_last_error()); exit(-1); }
     };
     const int32_t n = (int32_t)o.size();
     // 1 the summaries of the chosen records: the placement's intervals begin where the alignments do
-    std::vector<int32_t> chosen;
+    std::vector<int32_t> &chosen = pd.chosen;
     for (int32_t k = 0; k < n; k++)
         if (o[(size_t)k].emitted && keep[(size_t)k]) chosen.push_back(k);
     const int32_t n_chosen = (int32_t)chosen.size();
@@ -283,11 +298,23 @@ static void write_sam(gact_hip_engine *e, int slot, int cpu_id, int lo, int hi, 
     // 2 the placement, over the slot's own records and the window of this feeder's reads
     std::vector<int32_t> lens((size_t)(hi - lo));
     for (int r = lo; r < hi; r++) lens[(size_t)(r - lo)] = (int32_t)reads_seqs[(size_t)r].size();
-    std::vector<gact_placement> place((size_t)n_chosen);
+    pd.place.assign((size_t)n_chosen, gact_placement{});
     std::vector<gact_read_place> reads((size_t)(hi - lo));
     if (n_chosen)
         check(gact_hip_place_reads(e, slot, n, nullptr, n_chosen, chosen.data(), sums.data(), lo, hi - lo, lens.data(), nullptr,
-                                   place.data(), reads.data()), "gact_hip_place_reads");
+                                   pd.place.data(), reads.data()), "gact_hip_place_reads");
+}
+
+// --sam: darwin.<thread>.sam from the placement of the feeder's reads
+static void write_sam(gact_hip_engine *e, int slot, int cpu_id, int lo, int hi, const std::vector<gact_overlap> &o, int32_t nf,
+                      const Placed &pd)
+{
+    auto check = [](int rc, const char *what) {
+        if (rc != 0) { printf("\n%s failed: %s\n\n", what, gact_hip_last_error()); exit(-1); }
+    };
+    const std::vector<int32_t> &chosen = pd.chosen;
+    const std::vector<gact_placement> &place = pd.place;
+    const int32_t n_chosen = (int32_t)chosen.size();
     // 3 the alignments of the records to print, per read in id order, in rank order
     std::vector<int32_t> order;                   // positions in `chosen`
     for (int32_t k = 0; k < n_chosen; k++) {
@@ -425,9 +452,21 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
               "gact_hip_candidates_summaries");
         fpaf.open(paf_name(cpu_id));
     }
-    // --pileup: the same records' alignments onto their target sequences, counted on the device (gact_hip_pileup_add)
-    if (pileup_depth)
-        check(gact_hip_pileup_add(e, s.slot, (int32_t)sel.size(), sel.data(), nf, same_file), "gact_hip_pileup_add");
+    // --sam: where every read of this feeder goes (gact_hip_place_reads), for its SAM file and for --vcf
+    Placed placed;
+    if (sam_mode) place_feeder_reads(e, s.slot, lo, hi, o, keep, nf, placed);
+    // --pileup: the same records' alignments onto their target sequences, counted on the device (gact_hip_pileup_add).  With
+    // --vcf and --sam only the records the placement made primary or supplementary: a read that maps onto several copies of a
+    // repeat votes once
+    if (pileup_depth) {
+        std::vector<int32_t> parents;
+        if (want_vcf && sam_mode)
+            for (size_t k = 0; k < placed.chosen.size(); k++)
+                if (placed.place[k].kind == GACT_PLACE_PRIMARY || placed.place[k].kind == GACT_PLACE_SUPPLEMENTARY)
+                    parents.push_back(placed.chosen[k]);
+        const std::vector<int32_t> &stacked = want_vcf && sam_mode ? parents : sel;
+        check(gact_hip_pileup_add(e, s.slot, (int32_t)stacked.size(), stacked.data(), nf, same_file), "gact_hip_pileup_add");
+    }
     char line[1024];
     size_t next = 0;                              // (the emitted records in order: paths[next], sums[next] are this one's)
     for (int32_t at = 0; at < n; at++) {
@@ -472,7 +511,7 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
         }
         next++;
     }
-    if (sam_mode) write_sam(e, s.slot, cpu_id, lo, hi, o, keep, nf);
+    if (sam_mode) write_sam(e, s.slot, cpu_id, lo, hi, o, nf, placed);
     print_stage("Time GACT calling", t1, now());                 // darwin.cpp:441
 }
 
@@ -705,6 +744,45 @@ static int write_consensus(gact_hip_engine *e)
     return 0;
 }
 
+// --vcf: the variants of every reference sequence from the same counts, one gact_hip_pileup_variants call, then darwin.vcf
+static int write_variants(gact_hip_engine *e)
+{
+    const gact_variant_params params = {pileup_depth, vcf_min_alt, vcf_min_permille, vcf_hom_permille};
+    std::vector<gact_variant> v(1024);
+    int64_t n = 0;
+    int rc = gact_hip_pileup_variants(e, &params, v.data(), (int64_t)v.size(), &n, nullptr);
+    if (rc == GACT_HIP_EINVAL && n > (int64_t)v.size()) {
+        v.resize((size_t)n);
+        rc = gact_hip_pileup_variants(e, &params, v.data(), (int64_t)v.size(), &n, nullptr);
+    }
+    if (rc != 0) { printf("\ngact_hip_pileup_variants failed: %s\n\n", gact_hip_last_error()); return 1; }
+    FILE *f = fopen("darwin.vcf", "w");
+    if (!f) { fprintf(stderr, "--vcf: cannot write darwin.vcf\n"); return 1; }
+    fprintf(f, "##fileformat=VCFv4.2\n");
+    for (size_t i = 0; i < reference_seqs.size(); i++)
+        fprintf(f, "##contig=<ID=%s,length=%zu>\n", reference_descrips[i][0].c_str(), reference_seqs[i].size());
+    fprintf(f, "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Alignments that span the position\">\n"
+               "##INFO=<ID=AD,Number=1,Type=Integer,Description=\"Alignments that support the alternate allele\">\n"
+               "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype by the thresholds min_alt=%d min_permille=%d hom_permille=%d at depth >= %d\">\n"
+               "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tdarwin\n",
+            vcf_min_alt, vcf_min_permille, vcf_hom_permille, pileup_depth);
+    std::vector<char> line(4096);
+    for (int64_t k = 0; k < n; k++) {
+        const gact_variant &r = v[(size_t)k];
+        if (r.seq < 0 || (size_t)r.seq >= reference_seqs.size()) { fprintf(stderr, "--vcf: record %lld names sequence %d\n", (long long)k, r.seq); fclose(f); return 1; }
+        const std::string &seq = reference_seqs[(size_t)r.seq];
+        for (int attempt = 0; attempt < 2; attempt++) {
+            const int len = gact_hip_format_vcf(&r, reference_descrips[(size_t)r.seq][0].c_str(), (const uint8_t *)seq.data(),
+                                                (int64_t)seq.size(), line.data(), line.size());
+            if (len < 0) { printf("\ngact_hip_format_vcf failed: %s\n\n", gact_hip_last_error()); fclose(f); return 1; }
+            if ((size_t)len < line.size()) { fwrite(line.data(), 1, (size_t)len, f); break; }
+            line.resize((size_t)len + 1);
+        }
+    }
+    fclose(f);
+    return 0;
+}
+
 // --rccl-gather IDFILE (with --shard R/W): this rank's share as ONE run on the engine (no feeder threads: a run is fastest
 // with all of its candidates in one launch), then the job's one collective -- every rank's records to rank 0 over RCCL,
 // out of the engines' device arrays (gact_hip_comm_gather_lines) -- and rank 0 writes darwin.gathered.out: the lines of
@@ -870,7 +948,7 @@ int main(int argc, char *argv[])
     if (argc >= 3 && strcmp(argv[1], "--selftest") == 0) return selftest(argv[2]);
     if (argc < 4) {
         fprintf(stderr, "Usage: darwin_hip <REFERENCE>.fasta <READS>.fasta CPU_THREADS --candidates FILE "
-                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K [--ins-slots S]] [--gfa [--unitigs K [--bubbles D] [--clean LO:HI:N]]] [--sam primary|all]]\n");
+                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K [--ins-slots S] [--vcf A:P:H]] [--gfa [--unitigs K [--bubbles D] [--clean LO:HI:N]]] [--sam primary|all]]\n");
         return 1;
     }
     std::string cand_path, dump_path, cfg_path = "params.cfg", gather_id;
@@ -913,6 +991,16 @@ int main(int argc, char *argv[])
                 return 1;
             }
             pileup_ins_slots = (int)k;
+        }
+        else if (!strcmp(argv[a], "--vcf")) {
+            const char *v = a + 1 < argc ? argv[++a] : "";
+            int alt = 0, lo = 0, hi = 0, used = 0;
+            if (sscanf(v, "%d:%d:%d%n", &alt, &lo, &hi, &used) != 3 || v[used] || alt < 1 || lo < 0 || lo > hi || hi > 1000) {
+                fprintf(stderr, "--vcf wants A:P:H (min_alt:min_permille:hom_permille) with A >= 1 and 0 <= P <= H <= 1000, not '%s'\n", v);
+                return 1;
+            }
+            want_vcf = true;
+            vcf_min_alt = alt; vcf_min_permille = lo; vcf_hom_permille = hi;
         }
         else if (!strcmp(argv[a], "--gfa")) want_gfa = true;
         else if (!strcmp(argv[a], "--unitigs")) {
@@ -985,6 +1073,11 @@ int main(int argc, char *argv[])
     }
     if (pileup_ins_slots && !pileup_depth) {
         fprintf(stderr, "--ins-slots: only with --pileup\n");
+        return 1;
+    }
+    if (want_vcf && !pileup_depth) {
+        // the records are called from the counts of --pileup, whose K is their min_depth
+        fprintf(stderr, "--vcf: only with --pileup\n");
         return 1;
     }
     if (want_gfa && (!device_dsoft || shard_given || strcmp(argv[1], argv[2]) != 0)) {
@@ -1093,8 +1186,9 @@ int main(int argc, char *argv[])
         const int cover_rc = coverage_depth && !dumping ? write_coverage(e, want_gfa ? &spans : nullptr) : 0;
         const int gfa_rc = want_gfa && !dumping && !cover_rc ? write_gfa(e, spans) : 0;
         const int cons_rc = pileup_depth && !dumping ? write_consensus(e) : 0;
+        const int vcf_rc = want_vcf && !dumping && !cons_rc ? write_variants(e) : 0;
         GPU_close(&s, num_threads);
-        return cover_rc ? cover_rc : gfa_rc ? gfa_rc : cons_rc;
+        return cover_rc ? cover_rc : gfa_rc ? gfa_rc : cons_rc ? cons_rc : vcf_rc;
     }
 
     // per-thread candidate lists, contiguous read ranges like darwin.cpp:619-629

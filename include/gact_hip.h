@@ -900,6 +900,70 @@ int gact_hip_pileup_corrected(gact_hip_engine *e, int32_t min_depth, gact_pileup
 typedef struct { float device_ms; int32_t ins_slots; int64_t slot_adds, runs_truncated, emitted, table_bytes; } gact_pileup_ins_stats;
 int gact_hip_last_pileup_ins_stats(gact_hip_engine *e, gact_pileup_ins_stats *stats);
 
+/* Variants of the open window, called from its counts on the device (csrc/gact_variants.hpp).  What a user who maps reads
+ * against a reference asks of the pileup: where does the sample differ from this sequence, and in all of its reads or in part
+ * of them.  The consensus cannot say: a site where 40 % of the reads differ leaves it unchanged.  The rule, all integers, the
+ * same on every call, whichever slots added in whichever order:
+ *
+ *   params     min_depth, min_alt, min_permille, hom_permille; NULL: GACT_VARIANT_DEFAULT_* (8, 4, 250, 750).  PARAMETERS OF A
+ *              STATED RULE, NOT A CALIBRATED ERROR MODEL: thresholds on counts, no likelihoods, no QUAL, no strand counts.
+ *   qualifies  (a, d) iff a >= min_alt and 1000 * a >= min_permille * d (64-bit)
+ *   gt         (a, d) = 2 (all reads: 1/1) if 1000 * a >= hom_permille * d, else 1 (part of them: 0/1)
+ *   examined   position x of sequence i of the window, with the counts n[] (gact_pileup_col), d = n[GACT_PILEUP_DEPTH] and `own`
+ *              the sequence's raw byte at x, is examined iff d >= min_depth.  A position that is not examined makes no record
+ *              and breaks a deletion run.
+ *   INS        only on a window opened with ins_slots = K >= 1.  s_j = slot j's four counts at x together.  The record exists
+ *              iff qualifies(s_0, d); len = the number of leading slots j with qualifies(s_j, d); bases = each such slot's
+ *              largest count's letter, the first of equal ones in the order A C G T, slot j's in bits [8 j, 8 j + 8) (as the
+ *              slot call of gact_hip_pileup_corrected packs them); alt = s_0; GACT_VARIANT_TRUNCATED is set when len == K (the
+ *              window kept no more of the run).  The inserted bases lie IN FRONT OF x.
+ *   DEL        x is a deleted position iff it is examined and qualifies(n[GACT_PILEUP_DEL], d).  A maximal run of consecutive
+ *              deleted positions inside one sequence is one record: pos the run's first position, len its length, alt, depth
+ *              and gt those of the first position.  Runs never cross a sequence boundary.
+ *   SNV        only where own is one of acgtACGT: one record per base b other than own (case folded) with qualifies(n[b], d),
+ *              in the order A C G T; len = 1, alt = n[b], bases = b's upper-case letter.  An SNV inside a called deletion is
+ *              reported on its own.
+ *   order      by seq, then pos, then kind (INS, DEL, SNV), then the SNV's base: VCF lines made in this order have
+ *              non-decreasing POS.
+ *
+ *   variants   NULL, or room for cap records; n_variants: NULL, or where the number of records goes; seqs: NULL, or one
+ *              gact_seq_variants per sequence of the window: its examined positions, its records per kind, and `first`, the
+ *              index of its first record (of the next sequence's where it has none).
+ * cap < *n_variants with variants not NULL: GACT_HIP_EINVAL with *n_variants and seqs filled in, call again with room (the
+ * protocol of gact_hip_pileup_corrected).  GACT_HIP_EINVAL, with every output untouched: no open window, GACT_SET_REF uploaded
+ * again since, cap < 0, min_depth < 1, min_alt < 1, anything but 0 <= min_permille <= hom_permille <= 1000.  A window without
+ * slots makes no INS records; an empty window makes none at all.  Synchronous on slot 0's stream, as gact_hip_pileup_finish is,
+ * and as little to be called while an add is running; the counts stay: it may be called again with other parameters, and more
+ * adds may follow.  One wave takes GACT_VARIANT_CHUNK consecutive positions of the window, whichever sequences they belong to,
+ * so a window of a few long sequences fills the device as one of many short ones does.  Device memory of its own, one
+ * allocation of the engine's, grown on demand: 1 byte per position, 8 per chunk, 32 per sequence and 32 per record. */
+#define GACT_VARIANT_INS 0
+#define GACT_VARIANT_DEL 1
+#define GACT_VARIANT_SNV 2
+#define GACT_VARIANT_TRUNCATED 4        /* bit 2 of flags */
+#define GACT_VARIANT_CHUNK 4096         /* positions a wave takes: a multiple of 64 */
+#define GACT_VARIANT_DEFAULT_MIN_DEPTH    8
+#define GACT_VARIANT_DEFAULT_MIN_ALT      4
+#define GACT_VARIANT_DEFAULT_MIN_PERMILLE 250
+#define GACT_VARIANT_DEFAULT_HOM_PERMILLE 750
+typedef struct { int32_t min_depth, min_alt, min_permille, hom_permille; } gact_variant_params;
+typedef struct {
+    int32_t seq;            /* the sequence's id in GACT_SET_REF */
+    int32_t pos;            /* 0-based, on that sequence */
+    int32_t kind;           /* GACT_VARIANT_* */
+    int32_t len;
+    uint32_t bases;         /* SNV: the alt's letter in the low byte; INS: slot j's letter in bits [8 j, 8 j + 8); DEL: 0 */
+    uint32_t alt, depth;
+    int32_t flags;          /* gt (1 or 2) in bits 0-1, GACT_VARIANT_TRUNCATED */
+} gact_variant;             /* 32 bytes */
+typedef struct { int32_t examined, n_ins, n_del, n_snv, first, reserved[3]; } gact_seq_variants;      /* 32 bytes */
+int gact_hip_pileup_variants(gact_hip_engine *e, const gact_variant_params *params /* NULL: defaults */, gact_variant *variants,
+                             int64_t cap, int64_t *n_variants, gact_seq_variants *seqs);
+/* The last gact_hip_pileup_variants call that got as far as the device: HIP events on slot 0's stream around the whole call
+ * (copies and kernels), the chunks, the records per kind, the examined positions, the device memory the pass holds. */
+typedef struct { float device_ms; int32_t chunks; int64_t n_ins, n_del, n_snv, examined, scratch_bytes; } gact_variant_stats;
+int gact_hip_last_variant_stats(gact_hip_engine *e, gact_variant_stats *stats);
+
 /* ------------------------------------------------------------------------
  * D-SOFT seed filter on the device (the stage in front of the path; optional:
  * the reference's host filter keeps working against the calls above).
@@ -1098,6 +1162,21 @@ int64_t gact_hip_format_sam(const gact_overlap *o, const uint32_t *ops, int32_t 
                             const char *query_name, const uint8_t *query_seq /* the ORIGINAL read */, int64_t query_len,
                             const char *ref_name, char *buf, int64_t cap);
 int64_t gact_hip_format_sam_unmapped(const char *query_name, const uint8_t *query_seq, int64_t query_len, char *buf, int64_t cap);
+
+/* One VCF 4.2 line for a record of gact_hip_pileup_variants and the sequence it lies on (seq_len raw bytes); no engine, no
+ * device.  Returns the line's length as gact_hip_format_sam does: with cap too small (cap <= length) nothing useful is in buf.
+ *   name POS . REF ALT . . DP=<depth>;AD=<alt> GT <0/1 for gt 1, 1/1 for gt 2>\n
+ * Reference bytes are upper-cased, and anything that is not A C G T prints as N.  No QUAL: the rule has thresholds, not
+ * likelihoods.
+ *   SNV              POS = pos + 1, REF = seq[pos], ALT = the base
+ *   DEL, pos > 0     POS = pos, REF = seq[pos - 1 .. pos + len), ALT = seq[pos - 1]
+ *   INS, pos > 0     POS = pos, REF = seq[pos - 1], ALT = seq[pos - 1] + the bases
+ *   DEL, pos == 0    (VCF's rule for the first base) POS = 1, REF = seq[0 .. len], ALT = seq[len]; a deletion of the whole
+ *                    sequence has no line: 0 is returned
+ *   INS, pos == 0    POS = 1, REF = seq[0], ALT = the bases + seq[0]
+ * GACT_HIP_EINVAL: a NULL argument, a kind that is none of the three, a gt that is neither 1 nor 2, a record that does not lie
+ * inside the sequence, an INS with len outside [1, 4] or a base that is none of A C G T. */
+int gact_hip_format_vcf(const gact_variant *v, const char *seq_name, const uint8_t *seq, int64_t seq_len, char *buf, size_t cap);
 
 #ifdef __cplusplus
 }
