@@ -13,7 +13,8 @@
 // lane sp - 1.  The arcs of the popped vertex are crossed one after the other, in array order, so the first failure is the
 // model's.  A vertex is popped once, so a search ends after at most 64 pops.
 //
-// The kernels, all on the slot's stream, nothing on the host between them:
+// The kernels, all on the slot's stream, nothing on the host between them.  The first two are arc_graph_index (gact_unitig.hpp),
+// the others bubble_step below, which the cleaning rounds (gact_clean.hpp) call as well, on arcs that are already resident:
 //   unitig_first_kernel, unitig_check_kernel   gact_unitig.hpp's own, with want_bases = 0: the stretches and the arc checks.
 //                          EVERY LATER KERNEL RETURNS AT ONCE WHEN THE FLAG WORD IS SET
 //   unitig_recount_kernel  gact_unitig.hpp's own, with skip widened to int as its cut: out over W
@@ -237,10 +238,29 @@ bubble_flag_kernel(const gact_graph_arc *__restrict__ arcs, int n_arcs, const in
 
 }  // namespace gact
 
-// One allocation: arcs (32 n_arcs) | reads (32 n_reads) | lens (4 n_reads) | clip (8 n_reads, where given) | skip as ints
-// (4 n_reads, where given) | [ out of E0, out of W, found (4 each per vertex) | gone (4 n_reads) | bits (4 n_arcs) | counters (96)
-// | n_found (16) | flag (16) ], zeroed together | first (4 (2 n_reads + 1)) | owner (4 n_reads, set to 0x7f) | read_bubble
-// (4 n_reads, set to 0xff) | bubbles (32 per vertex: every source may find one).
+// The bubble step on an indexed graph (ArcGraphDev, gact_unitig.hpp), as the bubble call and the rounds of gact_clean.hpp
+// make it: W is the arcs with flags == 0 that touch no read of g.skip.  out, found, gone, bits, *n_found and the counters are
+// the caller's to have zeroed; owner and read_bubble are set here.  bits leaves as arc_flags
+static int bubble_step(const gact_hip_engine *e, const ArcGraphDev &g, int *out, const gact_bubble_params &p, int *owner, int *found,
+                       long long *n_found, gact_bubble *bubbles, int *read_bubble, int *gone, int *bits, unsigned long long *counters)
+{
+    const dim3 block(gact::kPassBlock);
+    const size_t n = (size_t)g.n_reads, nv = (size_t)g.nv, na = (size_t)g.n_arcs;
+    HIP_TRY(hipMemsetAsync(owner, 0x7f, n * sizeof(int), g.stream));
+    HIP_TRY(hipMemsetAsync(read_bubble, 0xff, n * sizeof(int), g.stream));
+    hipLaunchKernelGGL(gact::unitig_recount_kernel, lane_blocks(na), block, 0, g.stream, g.arcs, g.n_arcs, g.skip, out, counters, g.flag);
+    hipLaunchKernelGGL(gact::bubble_find_kernel, wave_blocks(e, nv), block, 0, g.stream, g.nv, g.arcs, g.first, g.skip, out, p.max_dist,
+                       p.max_vertices, owner, found, counters, g.flag);
+    hipLaunchKernelGGL(gact::bubble_scan_kernel, dim3(1), block, 0, g.stream, g.nv, found, n_found, g.flag);
+    hipLaunchKernelGGL(gact::bubble_pop_kernel, wave_blocks(e, nv), block, 0, g.stream, g.nv, g.arcs, g.first, g.skip, out, p.max_dist,
+                       p.max_vertices, owner, found, bubbles, read_bubble, gone, bits, counters, g.flag);
+    hipLaunchKernelGGL(gact::bubble_flag_kernel, lane_blocks(na), block, 0, g.stream, g.arcs, g.n_arcs, g.skip, gone, bits, counters, g.flag);
+    return 0;
+}
+
+// One allocation: the graph (ArcGraphDev) | [ out of E0, out of W, found (4 each per vertex) | gone (4 n_reads) | bits (4 n_arcs)
+// | counters (96) | n_found (16) | flag (16) ], zeroed together | first (4 (2 n_reads + 1)) | owner (4 n_reads, set to 0x7f) |
+// read_bubble (4 n_reads, set to 0xff) | bubbles (32 per vertex: every source may find one).
 int gact_hip_pop_bubbles(gact_hip_engine *e, int slot, int32_t n_reads, const int32_t *read_lens, const int32_t *clip,
                          const gact_graph_read *reads, int64_t n_arcs, const gact_graph_arc *arcs, const uint8_t *skip,
                          const gact_bubble_params *params, gact_bubble *bubbles, int64_t bubbles_cap, int64_t *n_bubbles,
@@ -254,11 +274,8 @@ int gact_hip_pop_bubbles(gact_hip_engine *e, int slot, int32_t n_reads, const in
     if (p.max_dist < 1 || p.max_dist > (1 << 30) || p.max_vertices < 3 || p.max_vertices > GACT_BUBBLE_MAX_VERTICES)
         return fail(GACT_HIP_EINVAL, "pop_bubbles: bad parameter (max_dist = %d: 1 .. 2^30; max_vertices = %d: 3 .. %d)", p.max_dist,
                     p.max_vertices, GACT_BUBBLE_MAX_VERTICES);
-    if (n_reads < 0 || n_reads > gact::kUnitigMaxReads || n_arcs < 0 || n_arcs > gact::kUnitigMaxArcs || (n_arcs > 0 && !arcs) ||
-        bubbles_cap < 0)
-        return fail(GACT_HIP_EINVAL, "pop_bubbles: bad arguments (n_reads = %d, at most %d; n_arcs = %lld, at most %lld; bubbles_cap = %lld)",
-                    n_reads, gact::kUnitigMaxReads, (long long)n_arcs, (long long)gact::kUnitigMaxArcs, (long long)bubbles_cap);
-    if (check_read_lens("pop_bubbles", n_reads, read_lens, clip) < 0) return GACT_HIP_EINVAL;
+    if (check_arc_graph("pop_bubbles", n_reads, read_lens, clip, n_arcs, arcs, "bubbles_cap", bubbles_cap, bubbles_cap < 0) < 0)
+        return GACT_HIP_EINVAL;
     if (n_reads == 0) {
         *n_bubbles = 0;
         return 0;
@@ -266,12 +283,9 @@ int gact_hip_pop_bubbles(gact_hip_engine *e, int slot, int32_t n_reads, const in
     if ((rc = set_device(e))) return rc;
     Slot &sl = e->slots[slot];
     PassScratch<gact_bubble_stats> &bb = sl.bubble;
+    ArcGraphDev g = arc_graph_layout(n_reads, clip, n_arcs, skip);
     const size_t n = (size_t)n_reads, nv = 2 * n, na = (size_t)n_arcs;
-    const size_t at_reads = up16(na * sizeof(gact_graph_arc));
-    const size_t at_lens = at_reads + n * sizeof(gact_graph_read);
-    const size_t at_clip = up16(at_lens + n * sizeof(int32_t));
-    const size_t at_skip = up16(at_clip + (clip ? nv * sizeof(int32_t) : 0));
-    const size_t at_out0 = up16(at_skip + (skip ? n * sizeof(int) : 0));
+    const size_t at_out0 = g.end;
     const size_t at_out1 = at_out0 + nv * sizeof(int);
     const size_t at_found = at_out1 + nv * sizeof(int);
     const size_t at_gone = at_found + nv * sizeof(int);
@@ -284,61 +298,21 @@ int gact_hip_pop_bubbles(gact_hip_engine *e, int slot, int32_t n_reads, const in
     const size_t at_read_bubble = at_owner + n * sizeof(int);
     const size_t at_bubbles = up16(at_read_bubble + n * sizeof(int));
     const size_t bytes = at_bubbles + nv * sizeof(gact_bubble);
-    if (bb.reserve(bytes))
-        return fail(GACT_HIP_ENOMEM, "pop_bubbles: device allocation failed (%d reads, %lld arcs, %zu bytes)", n_reads, (long long)n_arcs, bytes);
-    gact_graph_arc *d_arcs = (gact_graph_arc *)bb.p;
-    gact_graph_read *d_reads = (gact_graph_read *)(bb.p + at_reads);
-    int *d_lens = (int *)(bb.p + at_lens);
-    const int *d_clip = clip ? (const int *)(bb.p + at_clip) : nullptr;
-    const int *d_skip = skip ? (const int *)(bb.p + at_skip) : nullptr;
+    if ((rc = arc_graph_begin(g, bb, bytes, sl.stream, "pop_bubbles", read_lens, clip, reads, arcs))) return rc;
     int *d_out0 = (int *)(bb.p + at_out0), *d_out1 = (int *)(bb.p + at_out1), *d_found = (int *)(bb.p + at_found);
     int *d_gone = (int *)(bb.p + at_gone), *d_bits = (int *)(bb.p + at_bits), *d_flag = (int *)(bb.p + at_flag);
     unsigned long long *d_counters = (unsigned long long *)(bb.p + at_counters);
     long long *d_n_found = (long long *)(bb.p + at_n_found);
     int *d_first = (int *)(bb.p + at_first), *d_owner = (int *)(bb.p + at_owner), *d_read_bubble = (int *)(bb.p + at_read_bubble);
     gact_bubble *d_bubbles = (gact_bubble *)(bb.p + at_bubbles);
-    std::vector<int> wide;                                     // (alive until the copy has been waited for, below)
-    if (skip) {
-        wide.resize(n);
-        for (size_t i = 0; i < n; i++) wide[i] = skip[i] != 0;
-    }
-    if ((rc = bb.begin(sl.stream, "pop_bubbles"))) return rc;
-    if (na) HIP_TRY(hipMemcpyAsync(d_arcs, arcs, na * sizeof(gact_graph_arc), hipMemcpyHostToDevice, sl.stream));
-    HIP_TRY(hipMemcpyAsync(d_reads, reads, n * sizeof(gact_graph_read), hipMemcpyHostToDevice, sl.stream));
-    HIP_TRY(hipMemcpyAsync(d_lens, read_lens, n * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
-    if (clip) HIP_TRY(hipMemcpyAsync(bb.p + at_clip, clip, nv * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
-    if (skip) HIP_TRY(hipMemcpyAsync(bb.p + at_skip, wide.data(), n * sizeof(int), hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(hipMemsetAsync(d_out0, 0, at_first - at_out0, sl.stream));
-    HIP_TRY(hipMemsetAsync(d_owner, 0x7f, n * sizeof(int), sl.stream));
-    HIP_TRY(hipMemsetAsync(d_read_bubble, 0xff, n * sizeof(int), sl.stream));
-    const dim3 block(gact::kPassBlock);
-    const int n_a = (int)n_arcs, i_nv = (int)nv;
-    hipLaunchKernelGGL(gact::unitig_first_kernel, lane_blocks(nv + 1), block, 0, sl.stream, i_nv, d_arcs, n_a, d_first);
-    hipLaunchKernelGGL(gact::unitig_check_kernel, lane_blocks(na), block, 0, sl.stream, i_nv, d_arcs, n_a, d_first, d_reads, d_lens, d_clip,
-                       0, d_out0, d_counters, d_flag);
-    hipLaunchKernelGGL(gact::unitig_recount_kernel, lane_blocks(na), block, 0, sl.stream, d_arcs, n_a, d_skip, d_out1, d_counters, d_flag);
-    hipLaunchKernelGGL(gact::bubble_find_kernel, wave_blocks(e, nv), block, 0, sl.stream, i_nv, d_arcs, d_first, d_skip, d_out1, p.max_dist,
-                       p.max_vertices, d_owner, d_found, d_counters, d_flag);
-    hipLaunchKernelGGL(gact::bubble_scan_kernel, dim3(1), block, 0, sl.stream, i_nv, d_found, d_n_found, d_flag);
-    hipLaunchKernelGGL(gact::bubble_pop_kernel, wave_blocks(e, nv), block, 0, sl.stream, i_nv, d_arcs, d_first, d_skip, d_out1, p.max_dist,
-                       p.max_vertices, d_owner, d_found, d_bubbles, d_read_bubble, d_gone, d_bits, d_counters, d_flag);
-    hipLaunchKernelGGL(gact::bubble_flag_kernel, lane_blocks(na), block, 0, sl.stream, d_arcs, n_a, d_skip, d_gone, d_bits, d_counters, d_flag);
-    HIP_TRY(hipGetLastError());
+    arc_graph_index(g, 0, d_first, d_out0, d_counters, d_flag);
+    if ((rc = bubble_step(e, g, d_out1, p, d_owner, d_found, d_n_found, d_bubbles, d_read_bubble, d_gone, d_bits, d_counters))) return rc;
     // the one wait: the flag word and the number of bubbles, before the copies out
-    int flag = 0;
     long long n_found = 0;
     unsigned long long counters[gact::kBubbleCounters];
-    HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, sl.stream));
     HIP_TRY(hipMemcpyAsync(&n_found, d_n_found, sizeof n_found, hipMemcpyDeviceToHost, sl.stream));
-    HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost, sl.stream));
-    HIP_TRY(hipStreamSynchronize(sl.stream));
-    if (flag & gact::kUnitigBadRange)
-        return fail(GACT_HIP_EINVAL, "pop_bubbles: an arc with u or v outside [0, %zu), between the two vertices of one read, or with len < 1", nv);
-    if (flag & gact::kUnitigBadOrder) return fail(GACT_HIP_EINVAL, "pop_bubbles: the arcs are not ascending by (u, len, v)");
-    if (flag & gact::kUnitigNotLive)
-        return fail(GACT_HIP_EINVAL, "pop_bubbles: an arc with flags == 0 names a read that is not live (contained, or clipped to nothing)");
-    if (flag & gact::kUnitigNoComplement)
-        return fail(GACT_HIP_EINVAL, "pop_bubbles: an arc with flags == 0 whose complement v^1 -> u^1 is not among the arcs with flags == 0");
+    if ((rc = arc_graph_fetch(g, "pop_bubbles", d_counters, counters, gact::kBubbleCounters))) return rc;
     if (n_found < 0 || n_found > (long long)nv || n_found != (long long)counters[gact::kBubbleFoundN])
         return fail(GACT_HIP_EDEVICE, "pop_bubbles: the device numbered %lld bubbles and counted %llu", n_found, counters[gact::kBubbleFoundN]);
     const bool room = bubbles && bubbles_cap >= n_found;

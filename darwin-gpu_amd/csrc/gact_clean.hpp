@@ -14,8 +14,9 @@
 //   prune_mirror_kernel    one lane per arc: a weak arc sets the removed bit of itself and, by the walk through v^1's stretch
 //                          that unitig_check_kernel makes, of its complement (atomicOr: both may be weak)
 //   prune_count_kernel     one lane per vertex: its W arcs before and after, bared, the removed ones, and bits[] becomes arc_flags
-// The loop launches, on one upload of the arcs, gact_unitig.hpp's kernels up to the tip rule (recount, links, init, jump, tip),
-// gact_bubble.hpp's (recount, find, scan, pop, flag) and the three above, each on the flags the steps in front left, and
+// prune_step launches the three; the stretches and the checks are arc_graph_index (gact_unitig.hpp).  The loop calls, on one
+// upload and one index of the arcs, the stand-alone calls' own step functions -- unitig_sweep and the tip rule, bubble_step,
+// prune_step -- each on the flags the steps in front left, and behind each one of its own kernels:
 //   clean_init_kernel      one lane per read: its first state
 //   clean_tip_kernel       one lane per arc, vertex and read: GACT_GRAPH_ARC_TIP into the flags of an arc that touches a cut read
 //                          (its own arc: a plain store), the heads of the tip rule's chains, the state of a read cut for the
@@ -182,23 +183,21 @@ clean_flags_kernel(const gact_graph_arc *__restrict__ arcs, int n_arcs, int *__r
 
 }  // namespace gact
 
-// what the flag word says, in the words of the unitig and bubble calls
-static int clean_flag_refusal(const char *who, int flag, size_t nv)
+// The prune step on an indexed graph (ArcGraphDev, gact_unitig.hpp), as the prune call and the rounds make it: W is the arcs
+// with flags == 0 that touch no read of g.skip.  bits and the counters are the caller's to have zeroed; bits leaves as arc_flags,
+// best (NULL: not wanted) as vertex_best
+static void prune_step(const gact_hip_engine *e, const ArcGraphDev &g, int ratio, int *bits, int *best, unsigned long long *counters)
 {
-    if (flag & gact::kUnitigBadRange)
-        return fail(GACT_HIP_EINVAL, "%s: an arc with u or v outside [0, %zu), between the two vertices of one read, or with len < 1", who, nv);
-    if (flag & gact::kUnitigBadOrder) return fail(GACT_HIP_EINVAL, "%s: the arcs are not ascending by (u, len, v)", who);
-    if (flag & gact::kUnitigNotLive)
-        return fail(GACT_HIP_EINVAL, "%s: an arc with flags == 0 names a read that is not live (contained, or clipped to nothing)", who);
-    if (flag & gact::kUnitigNoComplement)
-        return fail(GACT_HIP_EINVAL, "%s: an arc with flags == 0 whose complement v^1 -> u^1 is not among the arcs with flags == 0", who);
-    if (flag) return fail(GACT_HIP_EDEVICE, "%s: the device left the flag word %d", who, flag);
-    return 0;
+    const dim3 block(gact::kPassBlock);
+    const size_t nv = (size_t)g.nv, na = (size_t)g.n_arcs;
+    hipLaunchKernelGGL(gact::prune_mark_kernel, wave_blocks(e, nv), block, 0, g.stream, g.nv, g.arcs, g.first, g.skip, ratio, bits, best,
+                       counters, g.flag);
+    hipLaunchKernelGGL(gact::prune_mirror_kernel, lane_blocks(na), block, 0, g.stream, g.arcs, g.n_arcs, g.first, bits, g.flag);
+    hipLaunchKernelGGL(gact::prune_count_kernel, lane_blocks(nv), block, 0, g.stream, g.nv, g.arcs, g.first, g.skip, bits, counters, g.flag);
 }
 
-// One allocation: arcs (32 n_arcs) | reads (32 n_reads) | lens (4 n_reads) | clip (8 n_reads, where given) | skip as ints
-// (4 n_reads, where given) | [ out of E0 (4 per vertex) | bits (4 n_arcs) | counters (64) | flag (16) ], zeroed together |
-// first (4 (2 n_reads + 1)) | best (4 per vertex).
+// One allocation: the graph (ArcGraphDev) | [ out of E0 (4 per vertex) | bits (4 n_arcs) | counters (64) | flag (16) ], zeroed
+// together | first (4 (2 n_reads + 1)) | best (4 per vertex).
 int gact_hip_prune_overlaps(gact_hip_engine *e, int slot, int32_t n_reads, const int32_t *read_lens, const int32_t *clip,
                             const gact_graph_read *reads, int64_t n_arcs, const gact_graph_arc *arcs, const uint8_t *skip,
                             const gact_prune_params *params, int32_t *arc_flags, int32_t *vertex_best)
@@ -210,66 +209,30 @@ int gact_hip_prune_overlaps(gact_hip_engine *e, int slot, int32_t n_reads, const
     const gact_prune_params p = params ? *params : gact_prune_params{GACT_PRUNE_DEFAULT_RATIO_PERMILLE};
     if (p.ratio_permille < 0 || p.ratio_permille > 1000)
         return fail(GACT_HIP_EINVAL, "prune_overlaps: bad parameter (ratio_permille = %d: 0 .. 1000)", p.ratio_permille);
-    if (n_reads < 0 || n_reads > gact::kUnitigMaxReads || n_arcs < 0 || n_arcs > gact::kUnitigMaxArcs || (n_arcs > 0 && !arcs))
-        return fail(GACT_HIP_EINVAL, "prune_overlaps: bad arguments (n_reads = %d, at most %d; n_arcs = %lld, at most %lld)", n_reads,
-                    gact::kUnitigMaxReads, (long long)n_arcs, (long long)gact::kUnitigMaxArcs);
-    if (check_read_lens("prune_overlaps", n_reads, read_lens, clip) < 0) return GACT_HIP_EINVAL;
+    if (check_arc_graph("prune_overlaps", n_reads, read_lens, clip, n_arcs, arcs) < 0) return GACT_HIP_EINVAL;
     if (n_reads == 0) return 0;
     if ((rc = set_device(e))) return rc;
     Slot &sl = e->slots[slot];
     PassScratch<gact_prune_stats> &pb = sl.prune;
-    const size_t n = (size_t)n_reads, nv = 2 * n, na = (size_t)n_arcs;
-    const size_t at_reads = up16(na * sizeof(gact_graph_arc));
-    const size_t at_lens = at_reads + n * sizeof(gact_graph_read);
-    const size_t at_clip = up16(at_lens + n * sizeof(int32_t));
-    const size_t at_skip = up16(at_clip + (clip ? nv * sizeof(int32_t) : 0));
-    const size_t at_out0 = up16(at_skip + (skip ? n * sizeof(int) : 0));
+    ArcGraphDev g = arc_graph_layout(n_reads, clip, n_arcs, skip);
+    const size_t nv = 2 * (size_t)n_reads, na = (size_t)n_arcs;
+    const size_t at_out0 = g.end;
     const size_t at_bits = at_out0 + nv * sizeof(int);
     const size_t at_counters = up16(at_bits + na * sizeof(int));
     const size_t at_flag = at_counters + 8 * sizeof(unsigned long long);
     const size_t at_first = at_flag + 16;
     const size_t at_best = up16(at_first + (nv + 1) * sizeof(int));
     const size_t bytes = at_best + nv * sizeof(int);
-    if (pb.reserve(bytes))
-        return fail(GACT_HIP_ENOMEM, "prune_overlaps: device allocation failed (%d reads, %lld arcs, %zu bytes)", n_reads, (long long)n_arcs, bytes);
-    gact_graph_arc *d_arcs = (gact_graph_arc *)pb.p;
-    gact_graph_read *d_reads = (gact_graph_read *)(pb.p + at_reads);
-    int *d_lens = (int *)(pb.p + at_lens);
-    const int *d_clip = clip ? (const int *)(pb.p + at_clip) : nullptr;
-    const int *d_skip = skip ? (const int *)(pb.p + at_skip) : nullptr;
+    if ((rc = arc_graph_begin(g, pb, bytes, sl.stream, "prune_overlaps", read_lens, clip, reads, arcs))) return rc;
     int *d_out0 = (int *)(pb.p + at_out0), *d_bits = (int *)(pb.p + at_bits), *d_flag = (int *)(pb.p + at_flag);
     unsigned long long *d_counters = (unsigned long long *)(pb.p + at_counters);
     int *d_first = (int *)(pb.p + at_first), *d_best = (int *)(pb.p + at_best);
-    std::vector<int> wide;                                     // (alive until the copy has been waited for, below)
-    if (skip) {
-        wide.resize(n);
-        for (size_t i = 0; i < n; i++) wide[i] = skip[i] != 0;
-    }
-    if ((rc = pb.begin(sl.stream, "prune_overlaps"))) return rc;
-    if (na) HIP_TRY(hipMemcpyAsync(d_arcs, arcs, na * sizeof(gact_graph_arc), hipMemcpyHostToDevice, sl.stream));
-    HIP_TRY(hipMemcpyAsync(d_reads, reads, n * sizeof(gact_graph_read), hipMemcpyHostToDevice, sl.stream));
-    HIP_TRY(hipMemcpyAsync(d_lens, read_lens, n * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
-    if (clip) HIP_TRY(hipMemcpyAsync(pb.p + at_clip, clip, nv * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
-    if (skip) HIP_TRY(hipMemcpyAsync(pb.p + at_skip, wide.data(), n * sizeof(int), hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(hipMemsetAsync(d_out0, 0, at_first - at_out0, sl.stream));
-    const dim3 block(gact::kPassBlock);
-    const int n_a = (int)n_arcs, i_nv = (int)nv;
-    hipLaunchKernelGGL(gact::unitig_first_kernel, lane_blocks(nv + 1), block, 0, sl.stream, i_nv, d_arcs, n_a, d_first);
-    hipLaunchKernelGGL(gact::unitig_check_kernel, lane_blocks(na), block, 0, sl.stream, i_nv, d_arcs, n_a, d_first, d_reads, d_lens, d_clip,
-                       0, d_out0, d_counters, d_flag);
-    hipLaunchKernelGGL(gact::prune_mark_kernel, wave_blocks(e, nv), block, 0, sl.stream, i_nv, d_arcs, d_first, d_skip, p.ratio_permille,
-                       d_bits, d_best, d_counters, d_flag);
-    hipLaunchKernelGGL(gact::prune_mirror_kernel, lane_blocks(na), block, 0, sl.stream, d_arcs, n_a, d_first, d_bits, d_flag);
-    hipLaunchKernelGGL(gact::prune_count_kernel, lane_blocks(nv), block, 0, sl.stream, i_nv, d_arcs, d_first, d_skip, d_bits, d_counters,
-                       d_flag);
-    HIP_TRY(hipGetLastError());
+    arc_graph_index(g, 0, d_first, d_out0, d_counters, d_flag);
+    prune_step(e, g, p.ratio_permille, d_bits, d_best, d_counters);
     // the one wait: the flag word, before the copies out
-    int flag = 0;
     unsigned long long counters[8];
-    HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, sl.stream));
-    HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost, sl.stream));
-    HIP_TRY(hipStreamSynchronize(sl.stream));
-    if ((rc = clean_flag_refusal("prune_overlaps", flag, nv))) return rc;
+    if ((rc = arc_graph_fetch(g, "prune_overlaps", d_counters, counters, 8))) return rc;
     if (na) HIP_TRY(hipMemcpyAsync(arc_flags, d_bits, na * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
     if (vertex_best) HIP_TRY(hipMemcpyAsync(vertex_best, d_best, nv * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
     if ((rc = pb.end(sl.stream))) return rc;
@@ -289,9 +252,8 @@ int gact_hip_last_prune_stats(gact_hip_engine *e, int slot, gact_prune_stats *st
     return last_pass_stats(e, slot, &Slot::prune, stats, "last_prune_stats", "has pruned no overlaps yet");
 }
 
-// One allocation: arcs (32 n_arcs) | reads (32 n_reads) | lens (4 n_reads) | clip (8 n_reads, where given) |
-// [ out, found (4 each per vertex) | gone (4 n_reads) | bits (4 n_arcs) | counters (128) | n_found (16) ], zeroed together in front
-// of every step | flag (16), zeroed once | first (4 (2 n_reads + 1)) | prev, len_in, len_out (4 each per vertex) | cut, owner,
+// One allocation: the graph (ArcGraphDev, no skip) | [ out, found (4 each per vertex) | gone (4 n_reads) | bits (4 n_arcs) |
+// counters (128) | n_found (16) ], zeroed together in front of every step | flag (16), zeroed once | first (4 (2 n_reads + 1)) | prev, len_in, len_out (4 each per vertex) | cut, owner,
 // read_bubble (4 each per read) | rank a, rank b (24 each per vertex) | bubbles (32 per vertex) | state (8 n_reads).
 int gact_hip_clean_graph(gact_hip_engine *e, int slot, int32_t n_reads, const int32_t *read_lens, const int32_t *clip,
                          const gact_graph_read *reads, int64_t n_arcs, const gact_graph_arc *arcs, const gact_clean_params *params,
@@ -311,11 +273,8 @@ int gact_hip_clean_graph(gact_hip_engine *e, int slot, int32_t n_reads, const in
         p.n_ratios > GACT_CLEAN_MAX_RATIOS || p.max_passes < 1 || p.max_passes > GACT_CLEAN_MAX_PASSES)
         return fail(GACT_HIP_EINVAL, "clean_graph: bad parameter (ratios %d .. %d: 0 <= lo <= hi <= 1000; n_ratios = %d: 0 .. %d; max_passes = %d: 1 .. %d)",
                     p.ratio_lo_permille, p.ratio_hi_permille, p.n_ratios, GACT_CLEAN_MAX_RATIOS, p.max_passes, GACT_CLEAN_MAX_PASSES);
-    if (n_reads < 0 || n_reads > gact::kUnitigMaxReads || n_arcs < 0 || n_arcs > gact::kUnitigMaxArcs || (n_arcs > 0 && !arcs) ||
-        steps_cap < 0)
-        return fail(GACT_HIP_EINVAL, "clean_graph: bad arguments (n_reads = %d, at most %d; n_arcs = %lld, at most %lld; steps_cap = %lld)",
-                    n_reads, gact::kUnitigMaxReads, (long long)n_arcs, (long long)gact::kUnitigMaxArcs, (long long)steps_cap);
-    if (check_read_lens("clean_graph", n_reads, read_lens, clip) < 0) return GACT_HIP_EINVAL;
+    if (check_arc_graph("clean_graph", n_reads, read_lens, clip, n_arcs, arcs, "steps_cap", steps_cap, steps_cap < 0) < 0)
+        return GACT_HIP_EINVAL;
     if (n_reads == 0) {
         *n_steps = 0;
         return 0;
@@ -323,11 +282,9 @@ int gact_hip_clean_graph(gact_hip_engine *e, int slot, int32_t n_reads, const in
     if ((rc = set_device(e))) return rc;
     Slot &sl = e->slots[slot];
     PassScratch<gact_clean_stats> &cb = sl.clean;
+    ArcGraphDev g = arc_graph_layout(n_reads, clip, n_arcs, nullptr);
     const size_t n = (size_t)n_reads, nv = 2 * n, na = (size_t)n_arcs;
-    const size_t at_reads = up16(na * sizeof(gact_graph_arc));
-    const size_t at_lens = at_reads + n * sizeof(gact_graph_read);
-    const size_t at_clip = up16(at_lens + n * sizeof(int32_t));
-    const size_t at_out = up16(at_clip + (clip ? nv * sizeof(int32_t) : 0));
+    const size_t at_out = g.end;
     const size_t at_found = at_out + nv * sizeof(int);
     const size_t at_gone = at_found + nv * sizeof(int);
     const size_t at_bits = at_gone + n * sizeof(int);
@@ -346,50 +303,28 @@ int gact_hip_clean_graph(gact_hip_engine *e, int slot, int32_t n_reads, const in
     const size_t at_bubbles = up16(at_rank_b + nv * sizeof(gact::UnitigRank));
     const size_t at_state = at_bubbles + nv * sizeof(gact_bubble);
     const size_t bytes = at_state + n * sizeof(gact_clean_read);
-    if (cb.reserve(bytes))
-        return fail(GACT_HIP_ENOMEM, "clean_graph: device allocation failed (%d reads, %lld arcs, %zu bytes)", n_reads, (long long)n_arcs, bytes);
-    gact_graph_arc *d_arcs = (gact_graph_arc *)cb.p;
-    gact_graph_read *d_reads = (gact_graph_read *)(cb.p + at_reads);
-    int *d_lens = (int *)(cb.p + at_lens);
-    const int *d_clip = clip ? (const int *)(cb.p + at_clip) : nullptr;
+    if ((rc = arc_graph_begin(g, cb, bytes, sl.stream, "clean_graph", read_lens, clip, reads, arcs))) return rc;
     int *d_out = (int *)(cb.p + at_out), *d_found = (int *)(cb.p + at_found), *d_gone = (int *)(cb.p + at_gone);
     int *d_bits = (int *)(cb.p + at_bits), *d_flag = (int *)(cb.p + at_flag);
     unsigned long long *d_counters = (unsigned long long *)(cb.p + at_counters);
     long long *d_n_found = (long long *)(cb.p + at_n_found);
-    int *d_first = (int *)(cb.p + at_first), *d_prev = (int *)(cb.p + at_prev), *d_len_in = (int *)(cb.p + at_len_in);
-    int *d_len_out = (int *)(cb.p + at_len_out), *d_cut = (int *)(cb.p + at_cut), *d_owner = (int *)(cb.p + at_owner);
+    int *d_first = (int *)(cb.p + at_first), *d_cut = (int *)(cb.p + at_cut), *d_owner = (int *)(cb.p + at_owner);
     int *d_read_bubble = (int *)(cb.p + at_read_bubble);
-    gact::UnitigRank *d_rank[2] = {(gact::UnitigRank *)(cb.p + at_rank_a), (gact::UnitigRank *)(cb.p + at_rank_b)};
+    const UnitigRankBufs rb{(int *)(cb.p + at_prev), (int *)(cb.p + at_len_in), (int *)(cb.p + at_len_out), nullptr,
+                            {(gact::UnitigRank *)(cb.p + at_rank_a), (gact::UnitigRank *)(cb.p + at_rank_b)}};
     gact_bubble *d_bubbles = (gact_bubble *)(cb.p + at_bubbles);
     gact_clean_read *d_state = (gact_clean_read *)(cb.p + at_state);
-    if ((rc = cb.begin(sl.stream, "clean_graph"))) return rc;
-    if (na) HIP_TRY(hipMemcpyAsync(d_arcs, arcs, na * sizeof(gact_graph_arc), hipMemcpyHostToDevice, sl.stream));
-    HIP_TRY(hipMemcpyAsync(d_reads, reads, n * sizeof(gact_graph_read), hipMemcpyHostToDevice, sl.stream));
-    HIP_TRY(hipMemcpyAsync(d_lens, read_lens, n * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
-    if (clip) HIP_TRY(hipMemcpyAsync(cb.p + at_clip, clip, nv * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(hipMemsetAsync(d_out, 0, at_first - at_out, sl.stream));
     const dim3 block(gact::kPassBlock);
-    int rounds = 1;
-    while (((size_t)1 << rounds) < nv) rounds++;
-    const int n_a = (int)n_arcs, i_nv = (int)nv;
     // the stretches and the arc checks, once: no step moves an arc, and every step leaves the arcs with flags == 0 closed under
     // complement and between live reads
-    hipLaunchKernelGGL(gact::unitig_first_kernel, lane_blocks(nv + 1), block, 0, sl.stream, i_nv, d_arcs, n_a, d_first);
-    hipLaunchKernelGGL(gact::unitig_check_kernel, lane_blocks(na), block, 0, sl.stream, i_nv, d_arcs, n_a, d_first, d_reads, d_lens, d_clip,
-                       0, d_out, d_counters, d_flag);
-    hipLaunchKernelGGL(gact::clean_init_kernel, lane_blocks(n), block, 0, sl.stream, n_reads, d_reads, d_lens, d_clip, d_state);
+    arc_graph_index(g, 0, d_first, d_out, d_counters, d_flag);
+    hipLaunchKernelGGL(gact::clean_init_kernel, lane_blocks(n), block, 0, sl.stream, n_reads, g.reads, g.lens, g.clip, d_state);
     std::vector<gact_clean_step> log;
     gact_clean_stats st{};
     unsigned long long counters[gact::kCleanCounters];
     // what every step ends with: its counters and the flag word on the host
-    auto fetch = [&]() -> int {
-        int flag = 0;
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, sl.stream));
-        HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost, sl.stream));
-        HIP_TRY(hipStreamSynchronize(sl.stream));
-        return clean_flag_refusal("clean_graph", flag, nv);
-    };
+    auto fetch = [&]() { return arc_graph_fetch(g, "clean_graph", d_counters, counters, gact::kCleanCounters); };
     auto record = [&](int kind, int param, unsigned long long reads_removed, unsigned long long examined, unsigned long long had,
                       unsigned long long removed) {
         gact_clean_step s;
@@ -401,40 +336,26 @@ int gact_hip_clean_graph(gact_hip_engine *e, int slot, int32_t n_reads, const in
     };
     // T: the first sweep of the unitig call and its tip rule on the arcs as they are; -> the arcs removed, or < 0
     auto tips = [&]() -> long long {
-        HIP_TRY(hipMemsetAsync(d_out, 0, at_flag - at_out, sl.stream));
-        HIP_TRY(hipMemsetAsync(d_prev, 0xff, nv * sizeof(int), sl.stream));
-        hipLaunchKernelGGL(gact::unitig_recount_kernel, lane_blocks(na), block, 0, sl.stream, d_arcs, n_a, nullptr, d_out, d_counters, d_flag);
-        hipLaunchKernelGGL(gact::unitig_links_kernel, lane_blocks(na), block, 0, sl.stream, d_arcs, n_a, nullptr, d_out, d_prev, d_len_in,
-                           d_len_out, nullptr, d_flag);
-        hipLaunchKernelGGL(gact::unitig_init_kernel, lane_blocks(nv), block, 0, sl.stream, i_nv, d_prev, d_len_in, nullptr, nullptr, d_rank[0],
-                           d_flag);
-        int cur = 0;
-        for (int r = 0; r < rounds; r++, cur ^= 1)
-            hipLaunchKernelGGL(gact::unitig_jump_kernel, lane_blocks(nv), block, 0, sl.stream, i_nv, d_rank[cur], d_rank[cur ^ 1], d_flag);
-        hipLaunchKernelGGL(gact::unitig_tip_kernel, lane_blocks(n), block, 0, sl.stream, n_reads, d_reads, d_lens, d_clip, d_prev, d_out,
-                           d_rank[cur], p.tip_reads, d_cut, d_counters, d_flag);
-        hipLaunchKernelGGL(gact::clean_tip_kernel, lane_blocks(std::max(na, nv)), block, 0, sl.stream, n_reads, d_arcs, n_a, d_reads, d_lens,
-                           d_clip, d_prev, d_cut, (int)log.size(), d_state, d_counters, d_flag);
+        const gact::UnitigRank *ranks;
+        HIP_TRY(hipMemsetAsync(d_out, 0, at_flag - at_out, sl.stream));      // (the step's block; the flag word stays)
+        if (int bad = unitig_sweep(g, rb, nullptr, d_out, nullptr, d_counters, nullptr, &ranks, nullptr)) return bad;
+        hipLaunchKernelGGL(gact::unitig_tip_kernel, lane_blocks(n), block, 0, sl.stream, n_reads, g.reads, g.lens, g.clip, rb.prev, d_out,
+                           ranks, p.tip_reads, d_cut, d_counters, d_flag);
+        hipLaunchKernelGGL(gact::clean_tip_kernel, lane_blocks(std::max(na, nv)), block, 0, sl.stream, n_reads, g.arcs, g.n_arcs, g.reads, g.lens,
+                           g.clip, rb.prev, d_cut, (int)log.size(), d_state, d_counters, d_flag);
         if (int bad = fetch()) return bad < 0 ? bad : -1;
         record(GACT_CLEAN_TIPS, p.tip_reads, counters[gact::kCleanReads], counters[gact::kCleanHeads], counters[gact::kUnitigE1],
                counters[gact::kCleanArcs]);
         st.reads_tip += (int32_t)counters[gact::kCleanReads];
         return (long long)counters[gact::kCleanArcs];
     };
-    // B: the kernels of the bubble call behind its checks, skip NULL
+    // B: the bubble call's step, no read skipped
     auto bubbles = [&]() -> long long {
-        HIP_TRY(hipMemsetAsync(d_out, 0, at_flag - at_out, sl.stream));
-        HIP_TRY(hipMemsetAsync(d_owner, 0x7f, n * sizeof(int), sl.stream));
-        HIP_TRY(hipMemsetAsync(d_read_bubble, 0xff, n * sizeof(int), sl.stream));
-        hipLaunchKernelGGL(gact::unitig_recount_kernel, lane_blocks(na), block, 0, sl.stream, d_arcs, n_a, nullptr, d_out, d_counters, d_flag);
-        hipLaunchKernelGGL(gact::bubble_find_kernel, wave_blocks(e, nv), block, 0, sl.stream, i_nv, d_arcs, d_first, nullptr, d_out, p.max_dist,
-                           p.max_vertices, d_owner, d_found, d_counters, d_flag);
-        hipLaunchKernelGGL(gact::bubble_scan_kernel, dim3(1), block, 0, sl.stream, i_nv, d_found, d_n_found, d_flag);
-        hipLaunchKernelGGL(gact::bubble_pop_kernel, wave_blocks(e, nv), block, 0, sl.stream, i_nv, d_arcs, d_first, nullptr, d_out, p.max_dist,
-                           p.max_vertices, d_owner, d_found, d_bubbles, d_read_bubble, d_gone, d_bits, d_counters, d_flag);
-        hipLaunchKernelGGL(gact::bubble_flag_kernel, lane_blocks(na), block, 0, sl.stream, d_arcs, n_a, nullptr, d_gone, d_bits, d_counters,
-                           d_flag);
-        hipLaunchKernelGGL(gact::clean_apply_kernel, lane_blocks(std::max(na, n)), block, 0, sl.stream, d_arcs, n_a, d_bits, n_reads, d_gone,
+        HIP_TRY(hipMemsetAsync(d_out, 0, at_flag - at_out, sl.stream));      // (the step's block; the flag word stays)
+        if (int bad = bubble_step(e, g, d_out, gact_bubble_params{p.max_dist, p.max_vertices}, d_owner, d_found, d_n_found, d_bubbles,
+                                  d_read_bubble, d_gone, d_bits, d_counters))
+            return bad;
+        hipLaunchKernelGGL(gact::clean_apply_kernel, lane_blocks(std::max(na, n)), block, 0, sl.stream, g.arcs, g.n_arcs, d_bits, n_reads, d_gone,
                            (int)log.size(), d_state, d_flag);
         if (int bad = fetch()) return bad < 0 ? bad : -1;
         record(GACT_CLEAN_BUBBLES, p.max_dist, counters[gact::kBubbleReadsRemoved], counters[gact::kBubbleSources], counters[gact::kBubbleW],
@@ -442,14 +363,11 @@ int gact_hip_clean_graph(gact_hip_engine *e, int slot, int32_t n_reads, const in
         st.reads_bubble += (int32_t)counters[gact::kBubbleReadsRemoved];
         return (long long)counters[gact::kBubbleArcsRemoved];
     };
+    // P: the prune call's step, no read skipped, vertex_best not wanted
     auto prune = [&](int ratio) -> long long {
-        HIP_TRY(hipMemsetAsync(d_out, 0, at_flag - at_out, sl.stream));
-        hipLaunchKernelGGL(gact::prune_mark_kernel, wave_blocks(e, nv), block, 0, sl.stream, i_nv, d_arcs, d_first, nullptr, ratio, d_bits,
-                           nullptr, d_counters, d_flag);
-        hipLaunchKernelGGL(gact::prune_mirror_kernel, lane_blocks(na), block, 0, sl.stream, d_arcs, n_a, d_first, d_bits, d_flag);
-        hipLaunchKernelGGL(gact::prune_count_kernel, lane_blocks(nv), block, 0, sl.stream, i_nv, d_arcs, d_first, nullptr, d_bits, d_counters,
-                           d_flag);
-        hipLaunchKernelGGL(gact::clean_apply_kernel, lane_blocks(na), block, 0, sl.stream, d_arcs, n_a, d_bits, n_reads, nullptr,
+        HIP_TRY(hipMemsetAsync(d_out, 0, at_flag - at_out, sl.stream));      // (the step's block; the flag word stays)
+        prune_step(e, g, ratio, d_bits, nullptr, d_counters);
+        hipLaunchKernelGGL(gact::clean_apply_kernel, lane_blocks(na), block, 0, sl.stream, g.arcs, g.n_arcs, d_bits, n_reads, nullptr,
                            (int)log.size(), d_state, d_flag);
         if (int bad = fetch()) return bad < 0 ? bad : -1;
         record(GACT_CLEAN_PRUNE, ratio, 0, counters[gact::kPruneExamined], counters[gact::kPruneW], counters[gact::kPruneRemoved]);
@@ -474,7 +392,7 @@ int gact_hip_clean_graph(gact_hip_engine *e, int slot, int32_t n_reads, const in
         if (removed < 0) return (int)removed;
         if (removed > 0 && (rc = settle())) return rc;
     }
-    hipLaunchKernelGGL(gact::clean_flags_kernel, lane_blocks(na), block, 0, sl.stream, d_arcs, n_a, d_bits, d_flag);
+    hipLaunchKernelGGL(gact::clean_flags_kernel, lane_blocks(na), block, 0, sl.stream, g.arcs, g.n_arcs, d_bits, d_flag);
     HIP_TRY(hipGetLastError());
     if (na) HIP_TRY(hipMemcpyAsync(arc_flags, d_bits, na * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
     HIP_TRY(hipMemcpyAsync(read_state, d_state, n * sizeof(gact_clean_read), hipMemcpyDeviceToHost, sl.stream));

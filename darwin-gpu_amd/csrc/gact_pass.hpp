@@ -17,6 +17,16 @@
 // and its gact_hip_last_*_stats is one call of last_pass_stats.  Its kernels start from gact_pass_device.hpp: kPassBlock
 // threads a block (the grids: lane_blocks, wave_blocks, full_device_blocks below), offsets by block_scan_step, a best-of-key table by
 // table_insert_best / table_find, counters by wave_count.
+//
+// A pass on an arc graph (n_reads, read_lens, clip, reads, n_arcs, arcs[, skip]: unitigs, bubbles, weak arcs, the cleaning
+// rounds) starts from the host part of gact_unitig.hpp, behind the kernels it launches.  Its entry point reads:
+//
+//     its own NULL list and parameter checks, then check_arc_graph (the bounds, the arcs, the lengths and clips)
+//     ArcGraphDev g = arc_graph_layout(...);                 // arcs | reads | lens | clip | skip; its own ladder starts at g.end
+//     arc_graph_begin(g, ps, bytes, ...): reserve, begin and the copies in; then the memset of its zeroed block
+//     arc_graph_index(g, want_bases, first, out, counters, flag);   // the stretches and the arc checks; g keeps first and flag
+//     its steps (unitig_sweep, bubble_step, prune_step, or kernels of its own that return at once when *flag is set)
+//     arc_graph_fetch(g, who, ...): the wait, the counters, and arc_graph_refusal's one wording of what the check kernel refused
 #pragma once
 
 extern "C++" {                  // (templates: not in gact_engine.hip's extern "C")

@@ -32,7 +32,8 @@
 //   unitig_bases_kernel    one wave per layout entry, grid-stride; lanes stride over the entry's take: a forward entry reads
 //                          ascending addresses, a reverse one descending addresses, both write ascending ones: coalesced on
 //                          both sides, one byte per lane and step
-// Three sweeps: on E0 for the tip rule, on E1 to find the cycles and their lowest ids, and on E1 with the cycles opened.
+// Three sweeps (unitig_sweep: links, init, the jumps): on E0 for the tip rule, on E1 to find the cycles and their lowest ids, and on
+// E1 with the cycles opened.  first and check are arc_graph_index: what every pass on an arc graph starts with.
 // Ordinary vector global atomics on integers; every value they leave is the same in whichever order they land.  No LDS but
 // the scan's, no spinning on other waves, no cooperative grid.
 //
@@ -43,7 +44,7 @@ namespace gact {
 
 constexpr int32_t kUnitigMaxReads = 1 << 30;               // (a vertex 2 i + 1 fits an int32)
 constexpr int64_t kUnitigMaxArcs = 1 << 29;
-// bits of the flag word
+// bits of the flag word (worded by arc_graph_refusal, below the kernels)
 constexpr int kUnitigBadRange = 1, kUnitigBadOrder = 2, kUnitigNotLive = 4, kUnitigNoComplement = 8, kUnitigLongArc = 16;
 // the counters
 constexpr int kUnitigE0 = 0, kUnitigE1 = 1, kUnitigJoins = 2, kUnitigCut = 3, kUnitigContained = 4, kUnitigCircular = 5,
@@ -371,7 +372,148 @@ unitig_bases_kernel(const UnitigTotals *__restrict__ totals, const gact_unitig_e
 
 }  // namespace gact
 
-// One allocation: arcs (32 n_arcs) | reads (32 n_reads) | lens (4 n_reads) | clip (8 n_reads, where given) |
+// ---- What a pass on an arc graph starts from (unitigs, gact_bubble.hpp, gact_clean.hpp; gact_pass.hpp says how)
+
+// The refusals those calls share, behind each call's own NULL list and parameter checks: the bounds, the arcs, the lengths and
+// clips -> the clipped total, or the refusal's code (< 0).  own: NULL, or the name of the call's own figure at the sentence's end
+static int64_t check_arc_graph(const char *who, int32_t n_reads, const int32_t *read_lens, const int32_t *clip, int64_t n_arcs,
+                               const gact_graph_arc *arcs, const char *own = nullptr, int64_t own_value = 0, bool own_bad = false)
+{
+    if (n_reads < 0 || n_reads > gact::kUnitigMaxReads || n_arcs < 0 || n_arcs > gact::kUnitigMaxArcs || (n_arcs > 0 && !arcs) || own_bad) {
+        char tail[64] = "";
+        if (own) snprintf(tail, sizeof tail, "; %s = %lld", own, (long long)own_value);
+        return fail(GACT_HIP_EINVAL, "%s: bad arguments (n_reads = %d, at most %d; n_arcs = %lld, at most %lld%s)", who, n_reads,
+                    gact::kUnitigMaxReads, (long long)n_arcs, (long long)gact::kUnitigMaxArcs, tail);
+    }
+    return check_read_lens(who, n_reads, read_lens, clip);
+}
+
+// The graph on the device.  A pass's scratch begins arcs (32 n_arcs) | reads (32 n_reads) | lens (4 n_reads) | clip (8 n_reads,
+// where given) | skip as ints (4 n_reads, where given), and its own part begins at `end`.  first and flag are the pass's own,
+// kept here by arc_graph_index because every later launch takes them.
+struct ArcGraphDev {
+    int n_reads, nv, n_arcs;
+    size_t at_reads, at_lens, at_clip, at_skip, end;
+    gact_graph_arc *arcs;
+    const gact_graph_read *reads;
+    const int *lens, *clip, *skip, *first;                     // clip, skip: NULL where the caller gave none
+    int *flag;
+    hipStream_t stream;
+    std::vector<int> wide;                                     // skip as ints: alive until the copies in have been waited for
+};
+
+// the layout (n_reads > 0), and skip widened: host work in front of the call's first event
+static ArcGraphDev arc_graph_layout(int32_t n_reads, const int32_t *clip, int64_t n_arcs, const uint8_t *skip)
+{
+    ArcGraphDev g{};
+    const size_t n = (size_t)n_reads;
+    g.n_reads = n_reads; g.nv = 2 * n_reads; g.n_arcs = (int)n_arcs;
+    g.at_reads = up16((size_t)n_arcs * sizeof(gact_graph_arc));
+    g.at_lens = g.at_reads + n * sizeof(gact_graph_read);
+    g.at_clip = up16(g.at_lens + n * sizeof(int32_t));
+    g.at_skip = up16(g.at_clip + (clip ? 2 * n * sizeof(int32_t) : 0));
+    g.end = up16(g.at_skip + (skip ? n * sizeof(int) : 0));
+    if (skip) g.wide.resize(n);
+    for (size_t i = 0; skip && i < n; i++) g.wide[i] = skip[i] != 0;
+    return g;
+}
+
+// the pass's scratch of `bytes`, its first event, and the copies in to the scratch's front, on the slot's stream
+extern "C++" template <class Stats>
+static int arc_graph_begin(ArcGraphDev &g, PassScratch<Stats> &ps, size_t bytes, hipStream_t stream, const char *who, const int32_t *read_lens,
+                           const int32_t *clip, const gact_graph_read *reads, const gact_graph_arc *arcs)
+{
+    const size_t n = (size_t)g.n_reads;
+    if (ps.reserve(bytes))
+        return fail(GACT_HIP_ENOMEM, "%s: device allocation failed (%d reads, %d arcs, %zu bytes)", who, g.n_reads, g.n_arcs, bytes);
+    if (int rc = ps.begin(stream, who)) return rc;
+    uint8_t *p = ps.p;
+    g.stream = stream;
+    g.arcs = (gact_graph_arc *)p;
+    g.reads = (const gact_graph_read *)(p + g.at_reads);
+    g.lens = (const int *)(p + g.at_lens);
+    g.clip = clip ? (const int *)(p + g.at_clip) : nullptr;
+    g.skip = g.wide.empty() ? nullptr : (const int *)(p + g.at_skip);
+    if (g.n_arcs) HIP_TRY(hipMemcpyAsync(p, arcs, (size_t)g.n_arcs * sizeof(gact_graph_arc), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(p + g.at_reads, reads, n * sizeof(gact_graph_read), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(p + g.at_lens, read_lens, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    if (clip) HIP_TRY(hipMemcpyAsync(p + g.at_clip, clip, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    if (g.skip) HIP_TRY(hipMemcpyAsync(p + g.at_skip, g.wide.data(), n * sizeof(int), hipMemcpyHostToDevice, stream));
+    return 0;
+}
+
+// the stretches and the arc checks: out gets the out-degrees over E0, counters[kUnitigE0] their number, *flag the refusals
+static void arc_graph_index(ArcGraphDev &g, int want_bases, int *first, int *out, unsigned long long *counters, int *flag)
+{
+    const dim3 block(gact::kPassBlock);
+    g.first = first;
+    g.flag = flag;
+    hipLaunchKernelGGL(gact::unitig_first_kernel, lane_blocks((size_t)g.nv + 1), block, 0, g.stream, g.nv, g.arcs, g.n_arcs, first);
+    hipLaunchKernelGGL(gact::unitig_check_kernel, lane_blocks((size_t)g.n_arcs), block, 0, g.stream, g.nv, g.arcs, g.n_arcs, first, g.reads,
+                       g.lens, g.clip, want_bases, out, counters, flag);
+}
+
+// what the flag word says, once it is on the host
+static int arc_graph_refusal(const char *who, int flag, int nv)
+{
+    if (flag & gact::kUnitigBadRange)
+        return fail(GACT_HIP_EINVAL, "%s: an arc with u or v outside [0, %d), between the two vertices of one read, or with len < 1", who, nv);
+    if (flag & gact::kUnitigBadOrder) return fail(GACT_HIP_EINVAL, "%s: the arcs are not ascending by (u, len, v)", who);
+    if (flag & gact::kUnitigNotLive)
+        return fail(GACT_HIP_EINVAL, "%s: an arc with flags == 0 names a read that is not live (contained, or clipped to nothing)", who);
+    if (flag & gact::kUnitigNoComplement)
+        return fail(GACT_HIP_EINVAL, "%s: an arc with flags == 0 whose complement v^1 -> u^1 is not among the arcs with flags == 0", who);
+    if (flag & gact::kUnitigLongArc)
+        return fail(GACT_HIP_EINVAL, "%s: bases asked for and an arc with flags == 0 is longer than the clipped read it leaves", who);
+    if (flag) return fail(GACT_HIP_EDEVICE, "%s: the device left the flag word %d", who, flag);
+    return 0;
+}
+
+// the wait of a call, or of a step of the rounds: its n counters and the flag word on the host -> what the flag word refuses
+static int arc_graph_fetch(const ArcGraphDev &g, const char *who, const unsigned long long *d_counters, unsigned long long *counters, size_t n)
+{
+    int flag = 0;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&flag, g.flag, sizeof flag, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(counters, d_counters, n * sizeof *counters, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return arc_graph_refusal(who, flag, g.nv);
+}
+
+// One ranking sweep over the arc set (cut == NULL: E0), as the unitig call makes three and the cleaning rounds one a tip step:
+// prev set to 0xff, the set's out-degrees counted into `out` where set_counters is given (else they are there), joins (counted
+// where join_counters is given), records, ceil(log2 nv) jumps; with `found`, the records of the sweep in front, the joins stay
+// and the cycles they found are opened.  *result: the buffer of rank[] that holds the result; *launches (NULL: not counted)
+// grows by the jumps
+struct UnitigRankBufs {
+    int *prev, *len_in, *len_out, *closing;                    // closing: NULL where no sweep opens cycles
+    gact::UnitigRank *rank[2];
+};
+static int unitig_sweep(const ArcGraphDev &g, const UnitigRankBufs &b, const int *cut, int *out, const gact::UnitigRank *found,
+                        unsigned long long *set_counters, unsigned long long *join_counters, const gact::UnitigRank **result, int *launches)
+{
+    const dim3 block(gact::kPassBlock);
+    const size_t nv = (size_t)g.nv, na = (size_t)g.n_arcs;
+    if (!found) {
+        HIP_TRY(hipMemsetAsync(b.prev, 0xff, nv * sizeof(int), g.stream));
+        if (set_counters)
+            hipLaunchKernelGGL(gact::unitig_recount_kernel, lane_blocks(na), block, 0, g.stream, g.arcs, g.n_arcs, cut, out, set_counters, g.flag);
+        hipLaunchKernelGGL(gact::unitig_links_kernel, lane_blocks(na), block, 0, g.stream, g.arcs, g.n_arcs, cut, out, b.prev, b.len_in,
+                           b.len_out, join_counters, g.flag);
+    }
+    int cur = found == b.rank[0] ? 1 : 0;                      // (the records of the sweep in front are read while these are made)
+    hipLaunchKernelGGL(gact::unitig_init_kernel, lane_blocks(nv), block, 0, g.stream, g.nv, b.prev, b.len_in, found, b.closing, b.rank[cur],
+                       g.flag);
+    int rounds = 1;
+    while (((size_t)1 << rounds) < nv) rounds++;
+    for (int r = 0; r < rounds; r++, cur ^= 1)
+        hipLaunchKernelGGL(gact::unitig_jump_kernel, lane_blocks(nv), block, 0, g.stream, g.nv, b.rank[cur], b.rank[cur ^ 1], g.flag);
+    *result = b.rank[cur];
+    if (launches) *launches += rounds;
+    return 0;
+}
+
+// One allocation: the graph (ArcGraphDev, no skip) |
 // [ out of E0, out of E1 (4 each per vertex) | counters (64) | totals (32) | flag (16) ], zeroed together |
 // first (4 (2 n_reads + 1)) | prev (4 per vertex, set to 0xff in front of each links kernel) | len_in, len_out, closing (4 each
 // per vertex) | cut (4 n_reads) | rank a, rank b (24 each per vertex) | number (4 per vertex) | layout_at, seq_at (8 each per
@@ -388,11 +530,7 @@ int gact_hip_unitigs(gact_hip_engine *e, int slot, int32_t n_reads, const int32_
     if (seq && !seq_len) return fail(GACT_HIP_EINVAL, "unitigs: seq without seq_len (NULL argument)");
     const gact_unitig_params p = params ? *params : gact_unitig_params{GACT_UNITIG_DEFAULT_TIP_READS};
     if (p.tip_reads < 0) return fail(GACT_HIP_EINVAL, "unitigs: bad parameter (tip_reads = %d: >= 0)", p.tip_reads);
-    if (n_reads < 0 || n_reads > gact::kUnitigMaxReads || n_arcs < 0 || n_arcs > gact::kUnitigMaxArcs || (n_arcs > 0 && !arcs) ||
-        (seq && seq_cap < 0))
-        return fail(GACT_HIP_EINVAL, "unitigs: bad arguments (n_reads = %d, at most %d; n_arcs = %lld, at most %lld; seq_cap = %lld)",
-                    n_reads, gact::kUnitigMaxReads, (long long)n_arcs, (long long)gact::kUnitigMaxArcs, (long long)seq_cap);
-    const int64_t clipped = check_read_lens("unitigs", n_reads, read_lens, clip);
+    const int64_t clipped = check_arc_graph("unitigs", n_reads, read_lens, clip, n_arcs, arcs, "seq_cap", seq_cap, seq && seq_cap < 0);
     if (clipped < 0) return GACT_HIP_EINVAL;
     const SeqSet &rs = e->sets[GACT_SET_REF];
     if (seq) {
@@ -412,11 +550,9 @@ int gact_hip_unitigs(gact_hip_engine *e, int slot, int32_t n_reads, const int32_
     if ((rc = set_device(e))) return rc;
     Slot &sl = e->slots[slot];
     PassScratch<gact_unitig_stats> &ub = sl.unitig;
+    ArcGraphDev g = arc_graph_layout(n_reads, clip, n_arcs, nullptr);
     const size_t n = (size_t)n_reads, nv = 2 * n, na = (size_t)n_arcs;
-    const size_t at_reads = up16(na * sizeof(gact_graph_arc));
-    const size_t at_lens = at_reads + n * sizeof(gact_graph_read);
-    const size_t at_clip = up16(at_lens + n * sizeof(int32_t));
-    const size_t at_out0 = up16(at_clip + (clip ? nv * sizeof(int32_t) : 0));
+    const size_t at_out0 = g.end;
     const size_t at_out1 = at_out0 + nv * sizeof(int);
     const size_t at_counters = up16(at_out1 + nv * sizeof(int));
     const size_t at_totals = at_counters + gact::kUnitigCounters * sizeof(unsigned long long);
@@ -437,85 +573,43 @@ int gact_hip_unitigs(gact_hip_engine *e, int slot, int32_t n_reads, const int32_
     const size_t at_places = at_layout + n * sizeof(gact_unitig_entry);
     const size_t at_seq = at_places + n * sizeof(gact_unitig_place);
     const size_t bytes = at_seq + (seq ? (size_t)clipped : 0);
-    if (ub.reserve(bytes))
-        return fail(GACT_HIP_ENOMEM, "unitigs: device allocation failed (%d reads, %lld arcs, %zu bytes)", n_reads, (long long)n_arcs, bytes);
-    gact_graph_arc *d_arcs = (gact_graph_arc *)ub.p;
-    gact_graph_read *d_reads = (gact_graph_read *)(ub.p + at_reads);
-    int *d_lens = (int *)(ub.p + at_lens);
-    const int *d_clip = clip ? (const int *)(ub.p + at_clip) : nullptr;
+    if ((rc = arc_graph_begin(g, ub, bytes, sl.stream, "unitigs", read_lens, clip, reads, arcs))) return rc;
     int *d_out0 = (int *)(ub.p + at_out0), *d_out1 = (int *)(ub.p + at_out1), *d_flag = (int *)(ub.p + at_flag);
     unsigned long long *d_counters = (unsigned long long *)(ub.p + at_counters);
     gact::UnitigTotals *d_totals = (gact::UnitigTotals *)(ub.p + at_totals);
-    int *d_first = (int *)(ub.p + at_first), *d_prev = (int *)(ub.p + at_prev), *d_len_in = (int *)(ub.p + at_len_in);
-    int *d_len_out = (int *)(ub.p + at_len_out), *d_closing = (int *)(ub.p + at_closing), *d_cut = (int *)(ub.p + at_cut);
-    gact::UnitigRank *d_rank[2] = {(gact::UnitigRank *)(ub.p + at_rank_a), (gact::UnitigRank *)(ub.p + at_rank_b)};
+    int *d_first = (int *)(ub.p + at_first), *d_cut = (int *)(ub.p + at_cut);
+    const UnitigRankBufs rb{(int *)(ub.p + at_prev), (int *)(ub.p + at_len_in), (int *)(ub.p + at_len_out), (int *)(ub.p + at_closing),
+                            {(gact::UnitigRank *)(ub.p + at_rank_a), (gact::UnitigRank *)(ub.p + at_rank_b)}};
     int *d_number = (int *)(ub.p + at_number);
     long long *d_layout_at = (long long *)(ub.p + at_layout_at), *d_seq_at = (long long *)(ub.p + at_seq_at);
     gact_unitig *d_unitigs = (gact_unitig *)(ub.p + at_unitigs);
     gact_unitig_entry *d_layout = (gact_unitig_entry *)(ub.p + at_layout);
     gact_unitig_place *d_places = (gact_unitig_place *)(ub.p + at_places);
     uint8_t *d_seq = ub.p + at_seq;
-    if ((rc = ub.begin(sl.stream, "unitigs"))) return rc;
-    if (na) HIP_TRY(hipMemcpyAsync(d_arcs, arcs, na * sizeof(gact_graph_arc), hipMemcpyHostToDevice, sl.stream));
-    HIP_TRY(hipMemcpyAsync(d_reads, reads, n * sizeof(gact_graph_read), hipMemcpyHostToDevice, sl.stream));
-    HIP_TRY(hipMemcpyAsync(d_lens, read_lens, n * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
-    if (clip) HIP_TRY(hipMemcpyAsync(ub.p + at_clip, clip, nv * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(hipMemsetAsync(d_out0, 0, at_first - at_out0, sl.stream));
     const dim3 block(gact::kPassBlock);
-    int rounds = 1;
-    while (((size_t)1 << rounds) < nv) rounds++;
-    const int n_a = (int)n_arcs, i_nv = (int)nv;
     int launches = 0;
-    // one sweep over the arc set (cut == NULL: E0): joins, records, `rounds` jumps; -> the buffer that holds the result
-    auto sweep = [&](const int *cut, const int *out, const gact::UnitigRank *found, bool count) -> gact::UnitigRank * {
-        if (!found) {
-            (void)hipMemsetAsync(d_prev, 0xff, nv * sizeof(int), sl.stream);
-            hipLaunchKernelGGL(gact::unitig_links_kernel, lane_blocks(na), block, 0, sl.stream, d_arcs, n_a, cut, out, d_prev, d_len_in, d_len_out,
-                               count ? d_counters : nullptr, d_flag);
-        }
-        const int at = found == d_rank[0] ? 1 : 0;             // (the records of the sweep in front are read while these are made)
-        hipLaunchKernelGGL(gact::unitig_init_kernel, lane_blocks(nv), block, 0, sl.stream, i_nv, d_prev, d_len_in, found, d_closing, d_rank[at],
-                           d_flag);
-        int cur = at;
-        for (int r = 0; r < rounds; r++, cur ^= 1, launches++)
-            hipLaunchKernelGGL(gact::unitig_jump_kernel, lane_blocks(nv), block, 0, sl.stream, i_nv, d_rank[cur], d_rank[cur ^ 1], d_flag);
-        return d_rank[cur];
-    };
-    hipLaunchKernelGGL(gact::unitig_first_kernel, lane_blocks(nv + 1), block, 0, sl.stream, i_nv, d_arcs, n_a, d_first);
-    hipLaunchKernelGGL(gact::unitig_check_kernel, lane_blocks(na), block, 0, sl.stream, i_nv, d_arcs, n_a, d_first, d_reads, d_lens, d_clip,
-                       seq ? 1 : 0, d_out0, d_counters, d_flag);
-    const gact::UnitigRank *on_e0 = sweep(nullptr, d_out0, nullptr, false);
-    hipLaunchKernelGGL(gact::unitig_tip_kernel, lane_blocks(n), block, 0, sl.stream, n_reads, d_reads, d_lens, d_clip, d_prev, d_out0, on_e0,
+    // three sweeps: on E0 for the tip rule, on E1 to find the cycles and their lowest ids, and on E1 with the cycles opened
+    const gact::UnitigRank *on_e0, *cycles, *ranks;
+    arc_graph_index(g, seq ? 1 : 0, d_first, d_out0, d_counters, d_flag);
+    if ((rc = unitig_sweep(g, rb, nullptr, d_out0, nullptr, nullptr, nullptr, &on_e0, &launches))) return rc;
+    hipLaunchKernelGGL(gact::unitig_tip_kernel, lane_blocks(n), block, 0, sl.stream, n_reads, g.reads, g.lens, g.clip, rb.prev, d_out0, on_e0,
                        p.tip_reads, d_cut, d_counters, d_flag);
-    hipLaunchKernelGGL(gact::unitig_recount_kernel, lane_blocks(na), block, 0, sl.stream, d_arcs, n_a, d_cut, d_out1, d_counters, d_flag);
-    const gact::UnitigRank *cycles = sweep(d_cut, d_out1, nullptr, true);
-    const gact::UnitigRank *ranks = sweep(d_cut, d_out1, cycles, false);
-    hipLaunchKernelGGL(gact::unitig_heads_kernel, lane_blocks(nv), block, 0, sl.stream, i_nv, d_reads, d_lens, d_clip, d_cut, ranks, d_closing,
+    if ((rc = unitig_sweep(g, rb, d_cut, d_out1, nullptr, d_counters, d_counters, &cycles, &launches))) return rc;
+    if ((rc = unitig_sweep(g, rb, d_cut, d_out1, cycles, nullptr, nullptr, &ranks, &launches))) return rc;
+    hipLaunchKernelGGL(gact::unitig_heads_kernel, lane_blocks(nv), block, 0, sl.stream, g.nv, g.reads, g.lens, g.clip, d_cut, ranks, rb.closing,
                        d_number, d_layout_at, d_seq_at, d_counters, d_flag);
-    hipLaunchKernelGGL(gact::unitig_scan_kernel, dim3(1), block, 0, sl.stream, i_nv, d_number, d_layout_at, d_seq_at, d_totals, d_flag);
-    hipLaunchKernelGGL(gact::unitig_fill_kernel, lane_blocks(nv), block, 0, sl.stream, i_nv, d_reads, d_lens, d_clip, d_cut, ranks, d_closing,
-                       d_len_out, d_number, d_layout_at, d_seq_at, d_unitigs, d_layout, d_places, d_flag);
+    hipLaunchKernelGGL(gact::unitig_scan_kernel, dim3(1), block, 0, sl.stream, g.nv, d_number, d_layout_at, d_seq_at, d_totals, d_flag);
+    hipLaunchKernelGGL(gact::unitig_fill_kernel, lane_blocks(nv), block, 0, sl.stream, g.nv, g.reads, g.lens, g.clip, d_cut, ranks, rb.closing,
+                       rb.len_out, d_number, d_layout_at, d_seq_at, d_unitigs, d_layout, d_places, d_flag);
     if (seq)
         hipLaunchKernelGGL(gact::unitig_bases_kernel, wave_blocks(e, n), block, 0, sl.stream, d_totals, d_layout, d_places, d_unitigs,
-                           rs.d_raw, rs.d_offsets, d_lens, d_clip, d_seq, d_flag);
-    HIP_TRY(hipGetLastError());
+                           rs.d_raw, rs.d_offsets, g.lens, g.clip, d_seq, d_flag);
     // the one wait: the flag word, the number of unitigs and the total length, before the copies out
-    int flag = 0;
     gact::UnitigTotals totals{};
     unsigned long long counters[gact::kUnitigCounters];
-    HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, sl.stream));
     HIP_TRY(hipMemcpyAsync(&totals, d_totals, sizeof totals, hipMemcpyDeviceToHost, sl.stream));
-    HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost, sl.stream));
-    HIP_TRY(hipStreamSynchronize(sl.stream));
-    if (flag & gact::kUnitigBadRange)
-        return fail(GACT_HIP_EINVAL, "unitigs: an arc with u or v outside [0, %zu), between the two vertices of one read, or with len < 1", nv);
-    if (flag & gact::kUnitigBadOrder) return fail(GACT_HIP_EINVAL, "unitigs: the arcs are not ascending by (u, len, v)");
-    if (flag & gact::kUnitigNotLive)
-        return fail(GACT_HIP_EINVAL, "unitigs: an arc with flags == 0 names a read that is not live (contained, or clipped to nothing)");
-    if (flag & gact::kUnitigNoComplement)
-        return fail(GACT_HIP_EINVAL, "unitigs: an arc with flags == 0 whose complement v^1 -> u^1 is not among the arcs with flags == 0");
-    if (flag & gact::kUnitigLongArc)
-        return fail(GACT_HIP_EINVAL, "unitigs: bases asked for and an arc with flags == 0 is longer than the clipped read it leaves");
+    if ((rc = arc_graph_fetch(g, "unitigs", d_counters, counters, gact::kUnitigCounters))) return rc;
     if (totals.unitigs < 0 || totals.unitigs > n_reads || totals.placed < totals.unitigs || totals.placed > n_reads ||
         totals.length < 0 || (seq && totals.length > clipped))
         return fail(GACT_HIP_EDEVICE, "unitigs: the device counted %lld unitigs of %lld reads and %lld bases", totals.unitigs,
@@ -556,3 +650,4 @@ int gact_hip_last_unitig_stats(gact_hip_engine *e, int slot, gact_unitig_stats *
 {
     return last_pass_stats(e, slot, &Slot::unitig, stats, "last_unitig_stats", "has made no unitigs yet");
 }
+

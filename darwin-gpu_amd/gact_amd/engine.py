@@ -909,13 +909,8 @@ class Engine:
         per class (a list of 8), arcs proposed, arcs, transitive arcs, kept arcs, table slots, device bytes the call holds"""
         return self._stats(self.L.gact_hip_last_graph_stats, GraphStats, slot)
 
-    def unitigs(self, read_lens, reads, arcs, clip=None, tip_reads=UNITIG_DEFAULT_TIP_READS, seq=False, slot=0):
-        """the unitigs of an overlap graph, made on the device: (unitigs, layout, places) -- UNITIG_DTYPE records ascending by
-        their first vertex, the UNITIG_ENTRY_DTYPE entries of their layouts one unitig after the other, and one
-        UNITIG_PLACE_DTYPE record per read -- or (unitigs, layout, places, bases) with the unitigs' bases as bytes, spelled
-        from the reads of SET_REF, when `seq` is set.  read_lens and clip as overlap_graph took them, reads and arcs as it
-        returned them; tip_reads: dead ends of at most that many reads are cut, 0 cuts nothing
-        (include/gact_hip.h gact_hip_unitigs)"""
+    def _graph_args(self, read_lens, reads, arcs, clip, skip=None):
+        """the arrays of a call on an overlap graph, as the C-ABI takes them"""
         read_lens = np.ascontiguousarray(read_lens, dtype=np.int32)
         reads = np.ascontiguousarray(reads, dtype=GRAPH_READ_DTYPE)
         arcs = np.ascontiguousarray(arcs, dtype=GRAPH_ARC_DTYPE)
@@ -924,21 +919,43 @@ class Engine:
         if clip is not None:
             clip = np.ascontiguousarray(clip, dtype=np.int32).reshape(-1)
             assert len(clip) == 2 * n
+        if skip is not None:
+            skip = np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8)
+            assert len(skip) == n
+        return read_lens, reads, arcs, clip, skip, n
+
+    def _with_room(self, cap, call):
+        """call(cap) -> (rc, the count the call filled in, the array of cap records): made once, and where it came back EINVAL
+        with a count beyond cap once more with room for that many; -> the array of the call that counts"""
+        rc, need, out = call(cap)
+        if rc != 0 and need > cap:
+            rc, need, out = call(need)
+        self._check(rc)
+        return out
+
+    def unitigs(self, read_lens, reads, arcs, clip=None, tip_reads=UNITIG_DEFAULT_TIP_READS, seq=False, slot=0):
+        """the unitigs of an overlap graph, made on the device: (unitigs, layout, places) -- UNITIG_DTYPE records ascending by
+        their first vertex, the UNITIG_ENTRY_DTYPE entries of their layouts one unitig after the other, and one
+        UNITIG_PLACE_DTYPE record per read -- or (unitigs, layout, places, bases) with the unitigs' bases as bytes, spelled
+        from the reads of SET_REF, when `seq` is set.  read_lens and clip as overlap_graph took them, reads and arcs as it
+        returned them; tip_reads: dead ends of at most that many reads are cut, 0 cuts nothing
+        (include/gact_hip.h gact_hip_unitigs)"""
+        read_lens, reads, arcs, clip, _, n = self._graph_args(read_lens, reads, arcs, clip)
         params = UnitigParams(int(tip_reads))
         unitigs = np.zeros(n, dtype=UNITIG_DTYPE)
         layout = np.zeros(n, dtype=UNITIG_ENTRY_DTYPE)
         places = np.zeros(n, dtype=UNITIG_PLACE_DTYPE)
         n_unitigs, seq_len = C.c_int32(), C.c_int64()
-        cap = int(read_lens.astype(np.int64).sum()) // 2 if seq else 0    # (most sets need far less than their reads' bases)
-        for attempt in range(2):
+
+        def call(cap):
             bases = np.zeros(cap, dtype=np.uint8) if seq else None
             rc = self.L.gact_hip_unitigs(self.h, slot, n, _ptr(read_lens), _ptr(clip), _ptr(reads), len(arcs), _ptr(arcs),
                                          C.byref(params), _ptr(unitigs), C.byref(n_unitigs), _ptr(layout), _ptr(places),
                                          _ptr(bases), cap, C.byref(seq_len))
-            if rc == 0 or attempt or not seq or seq_len.value <= cap:
-                break
-            cap = seq_len.value                     # (EINVAL with *seq_len filled: once more with room for the bases)
-        self._check(rc)
+            return rc, seq_len.value if seq else 0, bases
+
+        # (most sets need far less than their reads' bases)
+        bases = self._with_room(int(read_lens.astype(np.int64).sum()) // 2 if seq else 0, call)
         unitigs = unitigs[:n_unitigs.value].copy()
         layout = layout[:int(unitigs["n_reads"].sum())].copy()
         return (unitigs, layout, places, bases[:seq_len.value].tobytes()) if seq else (unitigs, layout, places)
@@ -957,31 +974,20 @@ class Engine:
         read_lens, clip, reads and arcs as unitigs takes them; skip: None, or one value per read, != 0 takes the read's arcs
         out of the working set (the tips of an earlier unitigs call, places["state"] == UNITIG_TIP)
         (include/gact_hip.h gact_hip_pop_bubbles)"""
-        read_lens = np.ascontiguousarray(read_lens, dtype=np.int32)
-        reads = np.ascontiguousarray(reads, dtype=GRAPH_READ_DTYPE)
-        arcs = np.ascontiguousarray(arcs, dtype=GRAPH_ARC_DTYPE)
-        n = len(read_lens)
-        assert len(reads) == n
-        if clip is not None:
-            clip = np.ascontiguousarray(clip, dtype=np.int32).reshape(-1)
-            assert len(clip) == 2 * n
-        if skip is not None:
-            skip = np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8)
-            assert len(skip) == n
+        read_lens, reads, arcs, clip, skip, n = self._graph_args(read_lens, reads, arcs, clip, skip)
         params = BubbleParams(int(max_dist), int(max_vertices))
         read_bubble = np.zeros(n, dtype=np.int32)
         arc_flags = np.zeros(len(arcs), dtype=np.int32)
         n_bubbles = C.c_int64()
-        cap = 64                                    # (a bubble per hundred reads is many)
-        for attempt in range(2):
+
+        def call(cap):
             bubbles = np.zeros(cap, dtype=BUBBLE_DTYPE)
             rc = self.L.gact_hip_pop_bubbles(self.h, slot, n, _ptr(read_lens), _ptr(clip), _ptr(reads), len(arcs), _ptr(arcs),
                                              _ptr(skip), C.byref(params), _ptr(bubbles), cap, C.byref(n_bubbles),
                                              _ptr(read_bubble), _ptr(arc_flags))
-            if rc == 0 or attempt or n_bubbles.value <= cap:
-                break
-            cap = n_bubbles.value                   # (EINVAL with *n_bubbles filled: once more with room for them)
-        self._check(rc)
+            return rc, n_bubbles.value, bubbles
+
+        bubbles = self._with_room(64, call)         # (a bubble per hundred reads is many)
         return bubbles[:n_bubbles.value].copy(), read_bubble, arc_flags
 
     def last_bubble_stats(self, slot=0):
@@ -989,21 +995,6 @@ class Engine:
         found, popped and lost, reads removed, arcs of the working set, arcs removed, the failed searches by their first
         failure (a list of 5: open, dead, twice, dist, many), device bytes the call holds"""
         return self._stats(self.L.gact_hip_last_bubble_stats, BubbleStats, slot)
-
-    def _graph_args(self, read_lens, reads, arcs, clip, skip=None):
-        """the arrays of a call on an overlap graph, as the C-ABI takes them"""
-        read_lens = np.ascontiguousarray(read_lens, dtype=np.int32)
-        reads = np.ascontiguousarray(reads, dtype=GRAPH_READ_DTYPE)
-        arcs = np.ascontiguousarray(arcs, dtype=GRAPH_ARC_DTYPE)
-        n = len(read_lens)
-        assert len(reads) == n
-        if clip is not None:
-            clip = np.ascontiguousarray(clip, dtype=np.int32).reshape(-1)
-            assert len(clip) == 2 * n
-        if skip is not None:
-            skip = np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8)
-            assert len(skip) == n
-        return read_lens, reads, arcs, clip, skip, n
 
     def prune_overlaps(self, read_lens, reads, arcs, clip=None, skip=None, ratio_permille=PRUNE_DEFAULT_RATIO_PERMILLE, best=False,
                        slot=0):
@@ -1037,15 +1028,14 @@ class Engine:
         arc_flags = np.zeros(len(arcs), dtype=np.int32)
         read_state = np.zeros(n, dtype=CLEAN_READ_DTYPE)
         n_steps = C.c_int64()
-        cap = 16                                    # (a graph that settles at once takes 2 + 3 steps)
-        for attempt in range(2):
+
+        def call(cap):
             steps = np.zeros(cap, dtype=CLEAN_STEP_DTYPE)
             rc = self.L.gact_hip_clean_graph(self.h, slot, n, _ptr(read_lens), _ptr(clip), _ptr(reads), len(arcs), _ptr(arcs),
                                              C.byref(params), _ptr(arc_flags), _ptr(read_state), _ptr(steps), cap, C.byref(n_steps))
-            if rc == 0 or attempt or n_steps.value <= cap:
-                break
-            cap = n_steps.value                     # (EINVAL with *n_steps filled: once more with room for them)
-        self._check(rc)
+            return rc, n_steps.value, steps
+
+        steps = self._with_room(16, call)           # (a graph that settles at once takes 2 + 3 steps)
         return arc_flags, read_state, steps[:n_steps.value].copy()
 
     def last_clean_stats(self, slot=0):

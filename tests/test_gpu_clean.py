@@ -1,8 +1,9 @@
 """GPU suite for the weak-arc rule and the cleaning rounds (gact_hip_prune_overlaps, gact_hip_clean_graph, csrc/gact_clean.hpp):
 arc_flags, vertex_best, read_state, the step log and the statistics' counts equal the model's (tests/clean_model.py) byte for
 byte -- on every hand-made case, at the ratios' ends, on generated graphs with and without repeats and with and without the
-tips skipped, three times over on two slots, through the steps_cap protocol and the refusals, composed with the unitig call, and
-through the driver's --clean.  No tolerance: everything is integer."""
+tips skipped, three times over on two slots, through the steps_cap protocol and the refusals, composed with the unitig call, against the
+same rounds made from the stand-alone calls, in the one wording the four calls on an arc graph share for a fault, and through the
+driver's --clean.  No tolerance: everything is integer."""
 import ctypes as C
 import os
 import subprocess
@@ -383,6 +384,150 @@ def test_clean_refusals(eng):
     assert call(lens=lens[:0], reads=reads[:0], arcs=arcs[:0], n_reads=0) == (0, 0) and (arc_flags == -7).all()
     got = eng.clean_graph(lens[:0], reads[:0], arcs[:0])
     assert [len(a) for a in got] == [0, 0, 0]
+
+
+# ---- the loop is the stand-alone calls' steps; the four calls on an arc graph refuse in one wording
+
+def _rounds_of_the_calls(eng, lens, reads, arcs, clip, tip_reads=3, max_dist=50000, max_vertices=64, ratios=(500, 700, 3), max_passes=4):
+    """the rounds made on the host out of the device's stand-alone calls, the way clean_model.clean composes the models:
+    -> (arc_flags, read_state, steps) as clean_graph returns them"""
+    from gact_amd import engine
+    n = len(lens)
+    work = arcs.copy()                                # (flags: F)
+    touches = list(zip((arcs["u"] >> 1).tolist(), (arcs["v"] >> 1).tolist()))
+    state, step_of, steps = [], [-1] * n, []
+
+    def log(kind, param, removed_reads, examined, new_flags):
+        had, left = int((work["flags"] == 0).sum()), int((new_flags == 0).sum())
+        for i in removed_reads:
+            state[i], step_of[i] = (clean_model.TIP if kind == clean_model.TIPS else clean_model.BUBBLE), len(steps)
+        steps.append((kind, param, len(removed_reads), examined, had - left, left))
+        work["flags"] = new_flags
+        return had - left
+
+    def tips():
+        places = eng.unitigs(lens, reads, work, clip=clip, tip_reads=tip_reads)[2]
+        if not state:                                 # (the first call says which reads are contained or empty)
+            own = {unitig_model.CONTAINED: clean_model.CONTAINED, unitig_model.EMPTY: clean_model.EMPTY}
+            state.extend(own.get(s, clean_model.KEPT) for s in places["state"].tolist())
+        cut = (places["state"] == unitig_model.TIP).tolist()
+        f = work["flags"].copy()
+        for k, (a, b) in enumerate(touches):
+            if f[k] == 0 and (cut[a] or cut[b]):
+                f[k] = clean_model.TIP_BIT
+        newly = [i for i in range(n) if cut[i] and state[i] == clean_model.KEPT]
+        return log(clean_model.TIPS, tip_reads, newly, clean_model._tip_chains(lens, reads, work, clip), f)
+
+    def bubbles():
+        _, read_bubble, arc_flags = eng.pop_bubbles(lens, reads, work, clip=clip, max_dist=max_dist, max_vertices=max_vertices)
+        return log(clean_model.BUBBLES, max_dist, np.flatnonzero(read_bubble >= 0).tolist(), eng.last_bubble_stats()["sources"], arc_flags)
+
+    def settle():
+        for _ in range(max_passes):
+            if tips() + bubbles() == 0:
+                break
+
+    settle()
+    for r in clean_model.ratios_of(*ratios):
+        arc_flags = eng.prune_overlaps(lens, reads, work, clip=clip, ratio_permille=r)
+        if log(clean_model.PRUNE, r, [], eng.last_prune_stats()["examined"], arc_flags):
+            settle()
+    read_state = np.zeros(n, dtype=engine.CLEAN_READ_DTYPE)
+    read_state["state"], read_state["step"] = state, step_of
+    return work["flags"].astype(np.int32), read_state, np.array(steps, dtype=engine.CLEAN_STEP_DTYPE).reshape(-1)
+
+
+@pytest.mark.parametrize("plan", [dict(), dict(ratios=(500, 700, 0), max_passes=1), dict(ratios=(600, 600, 1))], ids=str)
+@pytest.mark.parametrize("name", ["false_fork", "nested_in", "simple", "repeat300_1"])
+def test_the_loop_is_its_steps(eng, name, plan):
+    """clean_graph launches the step sequences of the unitig, bubble and prune calls on resident arcs: the same calls made one
+    by one from the host, each on the flags the one in front left, end with the same bytes"""
+    lens, reads, arcs, clip = _graph_of(name)[:4]
+    want = _rounds_of_the_calls(eng, lens, reads, arcs, clip, **plan)
+    got = eng.clean_graph(lens, reads, arcs, clip=clip, **plan)
+    _same(got, dict(zip(("arc_flags", "read_state", "steps"), want)), ("arc_flags", "read_state", "steps"), (name, plan))
+    kinds = got[2]["kind"].tolist()
+    assert kinds[:2] == [clean_model.TIPS, clean_model.BUBBLES] and kinds.count(clean_model.PRUNE) == plan.get("ratios", (0, 0, 3))[2]
+    # behind a prune that removed an arc the loop settles again, as the helper does; in false_fork one does, and makes new tips
+    dropped = [j for j, k in enumerate(kinds) if k == clean_model.PRUNE and got[2]["arcs_removed"][j] > 0]
+    assert all(kinds[j + 1] == clean_model.TIPS for j in dropped)
+    if name == "false_fork" and not plan:
+        assert dropped
+    if name == "repeat300_1" and not plan:
+        assert eng.last_clean_stats()["passes"] >= 2
+
+
+def _raw_unitigs(eng, lens, reads, arcs, clip=None, slot=0, n_reads=None, n_arcs=None, utg=None, layout=None, places=None, seq=None):
+    from gact_amd import engine
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    par = engine.UnitigParams(3)
+    count, seq_len = C.c_int32(-9), C.c_int64(-9)
+    rc = eng.L.gact_hip_unitigs(eng.h, slot, len(lens) if n_reads is None else n_reads, ptr(lens), ptr(clip), ptr(reads),
+                                len(arcs) if n_arcs is None else n_arcs, ptr(arcs), C.byref(par), ptr(utg), C.byref(count), ptr(layout),
+                                ptr(places), ptr(seq), len(seq) if seq is not None else 0, C.byref(seq_len))
+    return rc, count.value, seq_len.value
+
+
+def test_one_wording_for_one_fault(eng):
+    """the four calls on an arc graph refuse the same input with the same sentence behind their own names; an input wrong in two
+    ways gets the sentence of the first check from all four; a refused call writes nothing"""
+    from gact_amd import engine
+    from test_gpu_bubbles import _raw_call as _raw_bubbles
+    lens, reads, arcs, clip = _graph_of("false_fork")[:4]
+    n = len(lens)
+    out = dict(utg=np.full(n, -5, dtype=engine.UNITIG_DTYPE), layout=np.full(n, -5, dtype=engine.UNITIG_ENTRY_DTYPE),
+               places=np.full(n, -5, dtype=engine.UNITIG_PLACE_DTYPE), bubbles=np.full(8, -5, dtype=engine.BUBBLE_DTYPE),
+               read_bubble=np.full(n, -7, dtype=np.int32), arc_flags=np.full(len(arcs), -7, dtype=np.int32),
+               best=np.full(2 * n, -7, dtype=np.int32), read_state=np.full(n, -7, dtype=engine.CLEAN_READ_DTYPE),
+               steps=np.full(64, -5, dtype=engine.CLEAN_STEP_DTYPE), seq=np.full(int(lens.sum()), 7, dtype=np.uint8))
+    held = {k: a.tobytes() for k, a in out.items()}
+    entries = {
+        "unitigs": (_raw_unitigs, dict(utg=out["utg"], layout=out["layout"], places=out["places"])),
+        "pop_bubbles": (_raw_bubbles, dict(bubbles=out["bubbles"], cap=8, read_bubble=out["read_bubble"], arc_flags=out["arc_flags"])),
+        "prune_overlaps": (_raw_prune, dict(arc_flags=out["arc_flags"], best=out["best"])),
+        "clean_graph": (_raw_clean, dict(arc_flags=out["arc_flags"], read_state=out["read_state"], steps=out["steps"], cap=64))}
+
+    def refused(who, **over):
+        """the call of entry `who` on the graph with `over` laid over it -> the sentence behind the entry's name"""
+        fn, kw = entries[who]
+        kw = dict(dict(lens=lens, reads=reads, arcs=arcs, n_reads=n), **kw)
+        kw.update(over)
+        if who == "unitigs" and "arc_flags" in over:                    # (the unitig call has no arc_flags: its places)
+            kw["places"] = kw.pop("arc_flags")
+        res = fn(eng, kw.pop("lens"), kw.pop("reads"), kw.pop("arcs"), **kw)
+        assert (res if isinstance(res, int) else res[0]) == -1, (who, over)
+        assert isinstance(res, int) or all(v == -9 for v in res[1:]), (who, over, res)
+        said = eng.L.gact_hip_last_error().decode()
+        assert said.startswith(who + ": "), (who, over, said)
+        return said[len(who) + 2:]
+
+    tails = {b"outside": "an arc with u or v outside [0, %d), between the two vertices of one read, or with len < 1" % (2 * n),
+             b"ascending": "the arcs are not ascending by (u, len, v)",
+             b"not live": "an arc with flags == 0 names a read that is not live (contained, or clipped to nothing)",
+             b"complement": "an arc with flags == 0 whose complement v^1 -> u^1 is not among the arcs with flags == 0",
+             b"negative": "read 1 has the negative length -1",
+             b"clip": "the clip [3000, 2999) of read 2 is not inside [0, %d]" % lens[2]}
+    seen = set()
+    for bad, word in _bad_inputs(lens, reads, arcs):
+        for who in entries:
+            tail = refused(who, **bad)
+            assert word.decode() in tail, (who, bad, tail)
+            if word in tails:
+                assert tail == tails[word], (who, bad, tail)
+                seen.add(word)
+    assert seen == set(tails)
+    # wrong in two ways: the arcs reversed, and the one arc the order check passes -- the first -- leaves a contained read
+    contained = reads.copy()
+    contained["contained_by"][int(arcs["u"][-1]) >> 1] = 3
+    for who in entries:
+        assert refused(who, arcs=arcs[::-1].copy(), reads=contained) == tails[b"ascending"], who
+    # bases asked for, and an arc longer than its clipped read: the unitig call's own sentence, in front of the fallback
+    eng.upload_seqs(engine.SET_REF, [np.full(int(ln), ord("A"), dtype=np.uint8) for ln in lens])
+    long_arc = arcs.copy()
+    assert long_arc["flags"][-1] == 0
+    long_arc["len"][-1] = int(lens[int(arcs["u"][-1]) >> 1]) + 1
+    assert refused("unitigs", arcs=long_arc, seq=out["seq"]) == "bases asked for and an arc with flags == 0 is longer than the clipped read it leaves"
+    assert {k: a.tobytes() for k, a in out.items()} == held
 
 
 # ---- the driver
