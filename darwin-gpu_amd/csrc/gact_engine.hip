@@ -325,6 +325,8 @@ struct Slot {
     PassScratch<gact_clean_stats> clean;
     // gact_hip_place_reads (gact_place.hpp): host records | sel | sums | lens | first | fill | flag, counters | reads | items | CSR | ranked | place | spans
     PassScratch<gact_place_stats> place;
+    // gact_hip_filter_overlaps (gact_filter.hpp): host records | sel | sums | ident, why | flags | counts | counters, total, flag | table | kept_at | kept_sel
+    PassScratch<gact_filter_stats> filter;
     // gact_hip_pileup_add (gact_pileup.hpp): the events around this slot's adds; the counts are the engine's (Pileup)
     PassTimer pile_timer;
 
@@ -345,6 +347,7 @@ struct Slot {
         prune.release();
         clean.release();
         place.release();
+        filter.release();
         pile_timer.release();
         if (d_counter) (void)hipFree(d_counter);
         if (d_flags) (void)hipFree(d_flags);
@@ -1960,6 +1963,7 @@ int gact_hip_measure_valu_rate(gact_hip_engine *e, double *lane_ops_per_s)
 #include "gact_path_run.hpp"     // gact_hip_candidates_paths / _summaries: the alignments again, as CIGARs or as counts
 #include "gact_select.hpp"       // gact_hip_select_overlaps: one overlap per class, behind every other kernel
 #include "gact_cover.hpp"        // gact_hip_read_coverage: per-read coverage of an overlap set, behind those
+#include "gact_filter.hpp"       // gact_hip_filter_overlaps: the overlap set by identity, span and each read's best, ahead of the passes below
 #include "gact_graph.hpp"        // gact_hip_overlap_graph: containment, dovetail arcs and their transitive flags, behind those
 #include "gact_pileup.hpp"       // gact_hip_pileup_*: per-base pileup and consensus from the alignments' columns
 #include "gact_variants.hpp"     // gact_hip_pileup_variants: INS, DEL and SNV records from the pileup's counts, one wave per chunk of positions

@@ -1,7 +1,8 @@
 // What the passes behind an alignment run share on the host (included by gact_engine.hip; host code only, no kernel).
 //
 // A pass runs on a slot's stream behind the slot's last run: CIGAR paths and summaries (gact_path_run.hpp), selection
-// (gact_select.hpp), coverage (gact_cover.hpp), the overlap graph (gact_graph.hpp), its unitigs (gact_unitig.hpp), its bubbles
+// (gact_select.hpp), the filter by identity, span and each read's best (gact_filter.hpp), coverage (gact_cover.hpp), the
+// overlap graph (gact_graph.hpp), its unitigs (gact_unitig.hpp), its bubbles
 // (gact_bubble.hpp), its weak arcs and cleaning rounds (gact_clean.hpp), the placement of reads (gact_place.hpp), the pileup (gact_pileup.hpp) and its variants (gact_variants.hpp).  A new pass starts here.  It takes a PassScratch<its stats> in Slot (gact_engine.hip, beside DevBuf: Slot holds them by value, so
 // the two records are defined in front of it), and its entry point reads:
 //

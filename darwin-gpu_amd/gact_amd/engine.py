@@ -180,6 +180,25 @@ class CoverStats(C.Structure):
                 ("scratch_bytes", C.c_int64)]
 
 
+class FilterParams(C.Structure):
+    """the defaults are GACT_FILTER_DEFAULT_*"""
+    _fields_ = [("min_identity_permille", C.c_int32), ("min_span", C.c_int32), ("max_drop_permille", C.c_int32)]
+
+
+class FilterStats(C.Structure):
+    _fields_ = [("device_ms", C.c_float), ("reads", C.c_int32)] + \
+               [(n, C.c_int64) for n in ("chosen", "counted", "kept", "not_emitted", "empty", "identity", "span", "relative",
+                                         "scratch_bytes")]
+
+
+# the filter of an overlap set (include/gact_hip.h gact_hip_filter_overlaps): one record per read of the window; why per record
+FILTER_READ_DTYPE = np.dtype([(n, "<i4") for n in ("n_records", "n_passed", "n_kept", "best_permille")] +
+                             [("eq_sum", "<i8"), ("col_sum", "<i8")])
+assert FILTER_READ_DTYPE.itemsize == 32 and C.sizeof(FilterParams) == 12
+FILTER_KEPT, FILTER_NOT_EMITTED, FILTER_EMPTY, FILTER_IDENTITY, FILTER_SPAN, FILTER_RELATIVE = range(6)
+FILTER_DEFAULTS = {"min_identity": 650, "min_span": 0, "max_drop": 1000}
+
+
 class PlaceParams(C.Structure):
     """the defaults are GACT_PLACE_DEFAULT_*"""
     _fields_ = [("mask_permille", C.c_int32), ("mapq_cap", C.c_int32)]
@@ -449,6 +468,14 @@ def load():
     except AttributeError:
         pass
     try:
+        L.gact_hip_filter_overlaps.argtypes = [vp, C.c_int, i32, vp, i32, vp, vp, i32, i32, i32, C.POINTER(FilterParams), vp, vp, vp, i32,
+                                               C.POINTER(i32), vp]
+        L.gact_hip_filter_overlaps.restype = C.c_int
+        L.gact_hip_last_filter_stats.argtypes = [vp, C.c_int, C.POINTER(FilterStats)]
+        L.gact_hip_last_filter_stats.restype = C.c_int
+    except AttributeError:
+        pass
+    try:
         L.gact_hip_place_reads.argtypes = [vp, C.c_int, i32, vp, i32, vp, vp, i32, i32, vp, C.POINTER(PlaceParams), vp, vp]
         L.gact_hip_place_reads.restype = C.c_int
         L.gact_hip_last_place_stats.argtypes = [vp, C.c_int, C.POINTER(PlaceStats)]
@@ -558,7 +585,8 @@ EXPORTS = ("gact_hip_create", "gact_hip_destroy", "gact_hip_last_error", "gact_h
            "gact_hip_pileup_begin", "gact_hip_pileup_add", "gact_hip_pileup_finish", "gact_hip_last_pileup_stats",
            "gact_hip_pileup_begin_ins", "gact_hip_pileup_corrected", "gact_hip_last_pileup_ins_stats",
            "gact_hip_place_reads", "gact_hip_last_place_stats", "gact_hip_format_sam", "gact_hip_format_sam_unmapped",
-           "gact_hip_pileup_variants", "gact_hip_last_variant_stats", "gact_hip_format_vcf")
+           "gact_hip_pileup_variants", "gact_hip_last_variant_stats", "gact_hip_format_vcf",
+           "gact_hip_filter_overlaps", "gact_hip_last_filter_stats")
 
 
 def plan(count, flags=0, compute_units=256, tile_size=320, tile_overlap=120, scoring=(1, -1, -1, -1), threshold=35):
@@ -834,6 +862,58 @@ class Engine:
         """the slot's last coverage call: device ms (HIP events around the whole call), reads, intervals counted, positions,
         device bytes the call holds for itself"""
         return self._stats(self.L.gact_hip_last_cover_stats, CoverStats, slot)
+
+    def filter_overlaps(self, sums, n=None, records=None, sel=None, min_identity=FILTER_DEFAULTS["min_identity"],
+                        min_span=FILTER_DEFAULTS["min_span"], max_drop=FILTER_DEFAULTS["max_drop"], sides="both",
+                        read_lens_or_n_reads=None, read_first=0, table=False, why=False, slot=0):
+        """the overlap set filtered on the device by identity, span and each read's best: (sel2, sums2) -- the kept record
+        indices, ascending in their position in the chosen list, and their summaries, to be passed on as `sel` and `sums` --
+        followed by the FILTER_READ_DTYPE table of the window's reads when `table` is set and by the int32 reason of every
+        chosen record (FILTER_*) when `why` is set.  sums (SUMMARY_DTYPE, one per chosen record) is required; records, n and
+        sel as in read_coverage.  A record is dropped when it is not emitted, has no columns, has an identity under
+        min_identity (permille of its columns), a shorter span under min_span, or, with max_drop < 1000, lies more than
+        max_drop permille under the best passed record of a read it names on a requested side.  read_lens_or_n_reads: the
+        reads of the window [read_first, read_first + n_reads), as their number or as anything with a length; None: no table,
+        which max_drop == 1000 allows (include/gact_hip.h gact_hip_filter_overlaps)"""
+        if isinstance(sides, str):
+            if sides not in _COVER_SIDES:
+                raise GactHipError("filter_overlaps: unknown sides %r (\"ref\", \"query\" or \"both\")" % (sides,))
+            sides = _COVER_SIDES[sides]
+        records, n = self._records_arg(records, n, slot)
+        if sel is not None:
+            sel = np.ascontiguousarray(sel, dtype=np.int32)
+        n_chosen = len(sel) if sel is not None else max(n, 0)
+        if sums is not None:
+            sums = np.ascontiguousarray(sums, dtype=SUMMARY_DTYPE)
+            if len(sums) != n_chosen:
+                raise GactHipError("filter_overlaps: %d summaries for %d chosen records" % (len(sums), n_chosen))
+        if read_lens_or_n_reads is None:
+            n_reads = 0
+        elif isinstance(read_lens_or_n_reads, (int, np.integer)):
+            n_reads = int(read_lens_or_n_reads)
+        else:
+            n_reads = len(read_lens_or_n_reads)
+        params = FilterParams(int(min_identity), int(min_span), int(max_drop))
+        reasons = np.zeros(n_chosen, dtype=np.int32) if why else None
+        reads = np.zeros(max(n_reads, 0), dtype=FILTER_READ_DTYPE) if table else None
+        n_kept = C.c_int32()
+        kept_at = np.empty(n_chosen, dtype=np.int32)          # (room for every chosen record: the call never has to be repeated)
+        kept_sel = np.empty(n_chosen, dtype=np.int32)
+        self._check(self.L.gact_hip_filter_overlaps(self.h, slot, n, _ptr(records), len(sel) if sel is not None else 0, _ptr(sel),
+                                                    _ptr(sums), int(sides), int(read_first), n_reads, C.byref(params), _ptr(reasons),
+                                                    kept_at.ctypes.data, kept_sel.ctypes.data, n_chosen, C.byref(n_kept),
+                                                    _ptr(reads)))
+        out = (kept_sel[:n_kept.value].copy(), sums[kept_at[:n_kept.value]] if sums is not None else None)
+        if table:
+            out += (reads,)
+        if why:
+            out += (reasons,)
+        return out
+
+    def last_filter_stats(self, slot=0):
+        """the slot's last filter call: device ms (HIP events around the whole call), reads of the window, chosen, counted and
+        kept records, the dropped ones per reason, device bytes the call holds for itself"""
+        return self._stats(self.L.gact_hip_last_filter_stats, FilterStats, slot)
 
     def place_reads(self, read_lens, read_first=0, n=None, records=None, sel=None, sums=None, mask_permille=PLACE_DEFAULT_MASK_PERMILLE,
                     mapq_cap=PLACE_DEFAULT_MAPQ_CAP, slot=0):

@@ -4,6 +4,7 @@
 //              [--candidates FILE | --dump-candidates FILE [--dsoft-only]] [--device-dsoft]
 //              [--device D] [--shard R/W] [--recode] [--cigar] [--paf] [--unique exact|pair] [--coverage K]
 //              [--pileup K [--ins-slots S] [--vcf A:P:H]] [--gfa [--unitigs K [--bubbles D] [--clean LO:HI:N]]] [--sam primary|all]
+//              [--min-identity P[:S[:D]]]
 //
 // Plays the part of reference darwin.cpp:451-646 for the GACT stage: owns the
 // globals gact.cpp reads, loads params.cfg and the two FASTA files, builds the
@@ -77,6 +78,15 @@
 // no likelihoods.  With --sam as well a feeder's gact_hip_pileup_add takes only the records its placement made primary or
 // supplementary -- the one gact_hip_place_reads call serves both -- so that a read that maps onto several copies of a repeat
 // votes once, and darwin.cons.fa is made from those counts too.  Without --vcf every output byte is as without the flag.
+// --min-identity P[:S[:D]] (with --device-dsoft, not with --rccl-gather; integers, 0 <= P <= 1000 per mille, S >= 0 bases,
+// 0 <= D <= 1000 per mille): every feeder, behind its run and behind --unique, takes the summaries of the records it would write
+// (one gact_hip_candidates_summaries call, which serves --paf as well) and filters them on the device (gact_hip_filter_overlaps):
+// a record goes when its alignment has no column, when its identity -- matches per mille of its columns -- is under P, when the
+// shorter of its two spans is under S, or, with a D, when it lies more than D under the best record of its query read (the
+// feeder's own reads are the window: a feeder holds every record of its reads).  Everything behind it -- the .out lines,
+// --cigar, --paf, --coverage, --gfa, --pileup, --sam -- sees the kept records only, and stdout gets one line per feeder: kept of
+// counted, and the dropped ones per reason.  A malformed value is refused before any file is read.  Without the flag every output
+// byte is as before.
 //
 // --device D: the GPU this process uses (the reference is single-device, cuda_host.cu:195).  --shard R/W: this
 // process is rank R of W -- it extends every W-th candidate (host filter) or the R-th contiguous range of reads
@@ -127,6 +137,9 @@ static int vcf_min_alt = 0, vcf_min_permille = 0, vcf_hom_permille = 0;
 static int sam_mode = 0;                         // --sam: 1 primary (and supplementary) lines, 2 all lines, 0: no SAM files
 static int clean_lo = -1, clean_hi = 0, clean_n = 0;   // --clean LO:HI:N: the ratios of the cleaning rounds in front of the unitigs, lo < 0: none
 static int bubble_dist = 0;                      // --bubbles D: max_dist of the bubble popping in front of the unitigs, 0: none
+static bool want_filter = false;                 // --min-identity P[:S[:D]]: the records filtered on the device behind --unique
+static gact_filter_params filter_params = {0, GACT_FILTER_DEFAULT_MIN_SPAN, GACT_FILTER_DEFAULT_MAX_DROP_PERMILLE};
+static bool filter_relative = false;             // ... with a D: the relative rule over the feeder's own reads
 // --coverage, --gfa: the records every feeder wrote a line for, in its file's order, and with --paf their summaries
 static std::vector<std::vector<gact_overlap> > cover_records;
 static std::vector<std::vector<gact_path_summary> > cover_sums;
@@ -416,6 +429,39 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
         std::fill(keep.begin(), keep.end(), 0);
         for (int32_t k = 0; k < n_kept; k++) keep[(size_t)kept[(size_t)k]] = 1;
     }
+    // --min-identity: the summaries of the emitted (--unique: selected) records and one gact_hip_filter_overlaps call over the
+    // slot's own records; what it keeps goes into `keep`, and the kept records' summaries serve --paf
+    std::vector<gact_path_summary> kept_sums;
+    if (want_filter) {
+        std::vector<int32_t> chosen;
+        for (int32_t k = 0; k < n; k++)
+            if (o[(size_t)k].emitted && keep[(size_t)k]) chosen.push_back(k);
+        const int32_t n_chosen = (int32_t)chosen.size();
+        std::vector<gact_overlap> rec((size_t)n_chosen);
+        std::vector<gact_path_summary> all_sums((size_t)n_chosen);
+        std::vector<int32_t> kept_at((size_t)n_chosen), kept_sel((size_t)n_chosen);
+        int32_t n_kept = 0;
+        gact_filter_stats fs{};
+        if (n_chosen) {
+            check(gact_hip_candidates_summaries(e, s.slot, n_chosen, chosen.data(), nf, same_file, rec.data(), all_sums.data()),
+                  "gact_hip_candidates_summaries");
+            // with a D the table covers this feeder's reads [lo, hi), whose records are all on this slot: the rule is complete
+            check(gact_hip_filter_overlaps(e, s.slot, n, nullptr, n_chosen, chosen.data(), all_sums.data(),
+                                           filter_relative ? GACT_COVER_QUERY : GACT_COVER_BOTH, filter_relative ? lo : 0,
+                                           filter_relative ? hi - lo : 0, &filter_params, nullptr, kept_at.data(), kept_sel.data(),
+                                           n_chosen, &n_kept, nullptr), "gact_hip_filter_overlaps");
+            check(gact_hip_last_filter_stats(e, s.slot, &fs), "gact_hip_last_filter_stats");
+        }
+        std::fill(keep.begin(), keep.end(), 0);
+        kept_sums.resize((size_t)n_kept);
+        for (int32_t k = 0; k < n_kept; k++) {
+            keep[(size_t)kept_sel[(size_t)k]] = 1;
+            kept_sums[(size_t)k] = all_sums[(size_t)kept_at[(size_t)k]];
+        }
+        printf("Filter (thread %d): kept %lld of %lld counted records; dropped: %lld empty, %lld identity, %lld span, %lld relative\n",
+               cpu_id, (long long)fs.kept, (long long)fs.counted, (long long)fs.empty, (long long)fs.identity, (long long)fs.span,
+               (long long)fs.relative);
+    }
     // --cigar: the alignments of the emitted (--unique: selected) candidates, a second pass on the device (gact_hip_candidates_paths)
     std::vector<int32_t> sel;
     std::vector<gact_path> paths;
@@ -448,8 +494,10 @@ static void device_feeder(int cpu_id, int lo, int hi, GPU_storage s, std::vector
     std::ofstream fpaf;
     if (want_paf) {
         std::vector<gact_overlap> rec(sel.size());
-        check(gact_hip_candidates_summaries(e, s.slot, (int32_t)sel.size(), sel.data(), nf, same_file, rec.data(), sums.data()),
-              "gact_hip_candidates_summaries");
+        if (want_filter) sums = kept_sums;                                    // (of the same records in the same order: no second call)
+        else
+            check(gact_hip_candidates_summaries(e, s.slot, (int32_t)sel.size(), sel.data(), nf, same_file, rec.data(), sums.data()),
+                  "gact_hip_candidates_summaries");
         fpaf.open(paf_name(cpu_id));
     }
     // --sam: where every read of this feeder goes (gact_hip_place_reads), for its SAM file and for --vcf
@@ -948,7 +996,7 @@ int main(int argc, char *argv[])
     if (argc >= 3 && strcmp(argv[1], "--selftest") == 0) return selftest(argv[2]);
     if (argc < 4) {
         fprintf(stderr, "Usage: darwin_hip <REFERENCE>.fasta <READS>.fasta CPU_THREADS --candidates FILE "
-                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K [--ins-slots S] [--vcf A:P:H]] [--gfa [--unitigs K [--bubbles D] [--clean LO:HI:N]]] [--sam primary|all]]\n");
+                        "[--params params.cfg] [--device-dsoft [--cigar] [--paf] [--unique exact|pair] [--coverage K] [--pileup K [--ins-slots S] [--vcf A:P:H]] [--gfa [--unitigs K [--bubbles D] [--clean LO:HI:N]]] [--sam primary|all] [--min-identity P[:S[:D]]]]\n");
         return 1;
     }
     std::string cand_path, dump_path, cfg_path = "params.cfg", gather_id;
@@ -1027,6 +1075,30 @@ int main(int argc, char *argv[])
             }
             clean_lo = lo; clean_hi = hi; clean_n = k;
         }
+        else if (!strcmp(argv[a], "--min-identity")) {
+            const char *v = a + 1 < argc ? argv[++a] : "";
+            long f[3] = {0, GACT_FILTER_DEFAULT_MIN_SPAN, GACT_FILTER_DEFAULT_MAX_DROP_PERMILLE};
+            int got = 0;
+            bool ok = *v != 0;
+            for (const char *at = v; ok && got < 3;) {
+                char *end = nullptr;
+                ok = *at >= '0' && *at <= '9';                               // (no sign, no blank, no empty field)
+                if (ok) f[got++] = strtol(at, &end, 10);
+                if (!ok || !*end) break;
+                ok = *end == ':' && got < 3;
+                at = end + 1;
+            }
+            if (!ok || f[0] > 1000 || f[1] > 0x7fffffffL || f[2] > 1000) {
+                fprintf(stderr, "--min-identity wants P[:S[:D]] (min identity per mille, min span, max drop per mille under the read's "
+                                "best) with integers 0 <= P <= 1000, S >= 0 and 0 <= D <= 1000, not '%s'\n", v);
+                return 1;
+            }
+            want_filter = true;
+            filter_relative = got == 3;
+            filter_params.min_identity_permille = (int32_t)f[0];
+            filter_params.min_span = (int32_t)f[1];
+            filter_params.max_drop_permille = (int32_t)f[2];
+        }
         else if (!strcmp(argv[a], "--sam")) {
             const char *v = a + 1 < argc ? argv[++a] : "";
             if (!strcmp(v, "primary")) sam_mode = 1;
@@ -1057,6 +1129,12 @@ int main(int argc, char *argv[])
         // the selection runs over the records of one engine slot: the host-filter mode writes through GACT_Batch, and the ranks of
         // a sharded job each hold part of a pair's candidates, so a selection per rank would be incomplete
         fprintf(stderr, "--unique: only with --device-dsoft, and not with --shard\n");
+        return 1;
+    }
+    if (want_filter && (!device_dsoft || !gather_id.empty())) {
+        // (as --paf: the filter reads the summaries of the engine's own candidate arrays, and the gathered lines come from the
+        // device's records, which know nothing of what a feeder kept)
+        fprintf(stderr, "--min-identity: only with --device-dsoft, and not with --rccl-gather\n");
         return 1;
     }
     if (coverage_depth && (!device_dsoft || shard_given)) {

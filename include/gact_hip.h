@@ -381,6 +381,80 @@ int gact_hip_read_coverage(gact_hip_engine *e, int slot, int32_t n, const gact_o
 typedef struct { float device_ms; int32_t reads; int64_t intervals, positions, scratch_bytes; } gact_cover_stats;
 int gact_hip_last_cover_stats(gact_hip_engine *e, int slot, gact_cover_stats *stats);
 
+/* ---- filter: the overlap set by identity, by span and by each read's own best record, decided on the device ----
+ * Under +1/-1/-1/-1 two unrelated sequences align with a positive score, so a false seed hit becomes an emitted record, and
+ * every pass behind a run takes what the run emitted.  The summaries of gact_hip_candidates_summaries carry n_eq, and identity
+ * parts the two kinds; where no absolute threshold does (reads against contigs and a diverged copy of them), the distance to
+ * the best record of the same read does.  This entry sits between the summaries and every pass that takes `sel` and `sums`
+ * (csrc/gact_filter.hpp).  The rule, all integers (64-bit where a product is formed), the same on every call and slot:
+ *
+ *   chosen   records sel[0..n_sel) of the n records; sel == NULL: all of [0, n).  k is a record's position in that list, r =
+ *            records[sel[k]] and s = sums[k]; sums is REQUIRED here.
+ *   figures  cols = n_eq + n_x + ins_bases + del_bases, t_span = n_eq + n_x + del_bases, q_span = n_eq + n_x + ins_bases,
+ *            ident = cols ? floor(1000 * n_eq / cols) : 0.
+ *   why[k]   the first test that fails, in this order:
+ *            1 GACT_FILTER_NOT_EMITTED  r.emitted == 0
+ *            2 GACT_FILTER_EMPTY        cols == 0
+ *            3 GACT_FILTER_IDENTITY     ident < min_identity_permille
+ *            4 GACT_FILTER_SPAN         min(t_span, q_span) < min_span
+ *            5 GACT_FILTER_RELATIVE     only when max_drop_permille < 1000: for some read x that the record names on a requested
+ *                                       side, best[x] - ident > max_drop_permille, where best[x] is the largest ident among the
+ *                                       records that passed tests 1 to 4 and name x on a requested side.  One pass, not iterated:
+ *                                       a record that this test drops still counts towards best
+ *            0 GACT_FILTER_KEPT         otherwise
+ *   counted  a chosen record that is emitted and has cols > 0
+ *   sides    GACT_COVER_REF: a record names read ref_id.  GACT_COVER_QUERY: read query_id.  GACT_COVER_BOTH: both, ref and query
+ *            ids naming the same reads.  No special rule for ref_id == query_id: such a record counts once per side, as in
+ *            gact_hip_read_coverage
+ *   window   the per-read table covers reads [read_first, read_first + n_reads), as gact_hip_place_reads takes them.
+ *            n_reads == 0: no table and no per-read work, allowed only with max_drop_permille == 1000
+ *   reads[i] read read_first + i: n_records = the counted records that name it on a requested side, n_passed = those that
+ *            passed tests 1 to 4, n_kept = those kept, best_permille = best[x] (0 when none passed), eq_sum and col_sum = the
+ *            sums of n_eq and cols over the passed records: eq_sum / col_sum is the read's own identity estimate
+ *
+ * Outputs, each of which may be NULL: why[0..n_chosen); kept_at[0..*n_kept), the ascending positions k of the kept records;
+ * kept_sel[0..*n_kept), the kept record indices (sel[k], or k when sel == NULL); reads[0..n_reads); *n_kept.  kept_sel goes on
+ * as `sel`, and sums[kept_at[.]] as `sums`, to every pass that takes those.  cap is the room of kept_at and kept_sel; with
+ * cap < *n_kept and a list given the call returns GACT_HIP_EINVAL with *n_kept filled in and the lists untouched (why and reads
+ * are written) -- call again with room, as with gact_hip_select_overlaps.
+ * The defaults: 650 lies between the false records of the simulator's truth block B (identity at most 557) and its true ones
+ * (at least 758) at the simulator's 15 % error; it is a parameter for the data, not a calibrated constant.  The span and the
+ * relative test are off by default.
+ * Refused with GACT_HIP_EINVAL, outputs untouched (*n_kept = 0): sums == NULL, min_identity_permille or max_drop_permille
+ * outside [0, 1000], min_span < 0, sides not 1, 2 or 3, n < 0 or n > 2^30, n_sel < 0 or n_sel > 2^30 with sel, cap < 0, an index in sel outside
+ * [0, n), n_reads < 0, max_drop_permille < 1000 with n_reads == 0, records == NULL on a slot without records or with n beyond
+ * them.  Refused with GACT_HIP_ERANGE: a counted record whose read id on a requested side lies outside the window, when
+ * n_reads > 0; the check is made on the device before the id is used as an index.  n == 0, or an empty selection, returns 0
+ * with *n_kept = 0 and a zeroed table.
+ * Synchronous on the slot's stream; the slot's records and every other pass's statistics stay as they were.  Device memory of
+ * its own, one allocation per slot, grown on demand: about 16 bytes per chosen record and 32 per read, 56 per host record, 4 per
+ * sel entry, 32 per summary. */
+#define GACT_FILTER_KEPT        0
+#define GACT_FILTER_NOT_EMITTED 1
+#define GACT_FILTER_EMPTY       2
+#define GACT_FILTER_IDENTITY    3
+#define GACT_FILTER_SPAN        4
+#define GACT_FILTER_RELATIVE    5
+#define GACT_FILTER_DEFAULT_MIN_IDENTITY_PERMILLE 650
+#define GACT_FILTER_DEFAULT_MIN_SPAN              0
+#define GACT_FILTER_DEFAULT_MAX_DROP_PERMILLE     1000
+typedef struct { int32_t min_identity_permille, min_span, max_drop_permille; } gact_filter_params;     /* 12 bytes */
+typedef struct { int32_t n_records, n_passed, n_kept, best_permille; int64_t eq_sum, col_sum; } gact_read_filter;   /* 32 bytes */
+int gact_hip_filter_overlaps(gact_hip_engine *e, int slot, int32_t n, const gact_overlap *records,
+                             int32_t n_sel, const int32_t *sel, const gact_path_summary *sums,
+                             int32_t sides, int32_t read_first, int32_t n_reads,
+                             const gact_filter_params *params /* NULL: defaults */,
+                             int32_t *why, int32_t *kept_at, int32_t *kept_sel, int32_t cap, int32_t *n_kept,
+                             gact_read_filter *reads);
+/* What the slot's last gact_hip_filter_overlaps call that got as far as the device and was not refused there did: HIP events on
+ * the slot's stream around the whole call (copies and kernels), the reads of the window, the chosen records, the counted ones,
+ * the kept ones, the dropped ones per reason, and the device memory the call holds for itself.  A call that is refused -- on the
+ * host, or by the device's check of sel and of the window -- leaves the figures of the call before it; a call that lacks room
+ * for its lists is not such a refusal and leaves its own. */
+typedef struct { float device_ms; int32_t reads; int64_t chosen, counted, kept, not_emitted, empty, identity, span, relative,
+                 scratch_bytes; } gact_filter_stats;
+int gact_hip_last_filter_stats(gact_hip_engine *e, int slot, gact_filter_stats *stats);
+
 /* ---- placement: where every read goes -- primary, supplementary and secondary records, and a MAPQ ----
  * What a user who maps reads against a reference or against contigs asks first: where does this read go, how sure is that, is
  * the read split between two places.  GACT_SELECT_PAIR answers per (ref, query, strand) only; this entry orders ALL records of
