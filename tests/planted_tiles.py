@@ -84,6 +84,22 @@ def pass_shape(R, Q, tile=320, overlap=120):
     return T_end - tB + 1, tB - (T_end - LAG), both, r2, T_end - t + 1
 
 
+def split_first_pointer_step(R, Q, early):
+    """split_first_pointer_step<13> of csrc/gact_p16s.hpp: (the first step whose pointers the traceback can reach, region 2's
+    lane in which the pointer window begins, its column within that lane).  Where Q > early, jj = 209 - early whatever R and Q
+    are: the lane and the column are set by the geometry alone"""
+    r_first = max(1, R - early + 1)
+    j_first = max(1, Q - early + 1)
+    jj = j_first + (C2 * K_GROUP - Q)                                   # 1-based index inside region 2
+    return r_first + (jj - 1) // C2 + K_GROUP, (jj - 1) // C2, (jj - 1) % C2
+
+
+def window_start(tile, overlap):
+    """(lane, column) of region 2 at which the pointer window of a tile wider than tile - overlap begins"""
+    early = tile - overlap
+    return (W2 - early) // C2, (W2 - early) % C2
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 def _random(rng, n):
     return ACGT[rng.integers(0, 4, size=n)]
@@ -268,10 +284,11 @@ def lin_sizes():
     return tuple(range(1, 65)) + (111, 112, 113, 119) + tuple(range(120, 137)) + tuple(range(193, 233)) + tuple(range(289, 321))
 
 
-def shapes(tile, overlap):
+def shapes(tile, overlap, pad=True):
     """the clean list's shapes at a geometry: the cross product of the edge set, each with two kinds; at 320/120 also every
     structural size of the lin files against itself and against the full tile, with 15 % noise, and bursts on the largest tiles
-    (walks that leave the default band need room for a run of 49 and for what pays for it)"""
+    (walks that leave the default band need room for a run of 49 and for what pays for it).  pad: a small edge set's shapes are
+    repeated until the list holds 600 candidates (the geometries of CONFIGS; those of GEOMETRIES are many and stay as they are)"""
     es = edge_set(tile, overlap)
     out = [(r, q) for r in es for q in es]
     if (tile, overlap) == (320, 120):
@@ -283,9 +300,16 @@ def shapes(tile, overlap):
         big = (224, 232, 289, 304, 319, 320)
         out += [(r, q, "burst") for r in big for q in big] + [(320, 320, "burst")] * 4
     else:
-        big = ([x for x in es if x >= 2 * BURSTS[0] + 8] or list(es))[-4:]
-        out += [(r, q, "burst") for r in big for q in big] * 2
-        while len(out) * 2 < 600:                                     # small edge sets: more kinds per shape
+        if tile - overlap >= BURSTS[0]:
+            # (below that the band is the whole pointer window, which no walk can leave; and the left phase's anchor of
+            # tile - overlap bases scores less than crossing a run costs, so the first tile would end in front of the run)
+            big = ([x for x in es if x >= 2 * BURSTS[0] + 8] or list(es))[-4:]
+            out += [(r, q, "burst") for r in big for q in big] * 2
+        if not pad and 0 < overlap < C2:
+            # an overlap this small: only a walk from the corner of a full tile is long enough to end at the early-termination
+            # limit, tile - overlap steps on, in front of the border -- and the edge set's cross product holds that shape once
+            out += [(tile, tile, k) for k in NOISY] * 8
+        while pad and len(out) * 2 < 600:                            # small edge sets: more kinds per shape
             out += [(r, q) for r in es for q in es]
     return out
 
@@ -312,7 +336,56 @@ CONFIGS = (
     (64, 8, (62, -1, -1, -1), ("split", "coop")),                 # ... and the first row-drifted one
     (512, 128, PLAIN, ("split",)),                                # uniform, 32 columns per lane
 )
-RAW_CONFIGS = ((320, 120, PLAIN), (320, 120, AFFINE))
+RAW_CONFIGS = ((320, 120, PLAIN), (320, 120, AFFINE), (317, 119, PLAIN))       # 317: N and lower case where the tile fills no whole lane
+
+# Tile geometries: R and Q leave unchanged where in region 2 the split pass's pointer window begins (window_start: tile - overlap
+# alone sets it), which of the three kernel families runs (derive_kernel_flags: tile <= 320, tile - overlap <= 208, tile > 512)
+# and how much of the last lane and lane group a full tile fills.  (tile, overlap, what the row is for, the main kernel that
+# engine.plan names for 50,000 candidates under PLAIN, the same under AFFINE)
+LIN, AFF, UNI = "SplitLayoutLin", "SplitLayoutAff<cbneg>", "UniformLayout<tag>"
+WIDE_LIN, WIDE_TAG = "WideLayoutLin", "WideLayoutTagged"                   # what 100 candidates get where tile <= 320
+Geometry = namedtuple("Geometry", "tile overlap what plain affine")
+GEOMETRIES = tuple(Geometry(*g) for g in (
+    (320, 112, "largest split early (208): the window begins on region 2's first column, lane 0 column 0", LIN, AFF),
+    (320, 113, "lane 0, column 1", LIN, AFF),
+    (320, 124, "last column of lane 0", LIN, AFF),
+    (320, 125, "first column of lane 1", LIN, AFF),
+    (320, 216, "first column of lane 8", LIN, AFF),
+    (320, 294, "first column of lane 14", LIN, AFF),
+    (320, 307, "first column of the last lane", LIN, AFF),
+    (320, 308, "inside the last lane: early less than a lane", LIN, AFF),
+    (320, 319, "one step per tile, 320 tiles a chain", LIN, AFF),
+    (320, 111, "early 209: the first past the split layout", UNI, UNI),
+    (209, 0, "the same boundary with early == tile", UNI, UNI),
+    (208, 0, "no region 1 at all, early == tile", LIN, AFF),
+    (209, 1, "one column in region 1", LIN, AFF),
+    (317, 119, "tile no multiple of 16, 13, 8 or 7", LIN, AFF),
+    (300, 100, "region 1 of 92 columns, no multiple of 7", LIN, AFF),
+    (250, 90, "tile no multiple of 16", LIN, AFF),
+    (100, 37, "both odd", LIN, AFF),
+    (33, 7, "two lane groups and one column", LIN, AFF),
+    (17, 3, "one lane group and one column", LIN, AFF),
+    (16, 8, "one lane group", LIN, AFF),
+    (15, 0, "less than one lane group", LIN, AFF),
+    (2, 1, "the smallest tile with an overlap", LIN, AFF),
+    (1, 0, "the smallest tile the engine accepts", LIN, AFF),
+    (321, 121, "first tile size on 32 columns per lane", UNI, UNI),
+    (321, 113, "early 208 would allow the split, the tile size does not", UNI, UNI),
+    (333, 0, "32 columns per lane, overlap 0", UNI, UNI),
+    (511, 200, "the last size below 512, odd", UNI, UNI),
+))
+# the window starts the split rows must cover: a lane's first column (lanes 0, 1, 8, 14, 15), its second, its last, the last lane
+WINDOW_STARTS = ((0, 0), (0, 1), (0, 12), (1, 0), (8, 0), (14, 0), (15, 0), (15, 1))
+
+
+def geometry_layouts(g):
+    """[(scoring, layout of tests/test_gpu_int16_edges.py's LAYOUTS)] that tests/test_gpu_planted_tiles.py runs a row through"""
+    if g.plain == UNI:
+        return [(PLAIN, "split"), (AFFINE, "split")]                  # (it resolves to the uniform kernel, as 320/100 does)
+    out = [(PLAIN, "split"), (AFFINE, "split"), (PLAIN, "coop"), (PLAIN, "wide")]
+    if (g.tile, g.overlap) in ((320, 125), (317, 119)):
+        out += [(PLAIN, "uniform"), (PLAIN, "plain")]
+    return out
 
 
 def resolve(scoring):
@@ -328,8 +401,9 @@ def resolve(scoring):
     return tuple(scoring)
 
 
-def default_threshold(scoring):
-    return 35 * max(scoring[0], 1)
+def default_threshold(scoring, tile=320, overlap=120):
+    """the first tile's threshold: 35 matches, or as many as the exact segment of tile - overlap bases has"""
+    return min(35, tile - overlap) * max(scoring[0], 1)
 
 
 _PLANTED, _LISTS = {}, {}
@@ -337,10 +411,12 @@ _PLANTED, _LISTS = {}, {}
 
 def planted(tile, overlap, raw=False):
     """the reads and candidates of one geometry, built once: the anchors hold for every scoring used with default_threshold
-    (35 <= 56, the shortest tile - overlap here), so every scoring of a geometry shares them"""
+    (min(35, tile - overlap) matches), so every scoring of a geometry shares them"""
     key = (tile, overlap, raw)
     if key not in _PLANTED:
-        _PLANTED[key] = plant(tile, overlap, (1, -1, -1, -1), 35, raw_shapes(tile, overlap) if raw else shapes(tile, overlap),
+        pad = any((tile, overlap) == c[:2] for c in CONFIGS)
+        _PLANTED[key] = plant(tile, overlap, (1, -1, -1, -1), min(35, tile - overlap),
+                              raw_shapes(tile, overlap) if raw else shapes(tile, overlap, pad),
                               (KINDS[2],) if raw else KINDS, seed=4000 + tile * 3 + overlap + (7 if raw else 0), raw=raw)
     return _PLANTED[key]
 
@@ -351,7 +427,7 @@ def planted_lists(oracle, tile, overlap, scoring, raw=False):
     key = (tile, overlap, scoring, raw)
     if key not in _LISTS:
         pl = planted(tile, overlap, raw)
-        walks = describe(oracle, pl, scoring, default_threshold(scoring))
+        walks = describe(oracle, pl, scoring, default_threshold(scoring, tile, overlap))
         keep = np.array([w.present for w in walks], dtype=bool)
         share = {d: float(keep[pl.meta["reverse"] == d].mean()) for d in (0, 1)}
         kept = pl._replace(cf=pl.cf[keep], cr=pl.cr[keep], meta=pl.meta[keep])

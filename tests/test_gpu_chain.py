@@ -134,7 +134,11 @@ def test_chain_other_scoring(oracle, scoring, kernel_family):
 @pytest.mark.parametrize("tile,overlap,thr", [(320, 120, 35), (128, 32, 20), (200, 100, 35), (320, 200, 60),
                                               (320, 100, 35),     # early 220 > 208: uniform packed layout
                                               (400, 150, 35),     # tile > 320: the 32-column kernels
-                                              (512, 256, 50)])
+                                              (512, 256, 50),
+                                              # tests/planted_tiles.py GEOMETRIES: an odd tile, early 208 | 209, the pointer
+                                              # window on a lane's first column, 320 | 321, an early of one lane, small tiles
+                                              (317, 119, 35), (320, 112, 35), (320, 111, 35), (320, 125, 35), (321, 121, 35),
+                                              (320, 307, 13), (100, 37, 20), (17, 3, 5)])
 def test_chain_other_geometry(oracle, tile, overlap, thr):
     from gact_amd import synth
     rs = synth.simulate_reads(15000, n_reads=12, seed=21, mean_len=3000, sd_len=800, min_len=800, max_len=6000)

@@ -70,7 +70,9 @@ def test_raw_byte_reads_equal_the_model(oracle, scoring):
 
 @pytest.mark.parametrize("raw", [True, False], ids=["raw-bytes", "acgt"])
 @pytest.mark.parametrize("scoring", SCORINGS)
-@pytest.mark.parametrize("tile_size,tile_overlap", [(320, 120), (64, 24)])
+# (320/125: the pointer window begins on a lane's first column; 317/119: a tile that fills no whole lane; 321/121: the first tile
+# size on 32 columns per lane -- tests/planted_tiles.py GEOMETRIES)
+@pytest.mark.parametrize("tile_size,tile_overlap", [(320, 120), (64, 24), (320, 125), (317, 119), (321, 121)])
 def test_crafted_candidates_equal_the_model(oracle, tile_size, tile_overlap, scoring, raw):
     """in order (sel = None), as a reversed selection, and with same_file off (the same ops; `emitted` as the normal run
     with same_file off says)"""

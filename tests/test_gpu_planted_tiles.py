@@ -7,7 +7,9 @@ cells on the walk and where it ends (zero levels), I and D codes and ties at the
 leave the band, and lane partners of like and unlike size.  tests/test_planted_tiles.py holds the lists to that on the CPU.
 
 Every configuration of planted_tiles.CONFIGS runs the geometry's list through each of its layouts and compares every record field
-with the oracle (oracle.gact_many); every run asserts from last_run_stats() that the pass meant is the one that ran."""
+with the oracle (oracle.gact_many); every run asserts from last_run_stats() that the pass meant is the one that ran.  Every row of
+planted_tiles.GEOMETRIES does the same with its own list: the tile geometries at which the kernel family, the split pass's pointer
+window or the fill of the last lane change."""
 import numpy as np
 import pytest
 
@@ -24,7 +26,8 @@ _IDS = ["%d/%d-%s-%s" % (t, o, sc if isinstance(sc, str) else "%d,%d,%d,%d" % sc
 def _expected_stats(tile, overlap, scoring, layout):
     """what last_run_stats() must say (tests/test_gpu_int16_edges.py's _expected_stats, from the engine's plan of a large list)"""
     from gact_amd import engine
-    main = engine.plan(50000, tile_size=tile, tile_overlap=overlap, scoring=scoring, threshold=P.default_threshold(scoring))["main_kernel"]
+    main = engine.plan(50000, tile_size=tile, tile_overlap=overlap, scoring=scoring,
+                       threshold=P.default_threshold(scoring, tile, overlap))["main_kernel"]
     kind = "plain" if layout == "plain" else _kind(main)
     uniform = main.startswith("Uniform") or layout == "uniform"
     lin = kind == "lin" and not uniform
@@ -53,7 +56,8 @@ def _records(oracle, pl, tile, overlap, scoring, raw=False):
     key = (tile, overlap, scoring, raw)
     if key not in _WANT:
         cat, offs, rcat, roffs = _seqs(pl)
-        kw = dict(same_file=True, tile_size=tile, tile_overlap=overlap, threshold=P.default_threshold(scoring), scoring=scoring, n_threads=8)
+        kw = dict(same_file=True, tile_size=tile, tile_overlap=overlap, threshold=P.default_threshold(scoring, tile, overlap),
+                  scoring=scoring, n_threads=8)
         wf, _ = oracle.gact_many(cat, offs, cat, offs, pl.cf, complement=False, **kw)
         wr, _ = oracle.gact_many(cat, offs, rcat, roffs, pl.cr, complement=True, **kw)
         _WANT[key] = np.concatenate([wf, wr])
@@ -72,7 +76,8 @@ def _run(monkeypatch, pl, scoring, layout, band=None, orders=(None,)):
     if band is not None:
         monkeypatch.setenv("GACT_HIP_BAND", str(band))
     cat, offs, rcat, roffs = _seqs(pl)
-    eng = engine.Engine(tile_size=pl.tile, tile_overlap=pl.overlap, scoring=scoring, threshold=P.default_threshold(scoring))
+    eng = engine.Engine(tile_size=pl.tile, tile_overlap=pl.overlap, scoring=scoring,
+                        threshold=P.default_threshold(scoring, pl.tile, pl.overlap))
     out = []
     try:
         eng.upload(engine.SET_REF, cat, offs); eng.upload(engine.SET_QUERY, cat, offs); eng.upload(engine.SET_QUERY_RC, rcat, roffs)
@@ -104,6 +109,29 @@ def test_planted_tiles_match_the_oracle(monkeypatch, oracle, tile, overlap, scor
     if want_stats["linear_gap"] and any(w.band > 48 for w in walks):
         # default band: the walks that leave it give up and their tiles run again with every block stored.  (Only under the
         # largest |g| no walk can: 49 gap moves cost more than a tile of 320 rows can score, tests/test_planted_tiles.py)
+        assert st["band_redos"] > 0, (tag, st)
+    _same(got, _records(oracle, pl, tile, overlap, scoring), tag)
+    _reaches_the_tiles(got, pl)
+
+
+_GEO_CASES = [(g, sc, lay) for g in P.GEOMETRIES for sc, lay in P.geometry_layouts(g)]
+_GEO_IDS = ["%d/%d-%s-%s" % (g.tile, g.overlap, "plain" if sc == P.PLAIN else "affine", lay) for g, sc, lay in _GEO_CASES]
+
+
+@pytest.mark.parametrize("g,scoring,layout", _GEO_CASES, ids=_GEO_IDS)
+def test_planted_tiles_match_the_oracle_at_every_geometry(monkeypatch, oracle, g, scoring, layout):
+    """planted_tiles.GEOMETRIES: where the split pass's pointer window begins (tile - overlap alone sets its lane and column), which
+    kernel family runs, and tiles that fill no whole lane or lane group -- what no R x Q at 320/120 moves.  The same comparison
+    as above, on the row's own edge set crossed with itself"""
+    tile, overlap = g.tile, g.overlap
+    pl, walks, _ = P.planted_lists(oracle, tile, overlap, scoring)
+    (got, st), = _run(monkeypatch, pl, scoring, layout)
+    tag = "%d/%d %s %s" % (tile, overlap, (scoring,), layout)
+    want_stats = _expected_stats(tile, overlap, scoring, layout)
+    assert (want_stats["layout"] == "packed16-uniform") == (g.plain == P.UNI or layout == "uniform"), (tag, want_stats)
+    print(tag, len(got), "candidates, band_redos", st["band_redos"], "main_ms %.1f" % st["main_ms"])
+    _check_stats(st, want_stats, tag)
+    if want_stats["linear_gap"] and any(w.band > 48 for w in walks):
         assert st["band_redos"] > 0, (tag, st)
     _same(got, _records(oracle, pl, tile, overlap, scoring), tag)
     _reaches_the_tiles(got, pl)
@@ -142,7 +170,7 @@ def test_lane_partners_like_and_unlike(monkeypatch, oracle, layout):
     _same(back[0], back[1], "%s: sorted against shuffled" % layout)
 
 
-@pytest.mark.parametrize("tile,overlap,scoring", P.RAW_CONFIGS, ids=("plain", "affine"))
+@pytest.mark.parametrize("tile,overlap,scoring", P.RAW_CONFIGS, ids=("plain", "affine", "317/119-plain"))
 def test_raw_bytes(monkeypatch, oracle, tile, overlap, scoring):
     """N and lower-case bases inside the planted tiles: the raw-byte kernels of the split layout"""
     pl, _, _ = P.planted_lists(oracle, tile, overlap, scoring, raw=True)

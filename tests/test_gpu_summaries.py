@@ -49,7 +49,7 @@ def _model_of(exp):
 
 @pytest.mark.parametrize("raw", [True, False], ids=["raw-bytes", "acgt"])
 @pytest.mark.parametrize("scoring", [LINEAR, AFFINE], ids=["linear", "affine"])
-@pytest.mark.parametrize("tile_size,tile_overlap", [(320, 120), (64, 24)])
+@pytest.mark.parametrize("tile_size,tile_overlap", [(320, 120), (64, 24), (320, 125), (317, 119), (321, 121)])   # (planted_tiles.GEOMETRIES)
 def test_crafted_candidates_and_additions_equal_the_paths_and_the_model(oracle, tile_size, tile_overlap, scoring, raw):
     cb = summary_cases.combined(raw)
     kw = dict(tile_size=tile_size, tile_overlap=tile_overlap, scoring=scoring)

@@ -57,7 +57,11 @@ def test_tiles_with_non_acgt(oracle):
 
 
 @pytest.mark.parametrize("tile,overlap", [(320, 120), (320, 0), (320, 319), (128, 32), (64, 8), (96, 48), (448, 128),
-                                          (512, 200)])
+                                          (512, 200),
+                                          # tests/planted_tiles.py GEOMETRIES: tiles that fill no whole lane or lane group, tiles
+                                          # below one lane, either side of 320 | 321 and of early 208 | 209, an early of one lane
+                                          (317, 119), (321, 121), (209, 0), (208, 0), (100, 37), (33, 7), (17, 3), (16, 8),
+                                          (15, 0), (2, 1), (1, 0), (333, 0), (511, 200), (320, 307)])
 def test_other_tile_geometries(oracle, tile, overlap):
     from gact_amd import engine
     eng = engine.Engine(tile_size=tile, tile_overlap=overlap)

@@ -140,6 +140,41 @@ def test_oracle_equals_reference_chains_at_int16_edges(oracle, reflib):
     assert n > 500
 
 
+def test_oracle_equals_reference_at_the_geometry_edges(oracle, reflib):
+    """every row of planted_tiles.GEOMETRIES (tiles of 1 to 511 bases, early-termination limits of 1 to 333) under both scorings:
+    12 planted tiles, half of them read back to front, with the row's limit, and 8 whole planted candidates, both phases and both
+    strands.  The GPU geometry tests compare with the oracle; here the oracle follows the reference at the same geometries"""
+    from gact_amd import synth
+    import planted_tiles as P
+    n_tiles = n_chains = 0
+    for g in P.GEOMETRIES:
+        pl = P.planted(g.tile, g.overlap)
+        early = g.tile - g.overlap
+        by_phase = [np.flatnonzero(pl.meta["reverse"] == d) for d in (0, 1)]
+        for sc in (P.PLAIN, P.AFFINE):
+            thr = P.default_threshold(sc, g.tile, g.overlap)
+            for idx in by_phase:
+                for k in idx[np.linspace(0, len(idx) - 1, min(6, len(idx))).astype(int)]:
+                    a, b, _, _ = P._planted_bytes(pl, k)
+                    rev = bool(pl.meta[k]["reverse"])
+                    assert oracle.align_with_bt(a, b, sc, rev, False, early) == reflib.align_with_bt(a, b, sc, rev, False, early), \
+                        (g, sc, pl.meta[k])
+                    n_tiles += 1
+                # (other candidates than the tiles': one off the even spacing, so that the chains are of other shapes)
+                for j, k in enumerate(idx[np.linspace(0, len(idx) - 1, min(4, len(idx)) + 1).astype(int)[1:]]):
+                    comp = bool(j % 2)
+                    c = (pl.cr if comp else pl.cf)[k]
+                    r, q = pl.rs.reads[c["ref_id"]].tobytes(), pl.rs.reads[c["query_id"]]
+                    q = (synth.revcomp(q) if comp else q).tobytes()
+                    kw = dict(tile_size=g.tile, tile_overlap=g.overlap, threshold=thr, ref_id=int(c["ref_id"]),
+                              query_id=int(c["query_id"]), complement=comp, scoring=sc)
+                    ov, _ = oracle.gact(r, q, int(c["ref_pos"]), int(c["query_pos"]), **kw)
+                    line = oracle.format_line(ov, "r", "q") if ov.emitted else ""
+                    assert line == reflib.gact_line(r, q, int(c["ref_pos"]), int(c["query_pos"]), **kw), (g, sc, pl.meta[k], comp)
+                    n_chains += 1
+    assert n_tiles > 600 and n_chains > 400, (n_tiles, n_chains)
+
+
 def test_gact_many_threads_agree(oracle):
     from gact_amd import synth
     rs = synth.simulate_reads(9000, n_reads=8, seed=3, mean_len=2500, sd_len=500, min_len=800, max_len=4000)
