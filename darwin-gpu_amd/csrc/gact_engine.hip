@@ -153,6 +153,30 @@ struct PassTimer {
     }
 };
 
+// Diagnostic (GACT_HIP_POISON_SCRATCH=<seed>): seeded garbage (gact::poison_kernel) over a pass's WHOLE allocation, not over
+// this call's layout of it, in front of the call's first write, so that a region the pass reads without having copied, zeroed
+// or wholly written it holds words that change with the seed and with every fill instead of what an earlier call left there.
+// One record per engine; the passes' allocations point at it (null: the switch is unset, nothing is launched or counted).
+struct ScratchPoison {
+    uint32_t seed = 0;
+    unsigned blocks = 1;                        // the fill's grid: eight waves on every SIMD
+    std::atomic<uint32_t> calls{0};             // mixed into the seed: no two fills write the same words
+    std::atomic<int64_t> fills{0}, bytes{0};    // gact_hip_scratch_fills
+    int fill(void *p, size_t n_bytes, hipStream_t stream)
+    {
+        if (!p || n_bytes == 0) return 0;
+        const uint32_t salt = seed * 0x01000193u + calls.fetch_add(1) * 0x9E3779B9u;
+        const size_t words = n_bytes / sizeof(uint32_t);
+        if (words) hipLaunchKernelGGL(gact::poison_kernel, dim3(blocks), dim3(256), 0, stream, (uint32_t *)p, words, salt);
+        HIP_TRY(hipGetLastError());
+        if (n_bytes % sizeof(uint32_t))          // (hipMalloc's memory is word-aligned; an odd size leaves up to three bytes)
+            HIP_TRY(hipMemsetAsync((uint8_t *)p + words * sizeof(uint32_t), (int)(salt >> 24 | 1), n_bytes % sizeof(uint32_t), stream));
+        fills.fetch_add(1);
+        bytes.fetch_add((int64_t)n_bytes);
+        return 0;
+    }
+};
+
 // What a pass behind a run keeps between its calls (gact_pass.hpp): one allocation that only grows, to exactly what the
 // largest call so far needed, the events around a call, and the figures of the last one (gact_hip_last_*_stats).
 template <class Stats> struct PassScratch {
@@ -161,6 +185,7 @@ template <class Stats> struct PassScratch {
     size_t bytes = 0;
     Stats stats{};
     bool timed = false;
+    ScratchPoison *poison = nullptr;     // GACT_HIP_POISON_SCRATCH: begin() fills the allocation in front of ev0
     // non-zero: the device refused (the runtime's sticky error is cleared; the caller words the failure)
     int reserve(size_t want)
     {
@@ -175,8 +200,12 @@ template <class Stats> struct PassScratch {
     {
         stats = Stats{};
         timed = false;
+        if (int rc = refill(stream)) return rc;          // (in front of ev0: device_ms does not count the fill)
         return timer.start(stream, who);
     }
+    // the fill alone: for an allocation that is kept state and opens without begin() (the pileup window), or that grows in the
+    // middle of a call (the variants' records)
+    int refill(hipStream_t stream) { return poison ? poison->fill(p, bytes, stream) : 0; }
     int end(hipStream_t stream)
     {
         int rc = timer.stop(stream, &stats.device_ms);
@@ -464,6 +493,7 @@ static const OptionDef kOptions[] = {
     {"no_side_lane", "GACT_HIP_NO_SIDE_LANE", 'c', 's', "routed raw-byte launches after the 2-bit ones instead of beside them"},
     {"band", "GACT_HIP_BAND", 'c', 'k', "width of the stored pointer band in columns (default 48; 0: the whole window)"},
     {"poison_ws", "GACT_HIP_POISON_WS", 'c', 'k', "<seed>: seeded garbage over the traceback workspace before every launch (tests)"},
+    {"poison_scratch", "GACT_HIP_POISON_SCRATCH", 'c', 'k', "<seed>: seeded garbage over the whole scratch allocation of every pass behind a run, the path buffers and a newly opened pileup window, before the call's first write (tests; gact_hip_scratch_fills counts the fills)"},
     {"no_overlap", "GACT_HIP_NO_OVERLAP", 'c', 's', "seed launch, then one main launch, always; live: overlap_seed"},
     {"overlap_seed", nullptr, 'l', 's', "1 / 0: ordered, overlapped seeding of large runs on an idle engine"},
     {"shared_twelfths", "GACT_HIP_SHARED_TWELFTHS", 'l', 's', "<n>: a linear-gap main launch that shares the machine and has more chains than two thirds of the resident tile slots hold takes n twelfths of the resident blocks (default 6)"},
@@ -568,6 +598,7 @@ struct gact_hip_engine {
     bool chain_prio = true;     // main launch: longest chains first in the DP issue order too
     bool static_prio = false;   // GACT_HIP_STATIC_PRIO: fixed thresholds instead of the ranking (read once, at create)
     uint32_t poison = 0;        // GACT_HIP_POISON_WS=<seed>: the workspace is filled with a seeded pattern before every launch
+    ScratchPoison scratch_poison;       // GACT_HIP_POISON_SCRATCH=<seed> (seed 0: unset): the passes' allocations are filled before their first write
     int rank16 = (12 << 8) | 8; // GACT_HIP_RANK16: the ranking's thresholds in sixteenths of the longest running chain, hi << 8 | mid
     bool seed16 = false;        // first tiles on the packed seed kernel too (arg-max keys fit)
     int seed_grid_blocks = 0;   // persistent grid of the packed seed kernel (2 waves per SIMD)
@@ -614,6 +645,12 @@ int check_slot(gact_hip_engine *e, int slot)
     if (slot < 0 || slot >= e->n_user)
         return fail(GACT_HIP_EINVAL, "slot %d out of range [0,%d)", slot, e->n_user);
     return 0;
+}
+
+// GACT_HIP_POISON_SCRATCH: the fill of a device array that is no PassScratch (the path buffers, the corrected reads' bytes)
+int poison_scratch(gact_hip_engine *e, void *p, size_t bytes, hipStream_t stream)
+{
+    return e->scratch_poison.seed ? e->scratch_poison.fill(p, bytes, stream) : 0;
 }
 
 // a call for `slot` from this thread, now (the combiner's guess at who is about to submit a run)
@@ -1041,6 +1078,15 @@ int gact_hip_create(const gact_hip_params *p, gact_hip_engine **out)
     if (const char *v = opt_env("combine_window_us")) e->cb.window_us = std::max(0, atoi(v));
     e->cb.n_merge = (e->cb.enabled && p->n_slots > 1) ? 2 : 0;
     e->slots.resize(p->n_slots + e->cb.n_merge);            // (never resized again: references into it stay good)
+    if (const char *v = opt_env("poison_scratch")) {
+        ScratchPoison *sp = &e->scratch_poison;
+        sp->seed = (uint32_t)strtoul(v, nullptr, 0) | 0x80000000u;
+        sp->blocks = (unsigned)std::max(1, e->prop.multiProcessorCount) * 8;
+        for (Slot &sl : e->slots)
+            sl.summary.poison = sl.select.poison = sl.cover.poison = sl.graph.poison = sl.unitig.poison = sl.bubble.poison =
+                sl.prune.poison = sl.clean.poison = sl.place.poison = sl.filter.poison = sp;
+        e->pileup.scratch.poison = e->pileup.variants.poison = sp;
+    }
     // (the first merge slot with the callers' slots: its 1.3 GB would otherwise be allocated inside the first merged launch)
     for (int k = 0; k < p->n_slots + (e->cb.n_merge ? 1 : 0); k++)
         if ((rc = init_slot(e, e->slots[k]))) { gact_hip_destroy(e); return rc; }
@@ -1910,6 +1956,14 @@ int64_t gact_hip_options_describe(char *buf, int64_t cap)
         buf[n] = 0;
     }
     return (int64_t)t.size() + 1;
+}
+
+int gact_hip_scratch_fills(gact_hip_engine *e, int64_t *fills, int64_t *bytes)
+{
+    if (!e || !fills || !bytes) return fail(GACT_HIP_EINVAL, "scratch_fills: NULL argument");
+    *fills = e->scratch_poison.fills.load();
+    *bytes = e->scratch_poison.bytes.load();
+    return 0;
 }
 
 void *gact_hip_device_overlaps(gact_hip_engine *e, int slot)

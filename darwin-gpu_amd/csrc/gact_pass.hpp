@@ -182,6 +182,12 @@ static int select_candidates(gact_hip_engine *e, int slot, int32_t n_sel, const 
     return 0;
 }
 
+// GACT_HIP_POISON_SCRATCH over a DevBuf: all `cap` elements
+template <class T> static int poison_buf(gact_hip_engine *e, DevBuf<T> &b, hipStream_t stream)
+{
+    return poison_scratch(e, b.p, b.cap * sizeof(T), stream);
+}
+
 // the path run's pop counter and events, made on the slot's first path run or pileup add
 static int path_bufs_init(Slot::PathBufs &pb, const char *who)
 {
@@ -237,6 +243,17 @@ static int launch_path_chunk(gact_hip_engine *e, Slot &sl, const Selection &sn, 
         pb.op_off.reserve((size_t)n) || pb.n_cols.reserve(2 * (size_t)n) || pb.n_ops.reserve((size_t)n) ||
         pb.cols.reserve((size_t)bytes + 64))
         return fail(GACT_HIP_ENOMEM, "%s: device allocation failed (%d candidates, %lld column bytes)", who, n, (long long)bytes);
+    // GACT_HIP_POISON_SCRATCH: every array of the chunk, whole, in front of its copies and memsets.  A pileup add queues this
+    // chunk while the one before may still run: its chain kernel and its pileup kernel were launched on sl.stream, as the fills
+    // are, so they have read these arrays before a fill writes them (and pileup_add reserves them once, before its first chunk).
+    if (e->scratch_poison.seed) {
+        int rc;
+        if ((rc = poison_buf(e, pb.cands, sl.stream)) || (rc = poison_buf(e, pb.records, sl.stream)) ||
+            (rc = poison_buf(e, pb.col_off, sl.stream)) || (rc = poison_buf(e, pb.op_off, sl.stream)) ||
+            (rc = poison_buf(e, pb.n_cols, sl.stream)) || (rc = poison_buf(e, pb.n_ops, sl.stream)) ||
+            (rc = poison_buf(e, pb.cols, sl.stream)))
+            return rc;
+    }
     HIP_TRY(hipMemcpyAsync(pb.cands.p, sn.tagged.data() + first, (size_t)n * sizeof(gact_candidate), hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(hipMemcpyAsync(pb.col_off.p, col_off.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, sl.stream));
     HIP_TRY(hipMemsetAsync(pb.n_cols.p, 0, 2 * (size_t)n * sizeof(int32_t), sl.stream));

@@ -58,6 +58,7 @@ int gact_hip_candidates_paths(gact_hip_engine *e, int slot, int32_t n_sel, const
         room = room && total_ops + chunk_ops <= ops_cap;
         if (room && chunk_ops > 0) {
             if (pb.ops.reserve((size_t)chunk_ops)) return fail(GACT_HIP_ENOMEM, "candidates_paths: device allocation failed (%lld ops)", (long long)chunk_ops);
+            if ((rc = poison_buf(e, pb.ops, sl.stream))) return rc;
             HIP_TRY(hipMemcpyAsync(pb.op_off.p, op_off.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, sl.stream));
             hipLaunchKernelGGL(gact::path_ops_kernel<true>, dim3(op_blocks), dim3(256), 0, sl.stream, pb.cols.p, pb.col_off.p, pb.n_cols.p,
                                n, nullptr, pb.op_off.p, pb.ops.p);

@@ -373,6 +373,9 @@ int gact_hip_pileup_begin_ins(gact_hip_engine *e, int32_t read_first, int32_t n_
         return fail(GACT_HIP_ENOMEM, "pileup_begin: device allocation failed (%d reads, %lld positions, %zu bytes)", n_reads,
                     (long long)positions, bytes);
     hipStream_t stream = e->slots[0].stream;
+    // GACT_HIP_POISON_SCRATCH: here and nowhere else; from now to the next begin the window is kept state, which add, finish,
+    // corrected and variants build on
+    if ((rc = ps.refill(stream))) return rc;
     if (at_cons) HIP_TRY(hipMemsetAsync(ps.p, 0, at_cons, stream));
     HIP_TRY(hipMemsetAsync(ps.p + at_reads, 0, bytes - at_reads, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -614,6 +617,7 @@ int gact_hip_pileup_corrected(gact_hip_engine *e, int32_t min_depth, gact_pileup
             }
             pl.seq_cap = (size_t)totals[0];
         }
+        if ((rc = poison_scratch(e, pl.seq, pl.seq_cap, stream))) return rc;       // (the bytes are scratch: every call spells them anew)
         hipLaunchKernelGGL(gact::pileup_spell_kernel<true>, grid, block, 0, stream, d_counts, d_ins, K, own, d_cons,
                            rs.d_offsets + pl.read_first, (long long)pl.base, pl.n_reads, (uint32_t)min_depth, d_read_at, d_reads,
                            pl.seq, totals[0]);

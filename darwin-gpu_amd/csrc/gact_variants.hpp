@@ -350,6 +350,7 @@ int gact_hip_pileup_variants(gact_hip_engine *e, const gact_variant_params *para
         room = totals[0];
         if (ps.reserve(at_rec + (size_t)room * sizeof(gact_variant)))
             return fail(GACT_HIP_ENOMEM, "pileup_variants: device allocation failed (%lld records)", totals[0]);
+        if ((rc = ps.refill(stream))) return rc;           // GACT_HIP_POISON_SCRATCH: the new block, in front of the recount
     }
     const bool fits = !variants || cap >= totals[0];
     if (variants && fits && totals[0] > 0) {

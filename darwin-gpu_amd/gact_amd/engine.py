@@ -430,6 +430,8 @@ def load():
     L.gact_hip_stream.restype = vp
     L.gact_hip_measure_valu_rate.argtypes = [vp, C.POINTER(C.c_double)]
     L.gact_hip_measure_valu_rate.restype = C.c_int
+    L.gact_hip_scratch_fills.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.gact_hip_scratch_fills.restype = C.c_int
     L.gact_hip_format_overlap.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, i32]
     L.gact_hip_dsoft_build.argtypes = [vp, C.POINTER(DsoftParams), C.POINTER(DsoftInfo)]
     L.gact_hip_dsoft_query.argtypes = [vp, C.c_int, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_float)]
@@ -586,7 +588,7 @@ EXPORTS = ("gact_hip_create", "gact_hip_destroy", "gact_hip_last_error", "gact_h
            "gact_hip_pileup_begin_ins", "gact_hip_pileup_corrected", "gact_hip_last_pileup_ins_stats",
            "gact_hip_place_reads", "gact_hip_last_place_stats", "gact_hip_format_sam", "gact_hip_format_sam_unmapped",
            "gact_hip_pileup_variants", "gact_hip_last_variant_stats", "gact_hip_format_vcf",
-           "gact_hip_filter_overlaps", "gact_hip_last_filter_stats")
+           "gact_hip_filter_overlaps", "gact_hip_last_filter_stats", "gact_hip_scratch_fills")
 
 
 def plan(count, flags=0, compute_units=256, tile_size=320, tile_overlap=120, scoring=(1, -1, -1, -1), threshold=35):
@@ -1295,6 +1297,13 @@ class Engine:
         v = C.c_double()
         self._check(self.L.gact_hip_measure_valu_rate(self.h, C.byref(v)))
         return float(v.value)
+
+    def scratch_fills(self):
+        """(fills, bytes) of GACT_HIP_POISON_SCRATCH since the engine was made: how often a pass's scratch, a path buffer or a
+        newly opened pileup window was filled with seeded garbage, and the bytes that covered; (0, 0) with the switch unset"""
+        fills, nbytes = C.c_int64(), C.c_int64()
+        self._check(self.L.gact_hip_scratch_fills(self.h, C.byref(fills), C.byref(nbytes)))
+        return int(fills.value), int(nbytes.value)
 
     def device_overlaps_ptr(self, slot=0):
         return self.L.gact_hip_device_overlaps(self.h, slot)

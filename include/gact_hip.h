@@ -1157,6 +1157,11 @@ int gact_hip_set_option(gact_hip_engine *e, const char *name, int32_t value);
  * class | what it does`.  Writes at most cap bytes (NUL-terminated) into buf, returns the size the whole table needs.
  * No engine, no device. */
 int64_t gact_hip_options_describe(char *buf, int64_t cap);
+/* GACT_HIP_POISON_SCRATCH=<seed> (a test switch, read in gact_hip_create): how many times since then the engine has filled
+ * a pass's whole scratch allocation, a path buffer, a newly opened pileup window or the corrected reads' bytes with seeded
+ * garbage in front of the call's first write, and how many bytes those fills covered.  Both 0 with the switch unset: no
+ * launch is added then. */
+int gact_hip_scratch_fills(gact_hip_engine *e, int64_t *fills, int64_t *bytes);
 /* The launch plan -- sequence, kernels, grids -- that an engine of parameters p makes for one pass over `count` candidates on a
  * device of compute_units CUs (kernels at their nominal occupancy), as one JSON object.  flags: bit 0 = the read sets hold
  * bytes other than A/C/G/T, bit 1 = the launch shares the machine (other runs in flight), bit 2 = role launch on, bit 3 =

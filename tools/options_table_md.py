@@ -28,7 +28,10 @@ md.append("Outside the library: the C++ shim (`host/gact_shim.cpp`) reads `GACT_
           "`-DGACT_LIN_MAX3=0`, `-DGACT_WALK_TEAM=0/1`, `-DGACT_EXP_FAKE_WALK` (DESIGN.md, \"Diagnostic switches\").\n")
 path = os.path.join(ROOT, "INTEGRATION.md")
 s = open(path).read()
+rest = ""
 if "\n## 7. Switches" in s:
+    rest = s[s.index("\n## 7. Switches") + 1:]
+    rest = rest[rest.index("\n## "):] if "\n## " in rest else ""       # (the sections behind this one stay)
     s = s[:s.index("\n## 7. Switches")]
-open(path, "w").write(s.rstrip("\n") + "\n" + "\n".join(md))
+open(path, "w").write(s.rstrip("\n") + "\n" + "\n".join(md) + rest)
 print("INTEGRATION.md 7:", len(rows), "switches")
